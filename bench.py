@@ -11,7 +11,8 @@ rank 0's JSON line; under torchrun it is one of the ranks.  It never prints an `
 A step = reference train.py:272-328 on the MI355X path: boundary masking, two FC-DenseNet57
 forwards, depth scaling, flow-from-depth, sparse-flow loss, depth warping, depth-consistency loss,
 loss.item(), backward, one gradient all-reduce (N > 1), fused clip_grad_norm_(10) + SGD(0.9).
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+Inputs are resident in HBM before the timed region, and every step starts from the seeded initial parameters, so that what
+the steps compute is the same from run to run.  Rank 0 prints ONE JSON line.
 
 --config selects the BASELINE.json workload by its index in ``configs``:
     1   256 x 320, batch 8 per GPU, fp32                                   (default; the metric's configuration)
@@ -279,6 +280,31 @@ def pmc_traffic(family, config=1):
     return entry["traffic_bytes_per_step"], name
 
 
+def dump_outputs(directory, out, model, optimizer):
+    """--dump-outputs: what the last timed step gave its caller, as DIR/<name>.npy -- the StepOutput values (loss, dcl, sfl,
+    grad_norm, skipped as 0 / 1) and the state the step updated in place: the parameters (flat, reference .parameters() order), the
+    BatchNorm running statistics (module order) and the SGD momentum (parameter order).  About 11 MB at every config.  Inputs are
+    seeded and every step starts from the same parameters (train_step in main), so two runs with the same arguments agree to rounding."""
+    import numpy as np
+    import torch
+    with torch.no_grad():
+        bn = torch.cat([b.reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()])
+        momentum = torch.cat([s["momentum_buffer"].reshape(-1) for _, s in sorted(optimizer.state_dict()["state"].items())])
+        arrays = {
+            "loss": np.array([out["loss"]], dtype=np.float32),
+            "dcl": np.array([float(out["dcl"])], dtype=np.float32),
+            "sfl": np.array([float(out["sfl"])], dtype=np.float32),
+            "grad_norm": np.array([float(out["grad_norm"])], dtype=np.float64),
+            "skipped": np.array([1.0 if out["skipped"] else 0.0], dtype=np.float32),
+            "parameters": model.flat_parameters().detach().float().cpu().numpy(),
+            "bn_running_stats": bn.float().cpu().numpy(),
+            "momentum": momentum.float().cpu().numpy(),
+        }
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -289,9 +315,13 @@ def main():
     ap.add_argument("--breakdown", action="store_true", help="print a per-family time table to stderr")
     ap.add_argument("--kernel-option", action="append", default=[], metavar="ID=VALUE",
                     help="development A/B: FCDenseNet57.set_kernel_option(ID, VALUE) (include/endo_hip.h ENDO_OPT_*); recorded in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and env_world <= 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))          # before anything here touches the GPU
@@ -336,6 +366,18 @@ def main():
     step_fn = pkg.train_step.TrainingStep(model, optimizer, height, width, sfl_weight=20.0, dcl_weight=0.1, bf16_storage=bf16_storage and not fp16_storage,
                                           fp16_storage=fp16_storage)
     batch = {k: v.to(dev) for k, v in pkg.synthetic.make_batch(batch_size, height, width, seed=rank, gap_scale=cfg["gap"]).items()}
+    # Every step (warm-up, timed, --breakdown) starts from the seeded initial parameters: one 5.5 MB device copy in front of the step,
+    # on the launch stream.  The gradient kernels sum with floating-point atomics, so a step's gradients vary from run to run in the
+    # last bits, and on this workload a trajectory of training steps grows that into differences of order one within a few steps;
+    # from a fixed starting point every step, and so what the last one computes (--dump-outputs), is the same every run to rounding.
+    # Momentum and BatchNorm running statistics carry on from step to step as in training (sums of such steps: no amplification).
+    params = model.flat_parameters()
+    params0 = params.detach().clone()
+
+    def train_step():
+        with torch.no_grad():
+            params.copy_(params0)
+        return step_fn(batch)
 
     def barrier():
         if world > 1:
@@ -358,7 +400,7 @@ def main():
     serial_steps = min(args.warmup - product_steps, 2)
     for _ in range(args.warmup - product_steps - serial_steps):          # --warmup > 5: the rest, uninstrumented, first
         scheduler.batch_step(batch_iteration=it)
-        step_fn(batch)
+        train_step()
         it += 1
     model.set_kernel_option(5, 0)                                      # ENDO_OPT_WGRAD_OVERLAP off: kernels one at a time
     model.set_wgrad_overlap16(False)                                   # the same for the 16-bit-storage family's handles
@@ -366,7 +408,7 @@ def main():
     lib.endo_prof_enable(all_mask if serial_steps > 0 else 0)
     for _ in range(serial_steps):
         scheduler.batch_step(batch_iteration=it)
-        step_fn(batch)
+        train_step()
         it += 1
     barrier()
     fam_warm = {f: prof_read(lib, f) for f in MFMA_FAMILIES} if serial_steps > 0 else None
@@ -382,7 +424,7 @@ def main():
     lib.endo_prof_enable(all_mask)                                     # (the first launch of each family gets one event pair; nothing else)
     for _ in range(product_steps):
         scheduler.batch_step(batch_iteration=it)
-        step_fn(batch)
+        train_step()
         it += 1
     barrier()
     launches_per_step = {}
@@ -424,7 +466,7 @@ def main():
         if k == sampled_steps and period > 1:
             lib.endo_prof_sample(NEVER)          # the even cover is complete: the rest of the timed region is counted, not timed
         scheduler.batch_step(batch_iteration=it)
-        out = step_fn(batch)
+        out = train_step()
         if pending is not None:
             skipped += int(pending["skipped"])
         pending = out
@@ -451,6 +493,8 @@ def main():
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         torch.distributed.all_gather(gathered, mine)
         per_rank = [float(g) for g in gathered]
+    if args.dump_outputs and rank == 0:          # before anything below runs another training step
+        dump_outputs(args.dump_outputs, pending, model, optimizer)
 
     # second metric of BASELINE.json: depth-warp (+ consistency loss) fwd+bwd, both directions
     warp = pkg.models.DepthWarpingLayer()
@@ -501,7 +545,7 @@ def main():
     if args.breakdown and rank == 0:
         lib.endo_prof_enable(-1)
         scheduler.batch_step(batch_iteration=it)
-        step_fn(batch)
+        train_step()
         torch.cuda.synchronize()
         breakdown = {}
         for f in range(16):

@@ -613,6 +613,21 @@ def reader_case(ref, path):
     all_imgs = oreader.get_color_imgs(seq, visible, crop[0], crop[1], crop[2], crop[3], 4.0)
     clean = oreader.get_clean_point_list(all_imgs, data[3][key], data[6][key], data[5][key], float(data[12]), data[8][key], data[7][key])
     assert np.array_equal(clean, np.asarray(data[9][key])), "the restated contaminated-point filter does not reproduce the reference's list"
+    # what the filter reads of the 35 frames (the .jpg frames are ~12 MB): per frame the pixels its points project to -- a plane of
+    # pixel indices passed as `brightness` makes frame_point_terms return them -- and the filtered brightness there, so that the same
+    # check runs from the repository alone (tests/test_reader.py pins the values of the two committed frames to the live filter)
+    h, w = all_imgs.shape[1:3]
+    probe = np.arange(h * w, dtype=np.float64).reshape(h, w)
+    pixels, values = [], []
+    for i in range(len(visible)):
+        _, _, px = oreader.frame_point_terms(all_imgs[i], np.asarray(data[3][key]).reshape(-1, 4), np.asarray(data[6][key])[:, i], data[5][key], data[8][key][i],
+                                             data[7][key][i], brightness=probe)
+        px = np.unique(px.astype(np.int64))
+        pixels.append(px.astype(np.int32))
+        values.append(oreader.point_brightness(all_imgs[i]).reshape(-1)[px])
+    np.savez_compressed(os.path.join(HERE, "reader_sequence_brightness.npz"), visible_view_indexes=np.array(visible), height=np.array(h),
+                        width=np.array(w), counts=np.array([len(p) for p in pixels]), pixels=np.concatenate(pixels),
+                        brightness=np.concatenate(values))
     out["clean_point_list"] = np.asarray(data[9][key], dtype=np.float32)
     out["inlier_percentage"] = np.array(float(data[12]))
     pts = np.asarray(data[3][key]).reshape(-1, 4)
