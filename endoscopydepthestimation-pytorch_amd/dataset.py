@@ -6,9 +6,11 @@ that batches its samples (train.py:168-178, 254-270), without OpenCV / plyfile /
                         -> scatter.SequenceScatter: point cloud, mask, visibility, per-view matrices resident in HBM
     per sample          utils.generating_pos_and_increment (host RNG, same calls as the reference)
     per batch           SequenceScatter.training_batch -> the 14 non-image tensors, reader.FrameDecoder -> the two colour tensors
+                        (transform=augment.TrainingAugmentation(): decoded to uint8, the albumentations pipeline of train.py:121-142
+                        on the whole batch -- dataset.py:432-447 -- then normalised; without it the reference's validation-phase tensors)
 
-What the reference does per sample and this does not: the albumentations colour / blur / noise augmentations (train.py:121-144;
-out of scope) -- the colour tensors are the normalised frames, i.e. the reference's validation-phase tensors.
+HSV input (is_hsv, train.py --use_hsv_colorspace) together with a transform is refused: the reference converts HSV_FULL back to RGB
+for the augmentations (dataset.py:434-442), which is not built here.
 A sample whose sparse depth masks come out empty is redrawn as in dataset.py:372-376.
 """
 
@@ -63,11 +65,17 @@ class TrainingBatches(object):
                           per thread): 2.2 ms per 1920x1080 frame and thread, so 4 threads put a batch of 8 pairs together in ~9 ms
     prefetch              batches assembled ahead of the consumer by a producer thread on a side stream (the reference's DataLoader
                           workers); 0 = assemble in the caller's thread, on its stream
+    transform             None (the colour tensors are the normalised frames) or an augment.TrainingAugmentation: every frame of every
+                          pair draws its own plan from the transform's generator, in batch order (sample 0 frame 1, sample 0 frame 2,
+                          sample 1 ...) on the assembling thread, never from `rng`: pair selection does not change and the batches do not
+                          depend on reader_threads.  ``last_samples`` / ``last_plan`` hold the samples and the per-sample (frame 1, frame
+                          2) plans of the latest assembled batch (with prefetch, the producer may be one batch ahead of the consumer).
     """
 
     def __init__(self, folder_list, adjacent_range, batch_size, downsampling=4.0, network_downsampling=64, visible_interval=30,
                  precompute_path=None, image_file_names=None, num_iter=None, shuffle=True, rgb_mode="rgb", suggested_h=None,
-                 suggested_w=None, device="cuda", seed=None, inlier_percentage=None, reader_threads=4, prefetch=1, is_hsv=False):
+                 suggested_w=None, device="cuda", seed=None, inlier_percentage=None, reader_threads=4, prefetch=1, is_hsv=False,
+                 transform=None):
         assert len(adjacent_range) == 2
         self.folders = [str(f) for f in folder_list]
         self.adjacent_range = list(adjacent_range)
@@ -76,6 +84,12 @@ class TrainingBatches(object):
         self.rgb_mode = rgb_mode
         self.is_hsv = bool(is_hsv)          # train.py --use_hsv_colorspace: frames enter the network as cv2.COLOR_BGR2HSV_FULL values (dataset.py:439-442)
         self.shuffle = shuffle
+        if transform is not None and self.is_hsv:
+            raise NotImplementedError("is_hsv=True with a transform: the reference augments RGB frames converted back from HSV_FULL "
+                                      "(dataset.py:434-442); that HSV_FULL -> RGB conversion is not implemented")
+        self.transform = transform
+        self.last_samples = None
+        self.last_plan = None
         self.device = torch.device(device)
         self.rng = random.Random(seed)
         if image_file_names is None:
@@ -123,7 +137,9 @@ class TrainingBatches(object):
         with open(path, "rb") as f:
             data = f.read()
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
-            if self.is_hsv:
+            if dst.dtype == torch.uint8:          # (H, W, 3) for the augmentations
+                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, self.rgb_mode, out_u8=dst)
+            elif self.is_hsv:
                 scratch = torch.empty((dst.shape[1], dst.shape[2], 3), dtype=torch.uint8, device=self.device)
                 decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, "bgr", out_u8=scratch)
                 reader.hsv_full(scratch, blue_index=0, out_f32=dst)
@@ -145,6 +161,10 @@ class TrainingBatches(object):
     def _assemble(self, samples):
         """samples: list of (folder, pos, increment).  Returns (batch, per-sample validity)."""
         order, parts = [], []
+        plans = None
+        if self.transform is not None:          # batch order, this thread, the transform's own generator
+            plans = [tuple(self.transform.sample(2)) for _ in samples]
+            self.last_samples, self.last_plan = list(samples), plans
         for folder in sorted(set(s[0] for s in samples)):
             rows = [i for i, s in enumerate(samples) if s[0] == folder]
             seq = self.sequences[folder]
@@ -152,12 +172,20 @@ class TrainingBatches(object):
             part = seq["scatter"].training_batch(positions)
             sh, eh, sw, ew = [int(v) for v in seq["crop_positions"]]
             views = seq["visible_view_indexes"]
-            c1 = torch.empty((len(rows), 3, eh - sh, ew - sw), dtype=torch.float32, device=self.device)
-            c2 = torch.empty_like(c1)
             stream = torch.cuda.current_stream(self.device)
+            frames = None
+            if plans is None:
+                c1 = torch.empty((len(rows), 3, eh - sh, ew - sw), dtype=torch.float32, device=self.device)
+                c2 = torch.empty_like(c1)
+                d1, d2 = c1, c2
+            else:          # uint8 frames [frame 1 of every row, then frame 2 of every row], augmented as one batch below
+                colours = torch.empty((2 * len(rows), 3, eh - sh, ew - sw), dtype=torch.float32, device=self.device)
+                c1, c2 = colours[:len(rows)], colours[len(rows):]
+                frames = torch.empty((2 * len(rows), eh - sh, ew - sw, 3), dtype=torch.uint8, device=self.device)
+                d1, d2 = frames[:len(rows)], frames[len(rows):]
             jobs = []
             for k, (pos, inc) in enumerate(positions):
-                for dst, view in ((c1, views[pos]), (c2, views[pos + inc])):
+                for dst, view in ((d1, views[pos]), (d2, views[pos + inc])):
                     jobs.append((os.path.join(folder, "%08d.jpg" % view), (sh, eh, sw, ew), dst[k], stream))
             if self._pool is None:
                 for job in jobs:
@@ -165,6 +193,9 @@ class TrainingBatches(object):
             else:
                 for done in [self._pool.submit(self._decode_into, *job) for job in jobs]:
                     done.result()
+            if frames is not None:
+                plan = [plans[i][0] for i in rows] + [plans[i][1] for i in rows]
+                self.transform.apply(frames, plan, out_f32=colours)
             part["colors_1"], part["colors_2"] = c1, c2
             order += rows
             parts.append(part)

@@ -40,7 +40,9 @@ extern "C" {
  * adds endo_warp_consistency and endo_warp_fallback_blocks.
  * 4: round 3 -- the 16-bit-storage family (endo_net16_*, endo_net16h_*, endo_bf16_*, endo_f16_*).
  * 5: round 4 -- the non-finite-loss guard moves onto the device: endo_loss_head writes a FOURTH float (the flag),
- * endo_sgd_clip_step takes a `skip_flag` device pointer; endo_net16_offset what = 7; adds endo_hsv_full. */
+ * endo_sgd_clip_step takes a `skip_flag` device pointer; endo_net16_offset what = 7; adds endo_hsv_full.
+ * 6 (unchanged by additions): adds endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the
+ * endo_augment_frame record -- entry points only, no existing signature changes. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -394,6 +396,51 @@ int endo_point_brightness(const uint8_t* imgs, int frames, int height, int width
  * converted image in the reference tree).  src [pixels][3] uint8; out_u8 [pixels][3] (H, S, V) and / or out_f32 [3][pixels] =
  * (x / 255 - 0.5) / 0.5 (dataset.py:446-451); either may be null, src == out_u8 is allowed. */
 int endo_hsv_full(const uint8_t* src, int64_t pixels, int blue_index, uint8_t* out_u8, float* out_f32, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training-phase augmentations -- reference train.py:121-142 (albumentations 0.4.6: OneOf colour / OneOf quality / OneOf noise),
+ * applied to each frame of a pair with its own draws at dataset.py:432-447, then Normalize(0.5, 0.5) (dataset.py:446-451).
+ * One record per frame says what that frame drew (host memory; built by augment.py from its sampler):
+ *   colour   bit 0: every channel through rgb_lut (RandomBrightnessContrast then RandomGamma, composed on the host);
+ *            bit 1: cv2.COLOR_RGB2HSV (8 bit, hue in [0, 180)) -> hsv_lut[0 / 1 / 2] on H / S / V -> cv2.COLOR_HSV2RGB
+ *            (HueSaturationValue; OpenCV's scalar paths, PARITY UNPINNED against cv2 itself)
+ *   spatial  0 none; 1 cv2.blur (BORDER_REFLECT_101); 2 cv2.medianBlur (BORDER_REPLICATE); 3 MotionBlur: cv2.filter2D with the
+ *            k x k 0/1 mask `motion` (bit i * k + j = row i, column j; normalised to sum 1), BORDER_REFLECT_101, the mean of the
+ *            marked taps rounded half to even (cv2's float path may differ by 1 at exact ties: unpinned).  ksize 3, 5 or 7.
+ *   jpeg     1: JpegCompression, cv2.imencode(".jpg") + cv2.imdecode of the RGB array read as B, G, R: 4:2:0, libjpeg-turbo's
+ *            islow FDCT and quantisation with the tables `quant` (natural order, luma then chroma, entries in [1, 255]), decoded
+ *            as libjpeg (islow IDCT, fancy upsampling).  Bit-identical to libjpeg-turbo.
+ *   noise    1 GaussNoise: clip(float(v) + sigma * n, 0, 255) truncated, n independent per pixel and channel;
+ *            2 IAAAdditiveGaussianNoise: clip(round_half_even(v + sigma * n), 0, 255), one n per pixel shared by its 3 channels.
+ *            n from Philox4x32-10 (key `seed`, counter (pixel, frame, 0, 0)) + Box-Muller: independent of the launch geometry.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct endo_augment_frame {
+    int32_t colour;
+    int32_t spatial;
+    int32_t ksize;
+    int32_t jpeg;
+    int32_t noise;
+    float sigma;
+    uint32_t seed[2];
+    uint32_t motion[2];
+    int32_t reserved[6];
+    uint8_t rgb_lut[256];
+    uint8_t hsv_lut[3][256];
+    uint16_t quant[2][64];
+} endo_augment_frame;
+/* sizeof(endo_augment_frame) (1344), for bindings that mirror the record */
+int endo_augment_frame_bytes(void);
+/* device workspace bytes of endo_augment for `frames` frames of height x width (-1 for bad sizes) */
+int64_t endo_augment_workspace_bytes(int frames, int height, int width);
+/* src: device uint8 [frames][H][W][3] RGB (read only); params: HOST array of `frames` records, copied to the workspace on `stream`
+ * (pinned memory for an asynchronous copy; untouched until `stream` has passed the call); out_u8: device uint8 [frames][H][W][3]
+ * and / or out_f32: device fp32 [frames][3][H][W] = (v - 127.5) * (1 / 127.5); either may be NULL, out_u8 == src is allowed.
+ * Five launches whatever the records hold (colour, spatial, JPEG encode, JPEG decode, noise + normalise).  H, W >= 4.
+ * ENDO_E_BADARG for null pointers, bad sizes or a short workspace; ENDO_E_UNSUPPORTED for a record out of range (checked before the
+ * workspace size: an unknown op code, ksize not in {3, 5, 7}, an empty or oversized motion mask, a quantisation entry outside
+ * [1, 255], a negative or non-finite sigma). */
+int endo_augment(const uint8_t* src, const endo_augment_frame* params, int frames, int height, int width, uint8_t* out_u8,
+                 float* out_f32, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* live per-kernel-family timing for bench.py's roofline line: HIP events recorded on the launch
  * stream around every entry of the selected families.  family_mask: bit f enables family f
