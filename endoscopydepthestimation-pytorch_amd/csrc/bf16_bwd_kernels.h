@@ -625,10 +625,7 @@ inline int launch_bf16_wgrad(Wgrad16Params p, float* dw, hipStream_t stream) {
     if (p.partial_cap > 0 && bf16_wgrad_partial_floats(p.cin, p.cout, KS, blocks) > p.partial_cap) return ENDO_E_BADARG;   // never write past the workspace
     constexpr int T = bf16_wgrad_tiles_per_wave(KS), kWgCi = 64 * T;
     const int ci_groups = (p.cin + kWgCi - 1) / kWgCi, co_groups = KS == 3 ? (p.cout + 15) / 16 : (p.cout + kWgCo1 - 1) / kWgCo1;
-    const size_t smem = bf16_wgrad_smem<KS>();
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bf16_wgrad_kernel<KS, T>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-    bf16_wgrad_kernel<KS, T><<<dim3(blocks, ci_groups, co_groups), 256, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
+    ENDO_CHECK(launch_dyn(bf16_wgrad_kernel<KS, T>, dim3(blocks, ci_groups, co_groups), 256, bf16_wgrad_smem<KS>(), stream, p));
     const int64_t per_block = static_cast<int64_t>(co_groups) * 9 * 16 * p.ci_pad;
     bf16_wgrad_reduce_kernel<<<dim3(static_cast<int>((per_block + 255) / 256), (blocks + 63) / 64), 256, 0, stream>>>(p.partial, blocks, co_groups, p.ci_pad, p.cin, p.cout, KS, p.rot,
                                                                                             p.rot_n, dw, p.cin_w > 0 ? p.cin_w : p.cin, p.gscale);

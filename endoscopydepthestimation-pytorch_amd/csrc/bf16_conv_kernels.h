@@ -663,12 +663,7 @@ inline int launch_bf16_conv(const Conv16Params& p_, hipStream_t stream) {
     if ((p.in_blk & 7) || (p.out_blk & 3) || (p.ic0 & (QUADS ? 3 : 7)) || (p.oc0 & 3) || p.in_t % p.in_blk || p.out_t % p.out_blk) return ENDO_E_BADARG;
     const int tiles = ((p.w + kBfTileX - 1) / kBfTileX) * ((p.h + TY - 1) / TY);
     const int ngroups = (p.cout + NT * 16 - 1) / (NT * 16);
-    const size_t smem = bf16_conv_smem<KS, NT, WAVES, TY>(p.cin);
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bf16_conv_kernel<KS, NT, EPI, WAVES, WPE, EXP, UNPOOL, TY>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(smem)));
-    bf16_conv_kernel<KS, NT, EPI, WAVES, WPE, EXP, UNPOOL, TY><<<dim3(tiles, ngroups, p.n), 64 * WAVES, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(bf16_conv_kernel<KS, NT, EPI, WAVES, WPE, EXP, UNPOOL, TY>, dim3(tiles, ngroups, p.n), 64 * WAVES, bf16_conv_smem<KS, NT, WAVES, TY>(p.cin), stream, p);
 }
 
 // ---- weights: W[cout][cin][KS][KS] fp32 -> [chunk][group][tap][nt][16 cout][32 k] bf16 (zero padded) --------------------------------

@@ -269,11 +269,7 @@ inline size_t bf16_dgrad_block_smem() {
 inline int launch_bf16_dgrad_block(const DgradBlock16Params& p, hipStream_t stream) {
     if (p.c0 <= 0 || (p.c0 % 48) || (p.gc0 & 7) || (p.blk & 7)) return ENDO_E_BADARG;
     const int tiles = ((p.w + kBfTileX - 1) / kBfTileX) * ((p.h + kDbTileY - 1) / kDbTileY);
-    const size_t smem = bf16_dgrad_block_smem();
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bf16_dgrad_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-    bf16_dgrad_block_kernel<<<dim3(tiles, p.c0 / 48, p.n), kDbThreads, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(bf16_dgrad_block_kernel, dim3(tiles, p.c0 / 48, p.n), kDbThreads, bf16_dgrad_block_smem(), stream, p);
 }
 
 }  // inline namespace

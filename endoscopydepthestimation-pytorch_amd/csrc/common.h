@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/endo_hip.h"
 
 #define ENDO_CHECK(expr)                                 \
@@ -154,6 +158,71 @@ __device__ __forceinline__ int xcd_remap(int b, int total) {
     const int xcd = b & 7, idx = b >> 3;
     const int q = total >> 3, r = total & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// ---- persistent launches (dgrad_wino3p, td_dgrad, td_fwd): bpg blocks per group walk the group's t_total tiles -------------------------
+// Block r of a group (0 <= r < bpg) takes tiles begin, begin + step, ... < end.  With bpg a multiple of 8, the blocks of an XCD (bpg / 8
+// per group) share one contiguous range of the group's tiles and walk it INTERLEAVED: block idx takes tiles T0 + idx, T0 + idx + bpg / 8,
+// ... -- at any time the XCD's blocks work on neighbouring tiles, whose haloed input windows then meet in the XCD's L2.  (dgrad_wino3p:
+// with a contiguous run per block a 10 x 40 window of 8 x 32 pixels, 48 maps, was fetched again by the block's next tile ~60 us later,
+// after 16 MB of other traffic: 1.8 GB of HBM fetch per level-0 launch for 1.1 GB algorithmic.)  Otherwise one contiguous run per block.
+struct TileWalk {
+    int begin, end, step;
+};
+
+__host__ __device__ __forceinline__ TileWalk persistent_tile_walk(int r, int bpg, int t_total) {
+    if ((bpg & 7) == 0) {
+        const int q = bpg >> 3, xcd = r & 7, idx = r >> 3;
+        return {static_cast<int>(static_cast<int64_t>(xcd * q) * t_total / bpg) + idx, static_cast<int>(static_cast<int64_t>((xcd + 1) * q) * t_total / bpg), q};
+    }
+    return {static_cast<int>(static_cast<int64_t>(r) * t_total / bpg), static_cast<int>(static_cast<int64_t>(r + 1) * t_total / bpg), 1};
+}
+
+// blocks per group: `blocks` shared by `groups`, rounded down to a multiple of 8 (the XCD split above) from 8 on, at most one per tile
+inline int persistent_bpg(int blocks, int groups, int tiles_per_group) {
+    int bpg = blocks / groups;
+    if (bpg >= 8) bpg &= ~7;
+    if (bpg > tiles_per_group) bpg = tiles_per_group;
+    return bpg < 1 ? 1 : bpg;
+}
+
+// ---- launch plumbing -----------------------------------------------------------------------------------------------------------------
+// compute units of the current device, looked up once per device (the persistent kernels launch one or two blocks per CU)
+inline int device_cu_count() {
+    static std::mutex mu;
+    static std::map<int, int> cus;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    int& n = cus[dev];
+    if (n <= 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    return n > 0 ? n : 256;          // (a failed query: the MI355X's count; the launch itself then reports the error)
+}
+
+// The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the pair (kernel, device): raised when a launch needs more
+// than the pair was last given, never on a steady-state launch.  Up to 48 KiB need no attribute.  Keyed by function address (many kernels
+// share a signature); one mutex, as independent handles may launch from several threads.
+inline hipError_t ensure_dynamic_lds(const void* fn, size_t bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> given;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& g = given[{fn, dev}];
+    if (bytes <= g) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (e == hipSuccess) g = bytes;
+    return e;
+}
+
+// kernel<<<grid, block, smem, stream>>>(args...) behind ensure_dynamic_lds; returns the launch's error (ENDO_LAUNCH_CHECK's)
+template <typename... Params, typename... Args>
+inline hipError_t launch_dyn(void (*kernel)(Params...), dim3 grid, dim3 block, size_t smem, hipStream_t stream, Args&&... args) {
+    const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), smem);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, block, smem, stream>>>(std::forward<Args>(args)...);
+    return hipGetLastError();
 }
 
 }  // namespace endo

@@ -696,19 +696,7 @@ inline int launch_conv_dma_vec(ConvParams p, hipStream_t stream) {
     p.bn_cap = (IN == IN_BNRELU) ? ((p.cin + KC - 1) / KC * KC + 15) / 16 * 16 : 0;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
     dim3 grid(p.tiles_x * tiles_y, p.ksplit > 0 ? p.ksplit : (PH >= 0 ? (PH == 2 ? 2 : 1) : (p.cout + 16 * Q - 1) / (16 * Q)), p.n);
-    const size_t smem = S::bytes(p.bn_cap);
-    static size_t configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& configured = configured_by_device[dev & 15];
-    if (smem > 48 * 1024 && smem > configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dma_kernel<KS, KC, Q, IN, EPI, WX, R, NBUF, MINW, VEC, XF, EXP, PH, BF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-        configured = smem;
-    }
-    conv_dma_kernel<KS, KC, Q, IN, EPI, WX, R, NBUF, MINW, VEC, XF, EXP, PH, BF><<<grid, kConvThreads, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(conv_dma_kernel<KS, KC, Q, IN, EPI, WX, R, NBUF, MINW, VEC, XF, EXP, PH, BF>, grid, kConvThreads, S::bytes(p.bn_cap), stream, p);
 }
 
 // 16-byte DMA whenever the input rows are float4-aligned, dword DMA otherwise

@@ -425,24 +425,13 @@ inline int launch_dgrad_block(DgradBlockParams p, hipStream_t stream) {
     using G = DgradBlockGeom<NL, WX, R, GP, VEC>;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured && G::kBytes > 48 * 1024) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_block_kernel<NL, WX, R, GP, EXP, PIPE, VEC, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(G::kBytes)));
-        configured = true;
-    }
     // enough blocks for ~3 per CU: slice the channel group sets when the level has few tiles
     const int tiles = p.tiles_x * tiles_y * p.n;
     const int gsets = ((p.count + 15) / 16 + GP - 1) / GP;
     int ysplit = (768 + tiles - 1) / tiles;
     if (ysplit > gsets) ysplit = gsets;
     if (ysplit < 1) ysplit = 1;
-    dgrad_block_kernel<NL, WX, R, GP, EXP, PIPE, VEC, BF><<<dim3(p.tiles_x * tiles_y, ysplit, p.n), kConvThreads, G::kBytes, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_block_kernel<NL, WX, R, GP, EXP, PIPE, VEC, BF>, dim3(p.tiles_x * tiles_y, ysplit, p.n), kConvThreads, G::kBytes, stream, p);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -681,23 +670,12 @@ inline int launch_dgrad_block8(DgradBlockParams p, hipStream_t stream) {
     using G = DgradBlock8Geom<NL>;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_block8_kernel<NL, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(G::kBytes)));
-        configured = true;
-    }
     const int tiles = p.tiles_x * tiles_y * p.n;
     const int pairs = ((p.count + 15) / 16 + 1) / 2;
     int ysplit = (1024 + tiles - 1) / tiles;          // 4 blocks per CU at the coarse levels (in-job A/B: -1.5 % on the family vs 512)
     if (ysplit > pairs) ysplit = pairs;
     if (ysplit < 1) ysplit = 1;
-    dgrad_block8_kernel<NL, BF><<<dim3(p.tiles_x * tiles_y, ysplit, p.n), G::kThreads, G::kBytes, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_block8_kernel<NL, BF>, dim3(p.tiles_x * tiles_y, ysplit, p.n), G::kThreads, G::kBytes, stream, p);
 }
 
 // 16-byte DMA of the G tile: float4-aligned rows of the gradient maps

@@ -228,19 +228,7 @@ inline int launch_dgrad_dense(ConvParams p, hipStream_t stream) {
     using G = typename D::G;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    const size_t smem = D::bytes(p.cout);
-    static size_t configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& configured = configured_by_device[dev & 15];
-    if (smem > 48 * 1024 && smem > configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_dense_kernel<WX, R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(smem)));
-        configured = smem;
-    }
-    dgrad_dense_kernel<WX, R><<<dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_dense_kernel<WX, R>, dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, D::bytes(p.cout), stream, p);
 }
 
 // persistent kernel where its preconditions hold and there are enough tiles to fill the chip,

@@ -391,31 +391,13 @@ inline int launch_dgrad_newmap(DgradBlockParams p, hipStream_t stream) {
     using G = typename NG::G;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    static bool configured_by_device[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured && NG::kBytes > 48 * 1024) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_newmap_kernel<NL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(NG::kBytes)));
-        configured = true;
-    }
     const int groups = p.group_n > 0 ? p.n / p.group_n : 1;
     const int tiles_per_group = p.tiles_x * tiles_y * (p.group_n > 0 ? p.group_n : p.n);
-    static int cus_by_device[16] = {};
-    int& cus = cus_by_device[dev & 15];
-    if (cus == 0) {
-        hipDeviceProp_t prop;
-        ENDO_CHECK(hipGetDeviceProperties(&prop, dev));
-        cus = prop.multiProcessorCount;
-    }
-    const int resident = cus * NG::kBlocksPerCu / groups;          // blocks per group that are on the chip at once
+    const int resident = device_cu_count() * NG::kBlocksPerCu / groups;          // blocks per group that are on the chip at once
     const int tiles_per_block = (tiles_per_group + resident - 1) / resident;
     int blocks_per_group = (tiles_per_group + tiles_per_block - 1) / tiles_per_block;
     blocks_per_group = (blocks_per_group + 7) / 8 * 8;          // (empty blocks leave at once) a multiple of 8 for the XCD map
-    dgrad_newmap_kernel<NL><<<dim3(groups * blocks_per_group), kConvThreads, NG::kBytes, stream>>>(p, tiles_y, blocks_per_group, tiles_per_block);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_newmap_kernel<NL>, dim3(groups * blocks_per_group), kConvThreads, NG::kBytes, stream, p, tiles_y, blocks_per_group, tiles_per_block);
 }
 
 }  // namespace endo

@@ -479,11 +479,7 @@ inline int launch_dgrad_wino3(DgradBlockParams p, const float* const (&u)[4], hi
     using G = DgradWino3Geom<NL>;
     p.tiles_x = p.w / G::kTileX;
     const int tiles_y = p.h / G::kTileY;
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_wino3_kernel<NL, EXP, OPT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(G::kBytes)));
-    dgrad_wino3_kernel<NL, EXP, OPT><<<dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream>>>(p, u[0], u[1], u[2], u[3]);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_wino3_kernel<NL, EXP, OPT>, dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream, p, u[0], u[1], u[2], u[3]);
 }
 
 }  // namespace endo

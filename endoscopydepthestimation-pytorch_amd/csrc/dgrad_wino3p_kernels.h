@@ -89,21 +89,8 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
     const int r0 = blockIdx.x - grp * bpg;
     const int64_t grp_off = grp * p.gs;
     const int t_total = tiles_xy * gn;
-    // The blocks of an XCD (bpg / 8 per group) share one contiguous range of the group's tiles and walk it INTERLEAVED: block idx takes tiles
-    // T0 + idx, T0 + idx + bpg / 8, ... -- at any time the XCD's blocks work on neighbouring tiles, whose haloed gradient windows (10 x 40 of
-    // 8 x 32 pixels, 48 maps) then meet in the XCD's L2.  With a contiguous run per block a window's lines were fetched again by the block's
-    // next tile ~60 us later, after 16 MB of other traffic: 1.8 GB of HBM fetch per level-0 launch for 1.1 GB algorithmic (r06_b PMC passes).
-    int t_begin, t_end, t_step;
-    if ((bpg & 7) == 0) {
-        const int q = bpg >> 3, xcd = r0 & 7, idx = r0 >> 3;
-        t_begin = static_cast<int>(static_cast<int64_t>(xcd * q) * t_total / bpg) + idx;
-        t_end = static_cast<int>(static_cast<int64_t>((xcd + 1) * q) * t_total / bpg);
-        t_step = q;
-    } else {
-        t_begin = static_cast<int>(static_cast<int64_t>(r0) * t_total / bpg);
-        t_end = static_cast<int>(static_cast<int64_t>(r0 + 1) * t_total / bpg);
-        t_step = 1;
-    }
+    const TileWalk walk = persistent_tile_walk(r0, bpg, t_total);          // the XCD-interleaved walk (common.h)
+    const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_g = smem;                               // [NL*12][kCS]
@@ -684,16 +671,9 @@ inline int launch_dgrad_wino3p(DgradBlockParams p, const float* const (&u)[4], i
     const int tiles_xy = p.tiles_x * (p.h / G::kTileY);
     const int groups = p.group_n > 0 ? p.n / p.group_n : 1;
     const int gn = p.group_n > 0 ? p.group_n : p.n;
-    int bpg = blocks / groups;
-    if (bpg >= 8) bpg &= ~7;
-    if (bpg > tiles_xy * gn) bpg = tiles_xy * gn;
-    if (bpg < 1) bpg = 1;
+    const int bpg = persistent_bpg(blocks, groups, tiles_xy * gn);
     if (blocks_used) *blocks_used = bpg * groups;
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_wino3p_kernel<NL, FW, EXP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(G::kBytes)));
-    dgrad_wino3p_kernel<NL, FW, EXP><<<dim3(bpg * groups), G::kThreads, G::kBytes, stream>>>(p, u[0], u[1], u[2], u[3], tiles_xy, gn, bpg, fw_parts);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_wino3p_kernel<NL, FW, EXP>, dim3(bpg * groups), G::kThreads, G::kBytes, stream, p, u[0], u[1], u[2], u[3], tiles_xy, gn, bpg, fw_parts);
 }
 
 }  // namespace endo

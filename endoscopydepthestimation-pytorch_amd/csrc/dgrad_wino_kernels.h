@@ -340,18 +340,7 @@ inline int launch_dgrad_wino8(DgradBlockParams p, const float* const (&u)[4], hi
     using G = DgradWino8Geom<NL>;
     p.tiles_x = p.w / G::kTileX;
     const int tiles_y = p.h / G::kTileY;
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_wino8_kernel<NL, EXP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(G::kBytes)));
-        configured = true;
-    }
-    dgrad_wino8_kernel<NL, EXP><<<dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream>>>(p, u[0], u[1], u[2], u[3]);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(dgrad_wino8_kernel<NL, EXP>, dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream, p, u[0], u[1], u[2], u[3]);
 }
 
 }  // namespace endo

@@ -173,7 +173,6 @@ struct endo_net {
     int64_t gplane_off;       // float offset in gradws of g = grad_out * sign(pre), one plane per sample (final_g_kernel)
     int64_t bias_parts_off;   // float offset in gradws (group 0's) of prep_dy's per-block sums of G (BiasParts), bias_parts_floats long
     int64_t fw_parts_off;     // float offset in gradws (group 0's) of the persistent base pass's final-conv weight partials (kFwPartBlocks x 192 doubles)
-    int cus;                  // compute units of the device the handle was created on: the persistent kernels launch one block per CU
     int64_t bias_parts_floats;
     int64_t gradws_floats;
     // Weight gradients run on a side stream: a layer's wgrad depends only on its prepared dY and the forward tape, nothing on the
@@ -840,7 +839,7 @@ static int td_fwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
     ProfScope prof(kProfConv1x1Pool, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1),
                    4.0 * c.nt() * c.net->lv[level].plane * (cv.cin + cv.cout / 4.0));
     // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, all output channels per tile (td_fwd_kernels.h)
-    if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 2) && !mfma_bf16_fwd(c) && c.training && td_fwd_ok(p)) return launch_td_fwd(p, c.net->cus, c.stream);
+    if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 2) && !mfma_bf16_fwd(c) && c.training && td_fwd_ok(p)) return launch_td_fwd(p, device_cu_count(), c.stream);
     if (mfma_bf16_fwd(c)) return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4, 2, 1, 1>(p, c.stream);
     return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4>(p, c.stream);    // 32x8 tiles: -6 % in the in-job A/B (Q = 6 was 10 % slower; round 5: K-chunks of 16 channels +-0, of 32 +40 % on the family, Q = 6 with 16 +14 %)
 }
@@ -1123,7 +1122,7 @@ static int dense_block_bwd(const Ctx& c, int level, int ic0, int c0, const BnP* 
                 // persistent blocks, one per CU; with fv->base_w they leave per-block partials of dW_final[ic0 .. ic0 + c0), added up here
                 double* fwp = (fv && fv->base && fv->base_w) ? reinterpret_cast<double*>(c.gradws + c.net->fw_parts_off) : nullptr;
                 int used = 0;
-                rc = run_dgrad_wino3p_nl4(p, u, c.net->cus < kFwPartBlocks ? c.net->cus : kFwPartBlocks, fwp, &used, c.stream);
+                rc = run_dgrad_wino3p_nl4(p, u, std::min(device_cu_count(), kFwPartBlocks), fwp, &used, c.stream);
                 if (rc == 0 && fwp) {
                     final_w_reduce_kernel<<<c0, 64, 0, c.stream>>>(fwp, used, c0, fv->gw + ic0);
                     ENDO_LAUNCH_CHECK();
@@ -1190,7 +1189,7 @@ static int td_bwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
         // pooled rows of whole code dwords -> LDS-DMA kernel; otherwise the register-staged one
         // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, 16-byte DMA (td_dgrad_kernels.h)
         if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 1) && !mfma_bf16_dgrad(c) && td_dgrad_ok(p))
-            rc = launch_td_dgrad(p, c.net->cus, c.stream);
+            rc = launch_td_dgrad(p, device_cu_count(), c.stream);
         else if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 1) && !mfma_bf16_dgrad(c) && nx.w % 4 != 0 && td_dgrad_small_ok(p))
             // pooled rows without whole code dwords (level 4 of configs[1]: 8 x 10): 128-pixel runs, the routed gradient expanded on its way into
             // LDS -- 46 instead of the register-staged kernel's 100 us.  (At levels 2 / 3 the LDS-DMA kernel stays: 103 / 63 against 139 / 69 us, tools/td_bench)
@@ -1321,11 +1320,6 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     }
     net->fw_parts_off = net->bias_parts_off + align_up(net->bias_parts_floats, 64);
     net->gradws_floats = net->fw_parts_off + 2 * static_cast<int64_t>(kFwPartBlocks) * 192;
-    {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        net->cus = cus;
-    }
     // one stride for both buffers keeps the kernels' group arithmetic to a single number; the caller allocates
     // groups * gs floats for each when groups > 1 (the two sizes differ by a few per cent)
     net->gs = align_up(net->tape_floats > net->gradws_floats ? net->tape_floats : net->gradws_floats, 64);

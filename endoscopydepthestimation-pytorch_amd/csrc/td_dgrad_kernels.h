@@ -49,19 +49,10 @@ __global__ void __launch_bounds__(512, 2) td_dgrad_kernel(const ConvParams p, in
     const int r0 = blockIdx.x - grp * bpg;
     const int64_t grp_off = grp * p.gs;
     const int t_total = tiles_xy * gn;
-    // the blocks of an XCD (bpg / 8 per group) share one contiguous tile range and walk it interleaved (dgrad_wino3p_kernels.h): a tile's
-    // pooled rows are 64 bytes and its code rows 16 bytes of 128-byte lines whose rest belongs to the tiles beside it
-    int t_begin, t_end, t_step;
-    if ((bpg & 7) == 0) {
-        const int q8 = bpg >> 3, xcd = r0 & 7, idx = r0 >> 3;
-        t_begin = static_cast<int>(static_cast<int64_t>(xcd * q8) * t_total / bpg) + idx;
-        t_end = static_cast<int>(static_cast<int64_t>((xcd + 1) * q8) * t_total / bpg);
-        t_step = q8;
-    } else {
-        t_begin = static_cast<int>(static_cast<int64_t>(r0) * t_total / bpg);
-        t_end = static_cast<int>(static_cast<int64_t>(r0 + 1) * t_total / bpg);
-        t_step = 1;
-    }
+    // the XCD-interleaved walk (common.h): a tile's pooled rows are 64 bytes and its code rows 16 bytes of 128-byte lines whose rest belongs
+    // to the tiles beside it
+    const TileWalk walk = persistent_tile_walk(r0, bpg, t_total);
+    const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_w = smem;                                   // [o][kWS]
@@ -294,14 +285,8 @@ inline int launch_td_dgrad_t(ConvParams p, int blocks, hipStream_t stream) {
     const int tiles_xy = p.tiles_x * (p.h / G::kTileY);
     const int groups = p.group_n > 0 ? p.n / p.group_n : 1;
     const int gn = p.group_n > 0 ? p.group_n : p.n;
-    int bpg = blocks / groups;
-    if (bpg >= 8) bpg &= ~7;
-    if (bpg > tiles_xy * gn) bpg = tiles_xy * gn;
-    if (bpg < 1) bpg = 1;
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(td_dgrad_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G::kBytes)));
-    td_dgrad_kernel<C><<<dim3(bpg * groups), G::kThreads, G::kBytes, stream>>>(p, tiles_xy, gn, bpg);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    const int bpg = persistent_bpg(blocks, groups, tiles_xy * gn);
+    return launch_dyn(td_dgrad_kernel<C>, dim3(bpg * groups), G::kThreads, G::kBytes, stream, p, tiles_xy, gn, bpg);
 }
 
 inline int launch_td_dgrad(const ConvParams& p, int blocks, hipStream_t stream) {

@@ -57,19 +57,10 @@ __global__ void __launch_bounds__(64 * WAVES, 2) td_fwd_kernel(const ConvParams 
     const int r0 = blockIdx.x - grp * bpg;
     const ConvParams p = group_view(p0, grp);
     const int t_total = tiles_xy * gn;
-    // the blocks of an XCD (bpg / 8 per group) share one contiguous tile range and walk it interleaved (dgrad_wino3p_kernels.h): a tile's
-    // pooled rows are 64 bytes and its code rows 16 bytes of 128-byte lines whose rest belongs to the tiles beside it
-    int t_begin, t_end, t_step;
-    if ((bpg & 7) == 0) {
-        const int q8 = bpg >> 3, xcd = r0 & 7, idx = r0 >> 3;
-        t_begin = static_cast<int>(static_cast<int64_t>(xcd * q8) * t_total / bpg) + idx;
-        t_end = static_cast<int>(static_cast<int64_t>((xcd + 1) * q8) * t_total / bpg);
-        t_step = q8;
-    } else {
-        t_begin = static_cast<int>(static_cast<int64_t>(r0) * t_total / bpg);
-        t_end = static_cast<int>(static_cast<int64_t>(r0 + 1) * t_total / bpg);
-        t_step = 1;
-    }
+    // the XCD-interleaved walk (common.h): a tile's pooled rows are 64 bytes and its code rows 16 bytes of 128-byte lines whose rest belongs
+    // to the tiles beside it
+    const TileWalk walk = persistent_tile_walk(r0, bpg, t_total);
+    const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_w = smem;                                   // [c][kWS]: W[o][c] TRANSPOSED (a B fragment's lanes run over o: contiguous; its k-lanes over c: rows)
@@ -260,14 +251,8 @@ inline int launch_td_fwd_t(ConvParams p, int blocks, hipStream_t stream) {
     const int tiles_xy = p.tiles_x * (p.h / G::kTileY);
     const int groups = p.group_n > 0 ? p.n / p.group_n : 1;
     const int gn = p.group_n > 0 ? p.group_n : p.n;
-    int bpg = blocks * (WAVES == 8 ? 1 : 2) / groups;          // one or two blocks per CU
-    if (bpg >= 8) bpg &= ~7;
-    if (bpg > tiles_xy * gn) bpg = tiles_xy * gn;
-    if (bpg < 1) bpg = 1;
-    ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(td_fwd_kernel<C, WAVES, EXP>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G::kBytes)));
-    td_fwd_kernel<C, WAVES, EXP><<<dim3(bpg * groups), G::kThreads, G::kBytes, stream>>>(p, tiles_xy, gn, bpg);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    const int bpg = persistent_bpg(blocks * (WAVES == 8 ? 1 : 2), groups, tiles_xy * gn);          // one or two blocks per CU
+    return launch_dyn(td_fwd_kernel<C, WAVES, EXP>, dim3(bpg * groups), G::kThreads, G::kBytes, stream, p, tiles_xy, gn, bpg);
 }
 
 // blocks = compute units of the device

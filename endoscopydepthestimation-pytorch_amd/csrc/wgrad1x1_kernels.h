@@ -269,18 +269,7 @@ inline int launch_wgrad1x1_dma_shape(const WgradParams& p, hipStream_t stream) {
     int splits = 256 * per_cu / (tiles_co * tiles_ci);
     if (splits < 1) splits = 1;
     if (splits > chunks_total) splits = chunks_total;
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_dma_kernel<BF, QO, QI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(G::kBytes)));
-        configured = true;
-    }
-    wgrad1x1_dma_kernel<BF, QO, QI><<<dim3(splits, tiles_co, tiles_ci), 64 * G::kWaves, G::kBytes, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(wgrad1x1_dma_kernel<BF, QO, QI>, dim3(splits, tiles_co, tiles_ci), 64 * G::kWaves, G::kBytes, stream, p);
 }
 
 // shape: 0 = the one whose tiles cover cout x cin with the fewer MFMAs (2 x 2 on a tie), 1 / 2 = 2 x 2, 3 x 1 (tools/tdw_bench; 5 x 1 waves on

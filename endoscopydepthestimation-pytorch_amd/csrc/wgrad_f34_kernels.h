@@ -504,15 +504,7 @@ inline int launch_wgrad_f34(const WgradParams& p, float* scratch, hipStream_t st
     static_assert(!PREP || RAW, "the fused gradient preparation belongs to the first convolution's form");
     const F34Plan plan = wgrad_f34_plan(p, blocks / 2, RAW);
     constexpr int lds = 4 * 2 * kF34Xs * 4;          // 67,584 bytes per block, two blocks per CU
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!configured_by_device[dev & 15]) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f34_kernel<EXP, RAW, PREP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        configured_by_device[dev & 15] = true;
-    }
-    wgrad_f34_kernel<EXP, RAW, PREP><<<blocks, kConvThreads, lds, stream>>>(p, scratch, plan);
-    ENDO_LAUNCH_CHECK();
+    ENDO_CHECK(launch_dyn(wgrad_f34_kernel<EXP, RAW, PREP>, blocks, kConvThreads, lds, stream, p, scratch, plan));
     if (batch && !RAW && batch->count < 4) {
         const int k = batch->count++;
         batch->partial[k] = scratch; batch->dw[k] = p.dw; batch->plan[k] = plan; batch->cin[k] = p.cin;

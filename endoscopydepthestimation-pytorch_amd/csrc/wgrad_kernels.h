@@ -295,19 +295,7 @@ inline int launch_wgrad(const WgradParams& p, hipStream_t stream) {
     if (groups > 384) groups = 384;
     if (groups > tiles_total) groups = tiles_total;
     dim3 grid(ci_chunks, groups, co_sets);
-    constexpr size_t smem = wgrad_smem_bytes<KS, Q>();
-    static bool configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& configured = configured_by_device[dev & 15];
-    if (!configured && smem > 48 * 1024) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_mfma_kernel<KS, Q, IN, DY>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-        configured = true;
-    }
-    wgrad_mfma_kernel<KS, Q, IN, DY><<<grid, kConvThreads, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(wgrad_mfma_kernel<KS, Q, IN, DY>, grid, kConvThreads, wgrad_smem_bytes<KS, Q>(), stream, p);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -375,18 +375,7 @@ inline int launch_wino4_fwd_t(ConvParams p, hipStream_t stream) {
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     p.bn_cap = (p.cin + 15) / 16 * 16;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    const size_t smem = G::bytes(p.bn_cap);
-    static size_t configured_by_device[16] = {};          // the attribute belongs to the (function, device) pair
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& configured = configured_by_device[dev & 15];
-    if (smem > configured) {
-        ENDO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_fwd_kernel<FIN>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-        configured = smem;
-    }
-    wino4_fwd_kernel<FIN><<<dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, smem, stream>>>(p);
-    ENDO_LAUNCH_CHECK();
-    return 0;
+    return launch_dyn(wino4_fwd_kernel<FIN>, dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, G::bytes(p.bn_cap), stream, p);
 }
 // with p.fin_w / p.fin_out set: the launch also forms the final convolution's sum over its input channels (wino4_fwd_kernel<true>)
 inline int launch_wino4_fwd(const ConvParams& p, hipStream_t stream) {

@@ -41,8 +41,9 @@ extern "C" {
  * 4: round 3 -- the 16-bit-storage family (endo_net16_*, endo_net16h_*, endo_bf16_*, endo_f16_*).
  * 5: round 4 -- the non-finite-loss guard moves onto the device: endo_loss_head writes a FOURTH float (the flag),
  * endo_sgd_clip_step takes a `skip_flag` device pointer; endo_net16_offset what = 7; adds endo_hsv_full.
- * 6 (unchanged by additions): adds endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the
- * endo_augment_frame record -- entry points only, no existing signature changes. */
+ * 6: round 6 -- adds endo_warp_consistency_bytes, the option ENDO_OPT_TD_PERSIST and the value ENDO_OPT_WINO_DGRAD = 3; since then
+ * (unchanged by additions) endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the endo_augment_frame
+ * record -- entry points only, no existing signature changes. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */

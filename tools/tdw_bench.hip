@@ -1,5 +1,5 @@
 // The transition-down 1x1 weight gradient stand-alone (csrc/wgrad1x1_kernels.h): the 16-byte-DMA kernel against round 5's dword-DMA form
-// (tools/scratch/wgrad1x1_old_kernels.h, a renamed copy kept for this comparison) -- time and the difference of the two dW.  Development tool.
+// (tools/wgrad1x1_old_kernels.h, a renamed copy kept for this comparison) -- time and the difference of the two dW.  Development tool.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics tools/tdw_bench.hip -o tools/bin/tdw_bench
 //   tools/bin/tdw_bench [c] [n] [h] [w]
 #include <cstdio>
@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad1x1_kernels.h"
-#include "scratch/wgrad1x1_old_kernels.h"
+#include "wgrad1x1_old_kernels.h"
 
 using namespace endo;
 

@@ -13,8 +13,8 @@
 // LDS rows: x stride 66 (== 2 mod 32) and G stride 21 (odd): both fragment reads are bank-conflict free.
 
 
-#include "../../endoscopydepthestimation-pytorch_amd/csrc/conv_dma_kernels.h"
-#include "../../endoscopydepthestimation-pytorch_amd/csrc/wgrad_kernels.h"
+#include "../endoscopydepthestimation-pytorch_amd/csrc/conv_dma_kernels.h"
+#include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad_kernels.h"
 
 namespace endo {
 
