@@ -2,7 +2,7 @@
 """Headline benchmark: training frame-pairs/s of the full hot-path step (BASELINE.json metric) on
 synthetic frame pairs -- by default config 2 of BASELINE.json (configs[1]): 256 x 320, batch 8 per GPU, fp32.
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4|5|6]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4|5|6] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment the script starts N fresh rank processes itself
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py``, before this process touches the GPU) and relays
@@ -25,15 +25,19 @@ the steps compute is the same from run to run.  Rank 0 prints ONE JSON line.
     5   (not a BASELINE config) 256 x 320, batch 8 per GPU, bf16 MFMA operands over fp32 tensors: the mixed-precision mode of the
         fp32 family (round 2's --config 2)
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line.  Extra objects on that line:
   roofline             the dominant kernel family (dense-layer conv3x3 forward/dgrad/wgrad: whichever took the most
                        time in the warm-up steps, where all three carry HIP events), algorithmic FLOPs / HIP-event time
-                       of its launches measured live over the timed steps, on the launch stream; traffic = HBM bytes per
-                       launch from the rocprofv3 PMC passes committed under profiles/ (tools/pmc_traffic.py)
+                       of its launches measured live over the timed steps, on the launch stream
+  roofline_serial      the same families one kernel at a time, from the warm-up steps
+
+--full adds what takes work of its own after the timed steps (the timed steps and the figures above are the same either way):
+  roofline.traffic     HBM bytes per launch from the rocprofv3 PMC passes committed under profiles/ (tools/pmc_traffic.py);
+                       dispatches_per_step likewise from the kernel-trace summary there
   roofline_depth_warp  the second BASELINE metric (depth-warp fwd+bwd, both directions, + the consistency loss that
                        consumes it): HBM bound; algorithmic bytes / HIP-event kernel time, and the host-inclusive ms/pair
   cpu_baseline         the CPU oracle (oracle/, a port of the reference path) timed on this host's physical cores on a
-                       bounded sample of the same workload (the GPU batch size) and at batch 1
+                       bounded sample of the same workload (the GPU batch size) and at batch 1 (not with --no-cpu-baseline)
 """
 
 import argparse
@@ -305,13 +309,74 @@ def dump_outputs(directory, out, model, optimizer):
         np.save(os.path.join(directory, name + ".npy"), arr)
 
 
+def depth_warp_roofline(pkg, lib, batch, batch_size, height, width, dev):
+    """--full: the second metric of BASELINE.json, depth-warp (+ consistency loss) fwd+bwd, both directions, timed on its own
+    after the training steps -> the line's roofline_depth_warp."""
+    import torch
+    warp = pkg.models.DepthWarpingLayer()
+    dcl = pkg.losses.NormalizedDistanceLoss(height, width)
+    d1 = pkg.synthetic.smooth_depth(batch_size, height, width, seed=1).to(dev).requires_grad_(True)
+    d2 = pkg.synthetic.smooth_depth(batch_size, height, width, seed=2).to(dev).requires_grad_(True)
+
+    def warp_both():
+        w21, i1 = warp([d1, d2, batch["boundaries"], batch["translations_1_wrt_2"], batch["rotations_1_wrt_2"], batch["intrinsics"]])
+        w12, i2 = warp([d2, d1, batch["boundaries"], batch["translations_2_wrt_1"], batch["rotations_2_wrt_1"], batch["intrinsics"]])
+        loss = dcl([d1, w21, i1, batch["intrinsics"]]) + dcl([d2, w12, i2, batch["intrinsics"]])
+        d1.grad = d2.grad = None
+        loss.backward()
+
+    def warp_both_fused():          # the same chain as ONE library call (endo_warp_consistency): what the metric is quoted on
+        with torch.no_grad():
+            return pkg.losses.warp_consistency(d1, d2, batch["boundaries"], batch["translations_1_wrt_2"], batch["rotations_1_wrt_2"],
+                                               batch["translations_2_wrt_1"], batch["rotations_2_wrt_1"], batch["intrinsics"],
+                                               dcl_weight=2.0)
+
+    reps = 20
+
+    def host_inclusive(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        tw = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - tw) / reps / batch_size * 1e3
+
+    warp_ms_per_pair_modules = host_inclusive(warp_both)
+    warp_ms_per_pair = host_inclusive(warp_both_fused)
+    # device time of the same call: ONE pair of events around `reps` back-to-back calls on the launch stream (round 3 put events
+    # around every entry point of the composed chain, which serialised its 11 launches and read SLOWER than the host-inclusive
+    # figure); algorithmic bytes as SURVEY.md 8(d) counts them: 160 B per pixel and pair (both directions, forward and backward)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    for _ in range(reps):
+        warp_both_fused()
+    ev1.record()
+    torch.cuda.synchronize()
+    warp_kernel_ms = ev0.elapsed_time(ev1) / reps
+    warp_bytes = float(lib.endo_warp_consistency_bytes(batch_size, height, width))          # the library's own count (160 B per pixel of a pair)
+    warp_gbs = warp_bytes / warp_kernel_ms / 1e6 if warp_kernel_ms > 0 else 0.0
+    return {
+        "kernel": "depth_warp fwd+bwd (both directions) + depth-consistency loss fwd+bwd", "bound": "hbm",
+        "achieved": warp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": warp_gbs / HBM_PEAK_GBS, "traffic": None,
+        "algorithmic_bytes_per_pair": warp_bytes / batch_size,
+        "time_base": "device time of endo_warp_consistency (1 memset + 2 kernels), one event pair around %d back-to-back calls" % reps,
+        "device_ms_per_pair": warp_kernel_ms / batch_size,
+        "host_inclusive_ms_per_pair": warp_ms_per_pair,
+        "host_inclusive_ms_per_pair_through_the_modules_and_autograd": warp_ms_per_pair_modules}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS), help="index into BASELINE.json configs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the figures that need work of their own: profile lookups, the depth-warp "
+                         "roofline and the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--breakdown", action="store_true", help="print a per-family time table to stderr")
     ap.add_argument("--kernel-option", action="append", default=[], metavar="ID=VALUE",
                     help="development A/B: FCDenseNet57.set_kernel_option(ID, VALUE) (include/endo_hip.h ENDO_OPT_*); recorded in the line")
@@ -496,50 +561,7 @@ def main():
     if args.dump_outputs and rank == 0:          # before anything below runs another training step
         dump_outputs(args.dump_outputs, pending, model, optimizer)
 
-    # second metric of BASELINE.json: depth-warp (+ consistency loss) fwd+bwd, both directions
-    warp = pkg.models.DepthWarpingLayer()
-    dcl = pkg.losses.NormalizedDistanceLoss(height, width)
-    d1 = pkg.synthetic.smooth_depth(batch_size, height, width, seed=1).to(dev).requires_grad_(True)
-    d2 = pkg.synthetic.smooth_depth(batch_size, height, width, seed=2).to(dev).requires_grad_(True)
-
-    def warp_both():
-        w21, i1 = warp([d1, d2, batch["boundaries"], batch["translations_1_wrt_2"], batch["rotations_1_wrt_2"], batch["intrinsics"]])
-        w12, i2 = warp([d2, d1, batch["boundaries"], batch["translations_2_wrt_1"], batch["rotations_2_wrt_1"], batch["intrinsics"]])
-        loss = dcl([d1, w21, i1, batch["intrinsics"]]) + dcl([d2, w12, i2, batch["intrinsics"]])
-        d1.grad = d2.grad = None
-        loss.backward()
-
-    def warp_both_fused():          # the same chain as ONE library call (endo_warp_consistency): what the metric is quoted on
-        with torch.no_grad():
-            return pkg.losses.warp_consistency(d1, d2, batch["boundaries"], batch["translations_1_wrt_2"], batch["rotations_1_wrt_2"],
-                                               batch["translations_2_wrt_1"], batch["rotations_2_wrt_1"], batch["intrinsics"],
-                                               dcl_weight=2.0)
-
-    reps = 20
-
-    def host_inclusive(fn):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        tw = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - tw) / reps / batch_size * 1e3
-
-    warp_ms_per_pair_modules = host_inclusive(warp_both)
-    warp_ms_per_pair = host_inclusive(warp_both_fused)
-    # device time of the same call: ONE pair of events around `reps` back-to-back calls on the launch stream (round 3 put events
-    # around every entry point of the composed chain, which serialised its 11 launches and read SLOWER than the host-inclusive
-    # figure); algorithmic bytes as SURVEY.md 8(d) counts them: 160 B per pixel and pair (both directions, forward and backward)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(reps):
-        warp_both_fused()
-    ev1.record()
-    torch.cuda.synchronize()
-    warp_kernel_ms = ev0.elapsed_time(ev1) / reps
-    warp_bytes = float(lib.endo_warp_consistency_bytes(batch_size, height, width))          # the library's own count (160 B per pixel of a pair)
+    depth_warp = depth_warp_roofline(pkg, lib, batch, batch_size, height, width, dev) if args.full else None
 
     breakdown = None
     if args.breakdown and rank == 0:
@@ -569,12 +591,11 @@ def main():
     ms, cnt, fl, by = fam[dominant]
     achieved = fl / ms / 1e9 if ms > 0 else 0.0                         # TFLOP/s
     dom_name = lib.endo_prof_family_name(dominant).decode()
-    traffic, traffic_src = (None, None)
-    if args.config in (1, 2, 4, 5):
+    traffic, traffic_src = (None, None) if args.full else (None, "not read: bench.py --full reads it from profiles/")
+    if args.full and args.config in (1, 2, 4, 5):
         traffic, traffic_src = pmc_traffic(dom_name, args.config)      # bytes per step -> per launch with the launches counted here
     if traffic is not None:
         traffic = traffic / (seen[dominant] / args.steps) if seen[dominant] else None
-    warp_gbs = warp_bytes / warp_kernel_ms / 1e6 if warp_kernel_ms > 0 else 0.0
     result = {
         "metric": cfg["metric"],
         "value": pairs / elapsed,
@@ -597,9 +618,7 @@ def main():
         "per_rank_pairs_per_s": per_rank,
         "skipped_steps": skipped,
         "kernel_options_overridden": args.kernel_option or None,
-        "dispatches_per_step": dispatches_per_step(args.config),
         "conv_roofline_frac_whole_step": (pairs / elapsed) * pair_gflop / 1e3 / (FP32_MFMA_PEAK_TFLOPS * world),
-        "depth_warp_fwd_bwd_ms_per_pair": warp_ms_per_pair,
         "roofline": {"kernel": dom_name, "bound": "mfma", "achieved": achieved,
                      "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS,
                      "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC 2*FETCH_SIZE+WRITE_SIZE)",
@@ -626,14 +645,6 @@ def main():
             "frac": fam_warm[dominant][2] / fam_warm[dominant][0] / 1e9 / FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
             "families_ms_per_step": {lib.endo_prof_family_name(f).decode(): fam_warm[f][0] / serial_steps for f in MFMA_FAMILIES},
             "families_tflops": {lib.endo_prof_family_name(f).decode(): fam_warm[f][2] / fam_warm[f][0] / 1e9 for f in MFMA_FAMILIES}},
-        "roofline_depth_warp": {
-            "kernel": "depth_warp fwd+bwd (both directions) + depth-consistency loss fwd+bwd", "bound": "hbm",
-            "achieved": warp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": warp_gbs / HBM_PEAK_GBS, "traffic": None,
-            "algorithmic_bytes_per_pair": warp_bytes / batch_size,
-            "time_base": "device time of endo_warp_consistency (1 memset + 2 kernels), one event pair around %d back-to-back calls" % reps,
-            "device_ms_per_pair": warp_kernel_ms / batch_size,
-            "host_inclusive_ms_per_pair": warp_ms_per_pair,
-            "host_inclusive_ms_per_pair_through_the_modules_and_autograd": warp_ms_per_pair_modules},
     }
     if bf16 or bf16_storage:
         # with bf16 operands the matrix work is ~1/8 of the fp32 kernels' and the dense-layer families are bound by HBM / LDS / VALU:
@@ -656,8 +667,12 @@ def main():
                 result["roofline_serial"].pop("families_tflops", None)
         else:
             result["roofline_serial"] = None
-    if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only
-        result["cpu_baseline"] = cpu_baseline(cfg)
+    if args.full:
+        result["dispatches_per_step"] = dispatches_per_step(args.config)
+        result["depth_warp_fwd_bwd_ms_per_pair"] = depth_warp["host_inclusive_ms_per_pair"]
+        result["roofline_depth_warp"] = depth_warp
+        if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only
+            result["cpu_baseline"] = cpu_baseline(cfg)
     print(json.dumps(result))
     sys.stdout.flush()
     if world > 1:

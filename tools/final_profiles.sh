@@ -27,7 +27,7 @@ python3 $R/tools/pmc_sq_report.py $O/${TAG}_sq_counters.txt /tmp/sq1/s_results.d
 cd $R
 # the bench line reads profiles/*_pmc_traffic.json and *_kernel_stats.json of THIS source revision: put them in place first
 cp $O/${TAG}_pmc_traffic.json $O/${TAG}_kernel_stats.json $R/profiles/
-python bench.py > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
 # the bf16-storage mode (bench.py --config 2): kernel trace, HBM traffic of its families, its bench line
 cd /tmp
 rocprofv3 --kernel-trace --stats -d /tmp/kt2 -o kt -- python3 $R/bench.py --config 2 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config2_under_rocprof.json 2> $O/kt2.err
@@ -38,9 +38,9 @@ rocprofv3 --pmc WRITE_SIZE -d /tmp/pw2 -o w -- python3 $R/bench.py --config 2 --
 python3 $R/tools/pmc_traffic.py /tmp/pf2/f_results.db /tmp/pw2/w_results.db $O/${TAG}_pmc_traffic_config2.json 7 "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python3 bench.py --config 2 --steps 5 --warmup 2 --no-cpu-baseline" > $O/pmc_traffic2.log 2>&1
 cd $R
 cp $O/${TAG}_pmc_traffic_config2.json $O/${TAG}_kernel_stats_config2.json $R/profiles/
-python bench.py --config 2 --no-cpu-baseline > $O/${TAG}_bench_config2.json 2> $O/bench2.err
-python bench.py --config 4 --no-cpu-baseline > $O/${TAG}_bench_config4.json 2> $O/bench4.err
-python bench.py --config 3 --no-cpu-baseline > $O/${TAG}_bench_config3.json 2> $O/bench3.err
+python bench.py --config 2 --full --no-cpu-baseline > $O/${TAG}_bench_config2.json 2> $O/bench2.err
+python bench.py --config 4 --full --no-cpu-baseline > $O/${TAG}_bench_config4.json 2> $O/bench4.err
+python bench.py --config 3 --full --no-cpu-baseline > $O/${TAG}_bench_config3.json 2> $O/bench3.err
 tail -1 $O/${TAG}_bench.json | cut -c1-900
 ls -la $O
 # the F(3x3, 4x4) weight gradient stand-alone against the direct kernels (tools/x3_bench, built by hand: see its header) and its counters
