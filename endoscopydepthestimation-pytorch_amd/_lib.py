@@ -96,6 +96,8 @@ SIGNATURES = {
     "endo_augment_frame_bytes": (_I, []),
     "endo_augment_workspace_bytes": (_L, [_I, _I, _I]),
     "endo_augment": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "endo_evaluate_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_evaluate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "endo_point_brightness": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
     "endo_prof_enable": (_I, [_I]),
     "endo_prof_sample": (_I, [_I]),

@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "hsv_device.h"
 #include "jpeg_device.h"
 
 namespace endo {
@@ -33,33 +34,6 @@ __device__ __forceinline__ int aug_replicate(int i, int n) { return i < 0 ? 0 : 
 // ---------------------------------------------------------------------------------------------
 // colour
 // ---------------------------------------------------------------------------------------------
-// cv2.COLOR_HSV2RGB on 8 bits (color_hsv: HSV2RGB_b -> HSV2RGB_native, hscale = 6 / 180): every operation a separate float rounding
-__device__ void hsv180_to_rgb(int hh, int ss, int vv, int (&rgb)[3]) {
-#pragma clang fp contract(off)
-    const float s = static_cast<float>(ss) * (1.0f / 255.0f);
-    const float v = static_cast<float>(vv) * (1.0f / 255.0f);
-    float r, g, b;
-    if (s == 0.0f) {
-        r = g = b = v;
-    } else {
-        float h = static_cast<float>(hh) * (6.0f / 180.0f);
-        h = fmodf(h, 6.0f);
-        int sector = static_cast<int>(floorf(h));
-        h -= static_cast<float>(sector);
-        if (static_cast<unsigned>(sector) >= 6u) { sector = 0; h = 0.0f; }
-        const float t1 = v * (1.0f - s), t2 = v * (1.0f - s * h), t3 = v * (1.0f - s * (1.0f - h));
-        // sector_data {b, g, r} = {1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0} over tab = {v, t1, t2, t3}, one nibble per sector
-        const int shift = 4 * (5 - sector);
-        const int bi = (0x113002 >> shift) & 15, gi = (0x300211 >> shift) & 15, ri = (0x021130 >> shift) & 15;
-        b = bi == 0 ? v : (bi == 1 ? t1 : (bi == 2 ? t2 : t3));
-        g = gi == 0 ? v : (gi == 1 ? t1 : (gi == 2 ? t2 : t3));
-        r = ri == 0 ? v : (ri == 1 ? t1 : (ri == 2 ? t2 : t3));
-    }
-    rgb[0] = clamp255(static_cast<int>(rintf(r * 255.0f)));
-    rgb[1] = clamp255(static_cast<int>(rintf(g * 255.0f)));
-    rgb[2] = clamp255(static_cast<int>(rintf(b * 255.0f)));
-}
-
 constexpr int kColourPixels = 1024;          // per block: 256 threads x 4
 
 __global__ void __launch_bounds__(256) aug_colour_kernel(const uint8_t* __restrict__ src, const endo_augment_frame* __restrict__ prm,
@@ -98,7 +72,7 @@ __global__ void __launch_bounds__(256) aug_colour_kernel(const uint8_t* __restri
             h += h < 0 ? 180 : 0;
             h = h > 255 ? 255 : h;
             int rgb[3];
-            hsv180_to_rgb(lut[1][h], lut[2][sat], lut[3][v], rgb);
+            hsv_to_rgb<180>(lut[1][h], lut[2][sat], lut[3][v], rgb);          // cv2.COLOR_HSV2RGB
             r = rgb[0]; g = rgb[1]; b = rgb[2];
         }
         d[3 * i] = static_cast<uint8_t>(r);

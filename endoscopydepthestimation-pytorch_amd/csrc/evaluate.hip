@@ -1,0 +1,251 @@
+// Test-phase outputs -- reference evaluate.py:317-345 (per frame: colour display, depth display through COLORMAP_JET, the colour|depth
+// panel of cv2.hconcat and the coloured point cloud of utils.point_cloud_from_depth, utils.py:825-852) for a whole batch on the device.
+// tests/evaluate_restate.py is the numpy statement every output is checked against, bit for bit.
+//
+// Three launches whatever the batch size:
+//   rows   one block per (frame, row): masked depth d = b * pred, the row's maximum of d and its count of kept pixels
+//   scan   one block: exclusive prefix of the N * H row counts (frame-major, so each frame's points follow the previous frame's) and
+//          each frame's maximum of d from its row maxima
+//   write  one block per (frame, row): each pixel's colour display formed once, written to the panel and, when kept, to the point
+//          cloud at the row's offset, ordered inside the row by a wave-ballot prefix (as endo_point_cloud)
+// numpy's float32 arithmetic rounds every operation on its own: contraction is off and the roundings are explicit.
+#include <cmath>
+
+#include "common.h"
+#include "hsv_device.h"
+
+namespace endo {
+
+struct EvalParams {
+    const float* colors;          // [N][3][H][W] boundaries * colours_1 (normalised, masked)
+    const float* boundaries;      // [N][H][W]
+    const float* pred;            // [N][H][W]
+    const float* k;               // [N][3][3]
+    int frames, height, width, is_hsv, downsampling;
+    float* depth;                 // [N][H][W]
+    uint8_t* panels;              // [N][H][2W][3] B G R
+    float* points;                // [N * H * W][6]
+    int64_t* frame_offsets;       // [N + 1]
+    int64_t* row_offsets;         // [N * H] workspace: counts after `rows`, exclusive offsets after `scan`
+    float* row_max;               // [N * H] workspace
+    float* frame_max;             // [N] workspace
+};
+
+__device__ __forceinline__ bool eval_keep(const EvalParams& q, int h, int w, float bnd) {
+    return h % q.downsampling == 0 && w % q.downsampling == 0 && bnd > 0.5f;          // utils.py:836 (no thresholds: evaluate.py:340)
+}
+
+__global__ void __launch_bounds__(256) eval_rows_kernel(const EvalParams q) {
+    __shared__ int s_cnt[4];
+    __shared__ float s_max[4];
+    const int h = blockIdx.x, f = blockIdx.y;
+    const int64_t row = static_cast<int64_t>(f) * q.height + h;
+    const int64_t base = row * q.width;
+    int cnt = 0;
+    float mx = -INFINITY;
+    for (int w = threadIdx.x; w < q.width; w += 256) {
+        const float bnd = q.boundaries[base + w];
+        const float d = __fmul_rn(bnd, q.pred[base + w]);          // (boundaries * predicted_depth_maps_1), evaluate.py:338
+        q.depth[base + w] = d;
+        mx = fmaxf(mx, d);
+        cnt += eval_keep(q, h, w, bnd) ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_down(cnt, off, 64);
+        mx = fmaxf(mx, __shfl_down(mx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_max[threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        q.row_offsets[row] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        q.row_max[row] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    }
+}
+
+constexpr int kScanThreads = 1024;
+
+// one block: thread t owns the rows [t * chunk, (t + 1) * chunk); the block scans the per-thread sums, then each thread rewrites its rows
+__global__ void __launch_bounds__(kScanThreads) eval_scan_kernel(const EvalParams q) {
+    __shared__ int64_t s_wave[kScanThreads / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t rows = static_cast<int64_t>(q.frames) * q.height;
+    const int64_t chunk = (rows + kScanThreads - 1) / kScanThreads;
+    const int64_t r0 = min(rows, t * chunk), r1 = min(rows, r0 + chunk);
+    int64_t sum = 0;
+    for (int64_t r = r0; r < r1; ++r) sum += q.row_offsets[r];
+    int64_t incl = sum;          // inclusive prefix inside the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int64_t acc = incl - sum;
+    for (int i = 0; i < wave; ++i) acc += s_wave[i];
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t c = q.row_offsets[r];
+        q.row_offsets[r] = acc;
+        acc += c;
+    }
+    if (t == kScanThreads - 1) {
+        int64_t total = 0;
+        for (int i = 0; i < kScanThreads / 64; ++i) total += s_wave[i];
+        q.frame_offsets[q.frames] = total;
+    }
+    __syncthreads();          // every row offset is written before the frame offsets read them
+    for (int f = t; f < q.frames; f += kScanThreads) q.frame_offsets[f] = q.row_offsets[static_cast<int64_t>(f) * q.height];
+    // np.max(depth_map) of each frame: one wave per frame over its row maxima
+    for (int f = wave; f < q.frames; f += kScanThreads / 64) {
+        float mx = -INFINITY;
+        for (int h = lane; h < q.height; h += 64) mx = fmaxf(mx, q.row_max[static_cast<int64_t>(f) * q.height + h]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off, 64));
+        if (lane == 0) q.frame_max[f] = mx;
+    }
+}
+
+// np.uint8(255 * (0.5 * c + 0.5)), evaluate.py:329-330: three roundings, then truncation (c in [-1, 1] keeps it in [0, 255])
+__device__ __forceinline__ int display_u8(float c) {
+    const float v = __fmul_rn(255.0f, __fadd_rn(__fmul_rn(0.5f, c), 0.5f));
+    return v > 0.0f ? min(static_cast<int>(v), 255) : 0;
+}
+
+// np.uint8(b * x) of a float32 b in [0, 1] and a uint8 x (evaluate.py:336-337)
+__device__ __forceinline__ int masked_u8(float b, int x) {
+    const float v = __fmul_rn(b, static_cast<float>(x));
+    return v > 0.0f ? min(static_cast<int>(v), 255) : 0;
+}
+
+__global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
+    __shared__ uint8_t s_jet[256][3];          // B G R
+    __shared__ int s_wave[4];
+    __shared__ int64_t s_base;
+    const int h = blockIdx.x, f = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    {   // COLORMAP_JET restated: x = i / 255, channel = clip(min(4x + a, c - 4x), 0, 1), x 255 rounded half to even (fp64, as the
+        // numpy restatement; cv2's float32 interpolation of its own table may differ on ties -- DESIGN.md 4.8)
+#pragma clang fp contract(off)
+        const int i = threadIdx.x;
+        const double x = static_cast<double>(i) / 255.0;
+        const double r = fmin(fmax(fmin(4.0 * x - 1.5, 4.5 - 4.0 * x), 0.0), 1.0);
+        const double g = fmin(fmax(fmin(4.0 * x - 0.5, 3.5 - 4.0 * x), 0.0), 1.0);
+        const double b = fmin(fmax(fmin(4.0 * x + 0.5, 2.5 - 4.0 * x), 0.0), 1.0);
+        s_jet[i][0] = static_cast<uint8_t>(rint(255.0 * b));
+        s_jet[i][1] = static_cast<uint8_t>(rint(255.0 * g));
+        s_jet[i][2] = static_cast<uint8_t>(rint(255.0 * r));
+    }
+    if (threadIdx.x == 0) s_base = q.row_offsets[static_cast<int64_t>(f) * q.height + h];
+    __syncthreads();
+    const float mx = q.frame_max[f];
+    const float* kf = q.k + static_cast<int64_t>(f) * 9;
+    const float fx = kf[0], cx = kf[2], fy = kf[4], cy = kf[5];
+    const int64_t plane = static_cast<int64_t>(q.height) * q.width;
+    const int64_t pix0 = (static_cast<int64_t>(f) * q.height + h) * q.width;
+    const float* col = q.colors + static_cast<int64_t>(f) * 3 * plane + static_cast<int64_t>(h) * q.width;
+    uint8_t* panel = q.panels + pix0 * 6;          // this row of the (H, 2W, 3) panel
+    for (int w0 = 0; w0 < q.width; w0 += 256) {
+        const int w = w0 + threadIdx.x;
+        bool keep = false;
+        float bnd = 0.0f, d = 0.0f;
+        int bgr[3] = {0, 0, 0};
+        if (w < q.width) {
+            bnd = q.boundaries[pix0 + w];
+            d = q.depth[pix0 + w];
+            keep = eval_keep(q, h, w, bnd);
+            const int c0 = display_u8(col[w]), c1 = display_u8(col[plane + w]), c2 = display_u8(col[2 * plane + w]);
+            if (q.is_hsv) {          // cv2.COLOR_HSV2BGR_FULL of (H, S, V) = (c0, c1, c2)
+                int rgb[3];
+                hsv_to_rgb<256>(c0, c1, c2, rgb);
+                bgr[0] = rgb[2]; bgr[1] = rgb[1]; bgr[2] = rgb[0];
+            } else {                 // cv2.COLOR_RGB2BGR
+                bgr[0] = c2; bgr[1] = c1; bgr[2] = c0;
+            }
+            bgr[0] = masked_u8(bnd, bgr[0]); bgr[1] = masked_u8(bnd, bgr[1]); bgr[2] = masked_u8(bnd, bgr[2]);
+            // np.uint8(255 * d / np.max(d)) (evaluate.py:339): 255 * d rounded, divided by the maximum, truncated.  A frame whose maximum
+            // is 0 (0 / 0 in the reference) takes index 0 everywhere.
+            int idx = 0;
+            if (mx > 0.0f) {
+                const float v = __fdiv_rn(__fmul_rn(255.0f, d), mx);
+                idx = v > 0.0f ? min(static_cast<int>(v), 255) : 0;
+            }
+            uint8_t* left = panel + static_cast<int64_t>(w) * 3;
+            uint8_t* right = panel + (static_cast<int64_t>(q.width) + w) * 3;
+            left[0] = static_cast<uint8_t>(bgr[0]); left[1] = static_cast<uint8_t>(bgr[1]); left[2] = static_cast<uint8_t>(bgr[2]);
+            right[0] = s_jet[idx][0]; right[1] = s_jet[idx][1]; right[2] = s_jet[idx][2];
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int wave_off = 0;
+        for (int i = 0; i < wave; ++i) wave_off += s_wave[i];
+        const int chunk_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        if (keep) {
+            // utils.py:838-840 with the reference's operation order, (w - cx) / fx * z: three roundings
+            const float x = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(w), cx), fx), d);
+            const float y = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(h), cy), fy), d);
+            float* dst = q.points + (s_base + wave_off + before) * 6;
+            dst[0] = x; dst[1] = y; dst[2] = d;
+            dst[3] = static_cast<float>(bgr[2]);
+            dst[4] = static_cast<float>(bgr[1]);
+            dst[5] = static_cast<float>(bgr[0]);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_base += chunk_total;
+        __syncthreads();
+    }
+}
+
+static int64_t eval_align(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
+
+struct EvalLayout {
+    int64_t row_offsets, row_max, frame_max, total;
+};
+
+static EvalLayout eval_layout(int frames, int height) {
+    const int64_t rows = static_cast<int64_t>(frames) * height;
+    EvalLayout l;
+    l.row_offsets = 0;
+    l.row_max = eval_align(rows * static_cast<int64_t>(sizeof(int64_t)));
+    l.frame_max = l.row_max + eval_align(rows * static_cast<int64_t>(sizeof(float)));
+    l.total = l.frame_max + eval_align(static_cast<int64_t>(frames) * sizeof(float));
+    return l;
+}
+
+static bool eval_sizes_ok(int frames, int height, int width) {
+    return frames > 0 && frames <= 65535 && height > 0 && width > 0 && static_cast<int64_t>(frames) * height * width <= INT32_MAX;
+}
+
+}  // namespace endo
+
+using namespace endo;
+
+extern "C" int64_t endo_evaluate_workspace_bytes(int frames, int height, int width) {
+    if (!eval_sizes_ok(frames, height, width)) return -1;
+    return eval_layout(frames, height).total;
+}
+
+extern "C" int endo_evaluate(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics, int frames,
+                             int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
+                             int64_t* frame_offsets, void* workspace, int64_t workspace_bytes, void* stream_) {
+    if (!colors || !boundaries || !predictions || !intrinsics || !depth || !panels || !points || !frame_offsets || !workspace) return ENDO_E_BADARG;
+    if (!eval_sizes_ok(frames, height, width) || (is_hsv != 0 && is_hsv != 1) || point_cloud_downsampling <= 0) return ENDO_E_BADARG;
+    const EvalLayout l = eval_layout(frames, height);
+    if (workspace_bytes < l.total) return ENDO_E_BADARG;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    char* ws = static_cast<char*>(workspace);
+    const EvalParams q{colors, boundaries, predictions, intrinsics, frames, height, width, is_hsv, point_cloud_downsampling, depth, panels,
+                       points, frame_offsets, reinterpret_cast<int64_t*>(ws + l.row_offsets), reinterpret_cast<float*>(ws + l.row_max),
+                       reinterpret_cast<float*>(ws + l.frame_max)};
+    const double pixels = static_cast<double>(frames) * height * width;
+    ProfScope prof(kProfSmall, stream, 0.0, pixels * (4.0 * 5 + 4.0 + 6.0 + 24.0));
+    eval_rows_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    ENDO_LAUNCH_CHECK();
+    eval_scan_kernel<<<1, kScanThreads, 0, stream>>>(q);
+    ENDO_LAUNCH_CHECK();
+    eval_write_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    ENDO_LAUNCH_CHECK();
+    return 0;
+}

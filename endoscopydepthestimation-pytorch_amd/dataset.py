@@ -1,6 +1,7 @@
-"""Training batches straight from sequence folders, assembled on the GPU -- the counterpart of the reference's
-``dataset.SfMDataset`` (train / validation phases, dataset.py:133-333 set-up, 335-460 ``__getitem__``) plus the ``DataLoader``
-that batches its samples (train.py:168-178, 254-270), without OpenCV / plyfile / albumentations and without a host image.
+"""Training and test batches straight from sequence folders, assembled on the GPU -- the counterpart of the reference's
+``dataset.SfMDataset`` (train / validation phases, dataset.py:133-333 set-up, 335-460 ``__getitem__``; test phase, 464-486) plus the
+``DataLoader`` that batches its samples (train.py:168-178, 254-270; evaluate.py:279-292), without OpenCV / plyfile / albumentations
+and without a host image.  TestFrames is the test phase; the rest of this note is about TrainingBatches.
 
     per folder (once)   reader.load_sequence  (or the reference's own precompute file, ``use_store_data``: dataset.py:320-331)
                         -> scatter.SequenceScatter: point cloud, mask, visibility, per-view matrices resident in HBM
@@ -50,7 +51,81 @@ def _by_folder_name(table, folder):
     raise KeyError("no precomputed entry for sequence %s" % folder)
 
 
-class TrainingBatches(object):
+class _DeviceBatches(object):
+    """What the two frame sources share: a reader thread's frame decode and the prefetching iterator over ``_batches()``.  The
+    subclass sets device, downsampling, rgb_mode, is_hsv, prefetch, _local and _side."""
+
+    def _decode_into(self, path, window, dst, stream):
+        """One frame into dst (3, H, W) on `stream`; runs on a reader thread with its own FrameDecoder."""
+        decoder = getattr(self._local, "decoder", None)
+        if decoder is None:
+            decoder = self._local.decoder = reader.FrameDecoder(device=self.device, slots=4)
+        with open(path, "rb") as f:
+            data = f.read()
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            if dst.dtype == torch.uint8:          # (H, W, 3) for the augmentations
+                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, self.rgb_mode, out_u8=dst)
+            elif self.is_hsv:
+                scratch = torch.empty((dst.shape[1], dst.shape[2], 3), dtype=torch.uint8, device=self.device)
+                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, "bgr", out_u8=scratch)
+                reader.hsv_full(scratch, blue_index=0, out_f32=dst)
+                scratch.record_stream(stream)
+            else:
+                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, self.rgb_mode, out_f32=dst)
+
+    def __iter__(self):
+        if not self.prefetch:
+            yield from self._batches()
+            return
+        # producer thread: assembles on the side stream, hands over (batch, event); the consumer's stream waits for the event and
+        # the tensors are marked as used by it, so the caching allocator does not hand their memory back to the side stream early
+        handover = queue.Queue(maxsize=self.prefetch)
+        stop = threading.Event()
+
+        def hand_over(item):
+            """False when the consumer has left (the queue may be full and will never drain)."""
+            while not stop.is_set():
+                try:
+                    handover.put(item, timeout=0.1)
+                    return True
+                except queue.Full:
+                    continue
+            return False
+
+        def produce():
+            try:
+                with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+                    for batch in self._batches():
+                        ready = torch.cuda.Event()
+                        ready.record(self._side)
+                        if not hand_over((batch, ready)):
+                            return
+                hand_over(None)
+            except BaseException as exc:          # noqa: BLE001 -- re-raised in the consumer
+                hand_over(exc)
+
+        worker = threading.Thread(target=produce, daemon=True)
+        worker.start()
+        try:
+            while True:
+                item = handover.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                batch, ready = item
+                current = torch.cuda.current_stream(self.device)
+                current.wait_event(ready)
+                for value in batch.values():
+                    if torch.is_tensor(value):
+                        value.record_stream(current)
+                yield batch
+        finally:
+            stop.set()
+            worker.join(timeout=5.0)
+
+
+class TrainingBatches(_DeviceBatches):
     """Iterable over training batches (dictionaries keyed as ``synthetic.BATCH_KEYS``, everything on the device).
 
     folder_list           sequence folders (``<root>/bag_x/_start_...``), as utils.get_parent_folder_names returns them
@@ -129,24 +204,6 @@ class TrainingBatches(object):
         if torch.cuda.is_available():
             torch.cuda.current_stream(self.device).synchronize()
 
-    def _decode_into(self, path, window, dst, stream):
-        """One frame into dst (3, H, W) on `stream`; runs on a reader thread with its own FrameDecoder."""
-        decoder = getattr(self._local, "decoder", None)
-        if decoder is None:
-            decoder = self._local.decoder = reader.FrameDecoder(device=self.device, slots=4)
-        with open(path, "rb") as f:
-            data = f.read()
-        with torch.cuda.device(self.device), torch.cuda.stream(stream):
-            if dst.dtype == torch.uint8:          # (H, W, 3) for the augmentations
-                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, self.rgb_mode, out_u8=dst)
-            elif self.is_hsv:
-                scratch = torch.empty((dst.shape[1], dst.shape[2], 3), dtype=torch.uint8, device=self.device)
-                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, "bgr", out_u8=scratch)
-                reader.hsv_full(scratch, blue_index=0, out_f32=dst)
-                scratch.record_stream(stream)
-            else:
-                decoder.decode(data, window[0], window[1], window[2], window[3], self.downsampling, self.rgb_mode, out_f32=dst)
-
     def __len__(self):
         return (self.num_iter + self.batch_size - 1) // self.batch_size
 
@@ -206,56 +263,6 @@ class TrainingBatches(object):
         valid = (batch["sparse_depth_masks_1"].sum(dim=(1, 2, 3)) != 0) & (batch["sparse_depth_masks_2"].sum(dim=(1, 2, 3)) != 0)
         return batch, valid.tolist()
 
-    def __iter__(self):
-        if not self.prefetch:
-            yield from self._batches()
-            return
-        # producer thread: assembles on the side stream, hands over (batch, event); the consumer's stream waits for the event and
-        # the tensors are marked as used by it, so the caching allocator does not hand their memory back to the side stream early
-        handover = queue.Queue(maxsize=self.prefetch)
-        stop = threading.Event()
-
-        def hand_over(item):
-            """False when the consumer has left (the queue may be full and will never drain)."""
-            while not stop.is_set():
-                try:
-                    handover.put(item, timeout=0.1)
-                    return True
-                except queue.Full:
-                    continue
-            return False
-
-        def produce():
-            try:
-                with torch.cuda.device(self.device), torch.cuda.stream(self._side):
-                    for batch in self._batches():
-                        ready = torch.cuda.Event()
-                        ready.record(self._side)
-                        if not hand_over((batch, ready)):
-                            return
-                hand_over(None)
-            except BaseException as exc:          # noqa: BLE001 -- re-raised in the consumer
-                hand_over(exc)
-
-        worker = threading.Thread(target=produce, daemon=True)
-        worker.start()
-        try:
-            while True:
-                item = handover.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                batch, ready = item
-                current = torch.cuda.current_stream(self.device)
-                current.wait_event(ready)
-                for value in batch.values():
-                    value.record_stream(current)
-                yield batch
-        finally:
-            stop.set()
-            worker.join(timeout=5.0)
-
     def _batches(self):
         indices = list(range(self.num_iter))
         if self.shuffle:
@@ -271,3 +278,83 @@ class TrainingBatches(object):
                 samples = [s if ok else self._draw(self.rng.randint(0, len(self.image_file_names) - 1)) for s, ok in zip(samples, valid)]
                 batch, valid = self._assemble(samples)
             yield batch
+
+
+class TestFrames(_DeviceBatches):
+    """Iterable over test-phase batches -- the reference's ``SfMDataset(phase="test")`` (dataset.py:464-486) behind evaluate.py's
+    ``DataLoader`` (evaluate.py:279-292), with any batch size.  Each batch is a dictionary on the device:
+
+        colors      (N, 3, H, W) fp32   reference get_test_color_img + Normalize(0.5, 0.5) + img_to_tensor (is_hsv: HSV_FULL values)
+        boundaries  (N, 1, H, W) fp32   the folder's mask_boundary / 255, > 0.9 -> 1 else 0
+        intrinsics  (N, 3, 3) fp32      the folder's intrinsic_matrix[:3, :3]
+        names       list of N strings   the file's name[-12:-4]
+
+    image_file_names      the frames, in the order they are yielded (evaluate.py sorts them; utils.get_filenames_from_frame_indexes)
+    precompute_path       the reference's precompute pickle: crop window, intrinsics and mask of every folder as the reference stored
+                          them.  Without it each folder is read with reader.load_sequence(..., inlier_percentage=None).
+    A batch never spans two folders (frames of one folder share the crop window), so the last batch of each folder may be short.
+    reader_threads / prefetch / device as for TrainingBatches.
+    """
+
+    def __init__(self, image_file_names, batch_size=1, downsampling=4.0, network_downsampling=64, visible_interval=30, precompute_path=None,
+                 suggested_h=None, suggested_w=None, is_hsv=False, rgb_mode="rgb", reader_threads=4, prefetch=1, device="cuda"):
+        self.image_file_names = [str(n) for n in image_file_names]
+        if not self.image_file_names:
+            raise ValueError("no frames to read")
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        self.downsampling = float(downsampling)
+        self.is_hsv = bool(is_hsv)
+        self.rgb_mode = rgb_mode
+        self.device = torch.device(device)
+        stored = read_precompute_file(precompute_path) if precompute_path is not None else None
+        self.sequences = {}
+        for folder in dict.fromkeys(os.path.dirname(n) for n in self.image_file_names):
+            if stored is not None:
+                window, intrinsics, mask = (_by_folder_name(stored[k], folder) for k in ("crop_positions", "intrinsic_matrix", "mask_boundary"))
+            else:
+                seq = reader.load_sequence(folder, self.downsampling, network_downsampling, visible_interval, suggested_h, suggested_w, None)
+                window, intrinsics, mask = seq["crop_positions"], seq["intrinsic_matrix"], seq["mask_boundary"]
+            boundary = np.asarray(mask).astype(np.float32) / 255.0          # dataset.py:480-483
+            boundary = np.where(boundary > 0.9, np.float32(1.0), np.float32(0.0)).astype(np.float32)
+            k = np.asarray(intrinsics)[:3, :3].astype(np.float32).reshape(3, 3)
+            self.sequences[folder] = {"crop_positions": [int(v) for v in window],
+                                      "boundary": torch.from_numpy(boundary).reshape(1, 1, *boundary.shape).to(self.device),
+                                      "intrinsics": torch.from_numpy(k).reshape(1, 3, 3).to(self.device)}
+        self.batches = []          # (folder, [file names]) in file order
+        for name in self.image_file_names:
+            folder = os.path.dirname(name)
+            if not self.batches or self.batches[-1][0] != folder or len(self.batches[-1][1]) == self.batch_size:
+                self.batches.append((folder, []))
+            self.batches[-1][1].append(name)
+        self.reader_threads = max(1, int(reader_threads))
+        self.prefetch = max(0, int(prefetch))
+        self._pool = ThreadPoolExecutor(self.reader_threads) if self.reader_threads > 1 else None
+        self._local = threading.local()
+        self._side = torch.cuda.Stream(device=self.device) if self.prefetch else None
+        if torch.cuda.is_available():          # the resident boundary / intrinsics copies are read from the side stream
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def __len__(self):
+        return len(self.batches)
+
+    def _assemble(self, folder, names):
+        seq = self.sequences[folder]
+        sh, eh, sw, ew = seq["crop_positions"]
+        n = len(names)
+        stream = torch.cuda.current_stream(self.device)
+        colors = torch.empty((n, 3, eh - sh, ew - sw), dtype=torch.float32, device=self.device)
+        jobs = [(name, (sh, eh, sw, ew), colors[k], stream) for k, name in enumerate(names)]
+        if self._pool is None:
+            for job in jobs:
+                self._decode_into(*job)
+        else:
+            for done in [self._pool.submit(self._decode_into, *job) for job in jobs]:
+                done.result()
+        return {"colors": colors, "boundaries": seq["boundary"].expand(n, -1, -1, -1).contiguous(),
+                "intrinsics": seq["intrinsics"].expand(n, -1, -1).contiguous(), "names": [os.path.basename(name)[-12:-4] for name in names]}
+
+    def _batches(self):
+        for folder, names in self.batches:
+            yield self._assemble(folder, names)

@@ -1,4 +1,4 @@
-"""Host-side helpers of the training path with the reference's names (reference utils.py:615-682)."""
+"""Host-side helpers with the reference's names (reference utils.py:615-682 for the training path, 825-865 and 1405-1412 for the test phase)."""
 
 import torch
 
@@ -121,3 +121,67 @@ def point_cloud_from_depth(depth_map, color_img, mask_img, intrinsic_matrix, poi
     _lib.check(rc, "endo_point_cloud")
     n = int(count.item())
     return points[:n].cpu().numpy().reshape(-1, 6)
+
+
+def get_filenames_from_frame_indexes(sequence_root, frame_index_array):
+    """reference utils.py:1405-1412 (evaluate.py --load_all_frames, with reader.read_visible_view_indexes): the ``%08d.jpg`` file of
+    every frame index found anywhere below ``sequence_root``, missing frames skipped, the list sorted.  A frame found in several
+    subfolders gives the first of them in sorted order (the reference takes the first ``rglob`` yields, which is file-system order)."""
+    import pathlib
+    root = pathlib.Path(sequence_root)
+    names = []
+    for index in frame_index_array:
+        found = sorted(root.rglob("{:08d}.jpg".format(int(index))))
+        if found:
+            names.append(found[0])
+    names.sort()
+    return names
+
+
+_PLY_PROPERTIES = ("property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+                   "property uchar blue")
+
+
+def write_point_cloud(path, point_cloud, text=True):
+    """reference utils.py:855-865 without plyfile: one ``vertex`` element of float x, y, z and uchar red, green, blue per row of the
+    (P, 6) float32 array -- what ``PlyData([el], text=True).write(path)`` stores.  text=True: ASCII PLY 1.0, one vertex per line, the
+    floats with 9 significant digits (every float32 reads back exactly); text=False: binary_little_endian 1.0."""
+    import numpy as np
+    points = np.asarray(point_cloud, dtype=np.float32).reshape(-1, 6)
+    n = points.shape[0]
+    header = "\n".join(("ply", "format ascii 1.0" if text else "format binary_little_endian 1.0", "element vertex %d" % n)
+                       + _PLY_PROPERTIES + ("end_header",)) + "\n"
+    with open(str(path), "wb") as f:
+        f.write(header.encode("ascii"))
+        if text:
+            if n:
+                # the colours print as integers: plyfile casts them to uchar first (utils.py:862), these are whole numbers in [0, 255]
+                f.write((("%.9g %.9g %.9g %d %d %d\n" * n) % tuple(points.astype(np.float64).ravel().tolist())).encode("ascii"))
+        else:
+            rec = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+            for k, name in enumerate(("x", "y", "z", "red", "green", "blue")):
+                rec[name] = points[:, k]
+            f.write(rec.tobytes())
+
+
+def write_png(path, bgr, compress_level=1):
+    """cv2.imwrite(path, bgr) for an (H, W, 3) uint8 image in cv2's B, G, R order, with zlib and struct only: an 8-bit RGB PNG
+    (colour type 2, no interlace, filter type 0 on every row).  The pixels are the contract, not libpng's bytes."""
+    import struct
+    import zlib
+    import numpy as np
+    img = np.asarray(bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("write_png expects an (H, W, 3) uint8 array")
+    height, width = img.shape[:2]
+    raw = np.zeros((height, 1 + 3 * width), dtype=np.uint8)          # a filter-type byte (0) in front of each row
+    raw[:, 1:] = img[:, :, ::-1].reshape(height, 3 * width)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(str(path), "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), compress_level)))
+        f.write(chunk(b"IEND", b""))

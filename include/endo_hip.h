@@ -43,7 +43,7 @@ extern "C" {
  * endo_sgd_clip_step takes a `skip_flag` device pointer; endo_net16_offset what = 7; adds endo_hsv_full.
  * 6: round 6 -- adds endo_warp_consistency_bytes, the option ENDO_OPT_TD_PERSIST and the value ENDO_OPT_WINO_DGRAD = 3; since then
  * (unchanged by additions) endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the endo_augment_frame
- * record -- entry points only, no existing signature changes. */
+ * record; then endo_evaluate and endo_evaluate_workspace_bytes -- entry points only, no existing signature changes. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -442,6 +442,28 @@ int64_t endo_augment_workspace_bytes(int frames, int height, int width);
  * [1, 255], a negative or non-finite sigma). */
 int endo_augment(const uint8_t* src, const endo_augment_frame* params, int frames, int height, int width, uint8_t* out_u8,
                  float* out_f32, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Test-phase outputs of a batch -- reference evaluate.py:329-345 (colour display, depth display, cv2.hconcat panel, point cloud)
+ * with utils.py:825-865 (point_cloud_from_depth, write_point_cloud), for N frames at once; numpy's float32 roundings, bit for bit.
+ * colors [N][3][H][W] fp32: boundaries * colours_1 (the masked, Normalize(0.5, 0.5) network input); boundaries [N][1][H][W] fp32 in
+ * {0, 1}; predictions [N][1][H][W] fp32 (the network's output, >= 0); intrinsics [N][3][3] fp32.  Writes
+ *   depth          [N][1][H][W] fp32   d = boundaries * predictions
+ *   panels         [N][H][2W][3] uint8 B, G, R: columns [0, W) the colour display u8(b * C(u8(255 * (0.5 c + 0.5)))), C = RGB -> BGR
+ *                                      or, is_hsv = 1, cv2.COLOR_HSV2BGR_FULL (OpenCV's 8-bit float path; PARITY UNPINNED against cv2);
+ *                                      columns [W, 2W) COLORMAP_JET[u8(fl(255 d) / max(d))] (a frame whose max(d) is 0: entry 0
+ *                                      everywhere; JET restated from its piecewise-linear curves, PARITY UNPINNED against cv2)
+ *   points         capacity N * H * W rows of (x, y, z, r, g, b) fp32: every pixel with h % downsampling == 0, w % downsampling == 0
+ *                                      and boundary > 0.5, frame-major, row-major inside a frame: endo_point_cloud's rows of (d, the
+ *                                      colour display, b, K) bit for bit
+ *   frame_offsets  [N + 1] int64       frame f's rows are [frame_offsets[f], frame_offsets[f + 1])
+ * Three launches whatever N.  N <= 65535, N * H * W < 2^31.  ENDO_E_BADARG for null pointers, bad sizes, is_hsv not 0 / 1,
+ * downsampling < 1 or a short workspace. */
+/* device workspace bytes of endo_evaluate (-1 for bad sizes) */
+int64_t endo_evaluate_workspace_bytes(int frames, int height, int width);
+int endo_evaluate(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics, int frames,
+                  int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
+                  int64_t* frame_offsets, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* live per-kernel-family timing for bench.py's roofline line: HIP events recorded on the launch
  * stream around every entry of the selected families.  family_mask: bit f enables family f
