@@ -98,6 +98,11 @@ SIGNATURES = {
     "endo_augment": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
     "endo_evaluate_workspace_bytes": (_L, [_I, _I, _I]),
     "endo_evaluate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "endo_loss_head_planes": (_I, [_I, _I, _I, ctypes.POINTER(_L)]),
+    "endo_display_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_display_panel_shape": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "endo_display": (_I, [_P] * 9 + [_I, _I, _I, _P, _P, _L, _P]),
+    "endo_validation_accumulate": (_I, [_P, _I, _P, _P, _P]),
     "endo_point_brightness": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
     "endo_prof_enable": (_I, [_I]),
     "endo_prof_sample": (_I, [_I]),

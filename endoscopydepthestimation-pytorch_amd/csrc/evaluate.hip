@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "hsv_device.h"
+#include "jet_device.h"
 
 namespace endo {
 
@@ -124,18 +125,7 @@ __global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
     __shared__ int64_t s_base;
     const int h = blockIdx.x, f = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    {   // COLORMAP_JET restated: x = i / 255, channel = clip(min(4x + a, c - 4x), 0, 1), x 255 rounded half to even (fp64, as the
-        // numpy restatement; cv2's float32 interpolation of its own table may differ on ties -- DESIGN.md 4.8)
-#pragma clang fp contract(off)
-        const int i = threadIdx.x;
-        const double x = static_cast<double>(i) / 255.0;
-        const double r = fmin(fmax(fmin(4.0 * x - 1.5, 4.5 - 4.0 * x), 0.0), 1.0);
-        const double g = fmin(fmax(fmin(4.0 * x - 0.5, 3.5 - 4.0 * x), 0.0), 1.0);
-        const double b = fmin(fmax(fmin(4.0 * x + 0.5, 2.5 - 4.0 * x), 0.0), 1.0);
-        s_jet[i][0] = static_cast<uint8_t>(rint(255.0 * b));
-        s_jet[i][1] = static_cast<uint8_t>(rint(255.0 * g));
-        s_jet[i][2] = static_cast<uint8_t>(rint(255.0 * r));
-    }
+    jet_fill(s_jet, threadIdx.x);          // COLORMAP_JET (jet_device.h)
     if (threadIdx.x == 0) s_base = q.row_offsets[static_cast<int64_t>(f) * q.height + h];
     __syncthreads();
     const float mx = q.frame_max[f];

@@ -75,6 +75,41 @@ using namespace endo;
 
 // (endo_warp_consistency -- the depth-warp + consistency-loss chain as two fused kernels -- lives in geometry.hip.)
 
+// The carving of endo_loss_head's workspace (offsets in floats), the one statement of it: endo_loss_head takes its pieces from here and
+// endo_loss_head_planes reports the planes display.hip renders.  Every piece starts on a 4-float boundary, so plane-sized pieces stay
+// 16-byte aligned when p % 4 == 0 (head_add_kernel copes otherwise).
+struct HeadLayout {
+    int64_t scaled_1, scaled_2;          // depth-scaled predictions
+    int64_t flow_1, flow_2;              // flow from depth: raw, then masked in place
+    int64_t msf_1, msf_2;                // sparse flows * boundary
+    int64_t msm_1, msm_2;                // sparse flow masks * boundary
+    int64_t cons;                        // endo_consistency_phase's own carving (warped, intersect, sums)
+    int64_t g_flow_1, g_flow_2;          // d / d masked flow, then masked in place = d / d raw flow
+    int64_t g_s1, g_s2;                  // d loss / d scaled depth: the flow terms, then += the consistency terms
+    int64_t dstats;                      // fp64 reduction tables (depth scaling, sparse-flow loss, distance loss)
+    int64_t parts, up, ratio, end;
+};
+
+static HeadLayout head_layout(int n, int h, int w) {
+    const int64_t p = static_cast<int64_t>(n) * h * w;
+    int64_t at = 0;
+    auto take = [&](int64_t count) { const int64_t q = at; at += (count + 3) / 4 * 4; return q; };
+    HeadLayout l;
+    l.scaled_1 = take(p);       l.scaled_2 = take(p);
+    l.flow_1 = take(2 * p);     l.flow_2 = take(2 * p);
+    l.msf_1 = take(2 * p);      l.msf_2 = take(2 * p);
+    l.msm_1 = take(p);          l.msm_2 = take(p);
+    l.cons = take(endo_warp_consistency_workspace_floats(n, h, w));
+    l.g_flow_1 = take(2 * p);   l.g_flow_2 = take(2 * p);
+    l.g_s1 = take(p);           l.g_s2 = take(p);
+    l.dstats = take(2 * (2 * 8 * n + 2 * n + 2 * 2 * n + 2 * 4 * n));
+    l.parts = take(8);           // sfl_1, sfl_2, dcl_1, dcl_2
+    l.up = take(4);              // upstream gradients of the four terms
+    l.ratio = take(4);           // depth-scaling's second output (unused by the loss)
+    l.end = at;
+    return l;
+}
+
 extern "C" int64_t endo_loss_head_workspace_floats(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return -1;
     const int64_t p = static_cast<int64_t>(n) * h * w;
@@ -94,25 +129,23 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
     if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return ENDO_E_BADARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int hw = h * w;
-    const int64_t p = static_cast<int64_t>(n) * hw;
-    // ---- workspace carving (floats); every plane-sized piece stays 16-byte aligned when p % 4 == 0, head_add_kernel copes otherwise ----
-    float* ws = workspace;
-    auto take = [&](int64_t count) { float* q = ws; ws += (count + 3) / 4 * 4; return q; };
-    float* scaled_1 = take(p);      float* scaled_2 = take(p);
-    float* flow_1 = take(2 * p);    float* flow_2 = take(2 * p);          // raw, then masked in place
-    float* msf_1 = take(2 * p);     float* msf_2 = take(2 * p);           // sparse flows * boundary
-    float* msm_1 = take(p);         float* msm_2 = take(p);               // sparse flow masks * boundary
-    float* cons_ws = take(endo_warp_consistency_workspace_floats(n, h, w));          // endo_consistency_phase's own carving (warped, intersect, sums)
-    float* g_flow_1 = take(2 * p);  float* g_flow_2 = take(2 * p);        // d / d masked flow, then masked in place = d / d raw flow
-    float* g_s1 = take(p);          float* g_s2 = take(p);                // d loss / d scaled depth: the flow terms, then += the consistency terms
-    double* dstats = reinterpret_cast<double*>(take(2 * (2 * 8 * n + 2 * n + 2 * 2 * n + 2 * 4 * n)));
+    // ---- workspace carving (floats): head_layout ----
+    const HeadLayout l = head_layout(n, h, w);
+    float* scaled_1 = workspace + l.scaled_1;  float* scaled_2 = workspace + l.scaled_2;
+    float* flow_1 = workspace + l.flow_1;      float* flow_2 = workspace + l.flow_2;
+    float* msf_1 = workspace + l.msf_1;        float* msf_2 = workspace + l.msf_2;
+    float* msm_1 = workspace + l.msm_1;        float* msm_2 = workspace + l.msm_2;
+    float* cons_ws = workspace + l.cons;
+    float* g_flow_1 = workspace + l.g_flow_1;  float* g_flow_2 = workspace + l.g_flow_2;
+    float* g_s1 = workspace + l.g_s1;          float* g_s2 = workspace + l.g_s2;
+    double* dstats = reinterpret_cast<double*>(workspace + l.dstats);
     double* ds_stats_1 = dstats;            double* ds_stats_2 = ds_stats_1 + 8 * n;
     double* ds_work_1 = ds_stats_2 + 8 * n; double* ds_work_2 = ds_work_1 + n;
     double* l1_stats_1 = ds_work_2 + n;     double* l1_stats_2 = l1_stats_1 + 2 * n;
     double* nd_stats_1 = l1_stats_2 + 2 * n; double* nd_stats_2 = nd_stats_1 + 4 * n;
-    float* parts = take(8);          // sfl_1, sfl_2, dcl_1, dcl_2
-    float* up = take(4);             // upstream gradients of the four terms
-    float* ratio = take(4);          // depth-scaling's second output (unused by the loss)
+    float* parts = workspace + l.parts;
+    float* up = workspace + l.up;
+    float* ratio = workspace + l.ratio;
     int rc;
 #define HEAD(call) do { rc = (call); if (rc) return rc; } while (0)
     // ---- forward (train.py:279-315) ----
@@ -156,5 +189,13 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
     HEAD(endo_depth_scale_bwd_impl(g_s1, nullptr, pred_1, sparse_depths_1, ds_stats_1, grad_pred_1, ds_work_1, n, hw, eps, 0, stream));
     HEAD(endo_depth_scale_bwd_impl(g_s2, nullptr, pred_2, sparse_depths_2, ds_stats_2, grad_pred_2, ds_work_2, n, hw, eps, 0, stream));
 #undef HEAD
+    return 0;
+}
+
+extern "C" int endo_loss_head_planes(int n, int h, int w, int64_t* offsets) {
+    if (!offsets || n <= 0 || h <= 0 || w <= 0) return ENDO_E_BADARG;
+    const HeadLayout l = head_layout(n, h, w);
+    const int64_t planes[6] = {l.scaled_1, l.scaled_2, l.flow_1, l.flow_2, l.msf_1, l.msf_2};
+    for (int i = 0; i < 6; ++i) offsets[i] = planes[i];
     return 0;
 }

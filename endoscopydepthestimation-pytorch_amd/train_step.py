@@ -8,9 +8,12 @@ train.py:272-328, built from the drop-in modules of ``models`` / ``losses`` and 
   any rank's loss was NaN / Inf.
 """
 
+import collections
+import ctypes
+
 import torch
 
-from . import _lib, distributed, losses, models
+from . import _lib, display, distributed, losses, models
 
 
 class _MaskMulFn(torch.autograd.Function):
@@ -119,6 +122,7 @@ class TrainingStep(object):
         saves the autograd engine's start-up latency (~0.1 ms of idle GPU after the loss synchronisation).
         Returns (losses tensor [total, dcl, sfl], network input, forward tape, d loss / d prediction)."""
         lib = _lib.load()
+        self._display_source = None          # the previous call's masked input goes back to the allocator before this call's is taken
         b = _lib.dev_f32(batch["boundaries"], "boundaries")
         c1 = _lib.dev_f32(batch["colors_1"], "colors_1")
         c2 = _lib.dev_f32(batch["colors_2"], "colors_2")
@@ -145,6 +149,7 @@ class TrainingStep(object):
                 pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9),
                 self.sfl_weight, self.dcl_weight, self.epsilon, _lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]),
                 _lib.ptr(self._head_ws), n, h, w, _lib.stream()), "endo_loss_head")
+        self._display_source = (x, b)          # what display_panels() renders with the head workspace's planes
         return losses_t, x, tape, pred, grad_pred
 
     def _fused_backward(self, x, tape, grad_pred):
@@ -153,6 +158,45 @@ class TrainingStep(object):
                 self.model._run_backward16(tuple(x.shape), tape, grad_pred, self.model.training, 2, self.half_storage)
             else:
                 self.model._run_backward(x, tape, grad_pred, self.model.training, 2)
+
+    def validation_losses(self, batch):
+        """The validation body of reference train.py:403-444 for one batch: the two network forwards and the loss head, nothing else -- no
+        backward, no all-reduce, no optimizer: parameters, ``.grad``, momentum and the gradient bucket stay as they are.  The network runs in
+        its current mode; the reference validates in ``.train()`` mode (its model is never switched), so BatchNorm uses batch statistics and
+        updates the running ones (frame 1's, then frame 2's).  The reference's ``torch.abs`` on the predictions (train.py:418-421) is the
+        identity: the network's last operation is already ``torch.abs`` (models.py:186).  Returns the device fp32 [total, dcl, sfl, flag]
+        (flag 1.0 when the total is NaN / Inf); nothing is read back to the host.  With the fused head (the default) this is
+        ``_fused_iteration`` -- the loss head's backward half runs too, into its workspace and a scratch gradient; with fused_head=False it
+        is ``losses()`` under ``torch.no_grad()``."""
+        if self.fused_head:
+            losses_t, _, _, _, _ = self._fused_iteration(batch)
+            return losses_t
+        with torch.no_grad():
+            loss, dcl, sfl, _ = self.losses(batch)
+            bad = (~torch.isfinite(loss)).to(torch.float32).reshape(1)
+            return torch.cat([loss.reshape(1), dcl.reshape(1), sfl.reshape(1), bad]).to(torch.float32)
+
+    def display_panels(self):
+        """The display panel of this step's latest call -- training (``__call__``) or validation (``validation_losses``) -- as
+        train.py:353-371 / 460-478 build it: the device uint8 (8 Hg, Wg, 3) R, G, B image of ``display.panels``.  Rendered from the planes
+        the loss head left in its workspace (``endo_loss_head_planes``: scaled depths, masked flows, masked sparse flows) and the masked
+        network input the call kept: no recompute.  Issue it on the stream of the call it renders, before the next call of this step
+        (which overwrites the workspace).  Needs the fused loss head; on the module path use ``display.panels`` on ``losses()``' extras."""
+        if not self.fused_head:
+            raise RuntimeError("display_panels renders from the fused loss head's workspace; with fused_head=False build the panel with "
+                               "display.panels from losses()' extras")
+        source = self.__dict__.get("_display_source")
+        if source is None:
+            raise RuntimeError("display_panels: no training or validation call to render yet")
+        x, b = source
+        n2, _, h, w = x.shape
+        n = n2 // 2
+        offsets = (ctypes.c_int64 * 6)()
+        _lib.check(_lib.load().endo_loss_head_planes(n, h, w, offsets), "endo_loss_head_planes")
+        p = n * h * w
+        ws = self._head_ws
+        plane = lambda i, c: ws[offsets[i]:offsets[i] + c * p].view(n, c, h, w)
+        return display.panels(x[:n], x[n:], plane(0, 1), plane(1, 1), b, plane(4, 2), plane(5, 2), plane(2, 2), plane(3, 2))
 
     def __call__(self, batch, lr=None):
         """One iteration.  Nothing in it waits for the host: the non-finite-loss guard (train.py:317-322) is a flag the loss head writes on
@@ -191,6 +235,70 @@ class TrainingStep(object):
         slot = ring[self._readback_next]
         slot.release()          # an output issued 8 steps ago and never read takes its values now (its copy finished long ago)
         return slot
+
+
+ValidationResult = collections.namedtuple("ValidationResult", ["mean_loss", "mean_depth_consistency_loss", "mean_sparse_flow_loss",
+                                                               "running_means", "losses"])
+ValidationResult.__doc__ = """What ``validate`` returns: the three running means after the last batch as Python floats (the values train.py's
+mean_loss, mean_depth_consistency_loss and mean_sparse_flow_loss hold after its validation loop, bit for bit), ``running_means`` the
+float64 numpy (B, 3) means after each batch (what train.py:481-483 logs per batch) and ``losses`` the float32 numpy (B, 3) per-batch
+[total, dcl, sfl]."""
+
+
+def validate(step, batches, initial=None, display_each=None, on_display=None):
+    """The validation pass of reference train.py:378-485 with a TrainingStep: ``step.validation_losses`` on every batch of ``batches`` (for
+    example ``dataset.TrainingBatches(..., transform=None, shuffle=False)``, the reference's validation loader), the running means of
+    train.py:446-456 updated on the device by ``endo_validation_accumulate`` (fp64), and ``on_display(batch_index, panel)`` with the device
+    uint8 panel of ``step.display_panels()`` when ``batch_index % display_each == 0`` (the callback may keep the tensor; hand it to
+    ``display.stack_and_display`` for a TensorBoard writer).  Nothing in the pass reads the device per batch: the means, their per-batch
+    history and the per-batch losses come back in one read at the end.
+
+    initial: the three means (loss, depth consistency, sparse flow) before the pass, default NaN -- in the reference a NaN batch 0 leaves
+    the Python variables as the training loop left them, so pass the training means to reproduce that.  With world > 1 each rank's
+    result covers its own batches (the reference has one process); averaging across ranks is the caller's.  Returns a
+    ``ValidationResult``; the checkpoint name of train.py:486-488 is
+    ``'checkpoint_model_epoch_{}_validation_{}.pt'.format(epoch, result.mean_sparse_flow_loss)``."""
+    nan = float("nan")
+    initial = (nan, nan, nan) if initial is None else tuple(float(v) for v in initial)
+    if len(initial) != 3:
+        raise ValueError("initial must hold three means (loss, depth consistency, sparse flow)")
+    if display_each is not None:
+        display_each = int(display_each)
+        if display_each <= 0:
+            raise ValueError("display_each must be a positive number of batches (got %d)" % display_each)
+        if on_display is None:
+            raise ValueError("display_each needs an on_display(batch_index, panel) callback")
+        if not step.fused_head:
+            raise ValueError("validate(display_each=...) renders through TrainingStep.display_panels, which needs the fused loss head")
+    elif on_display is not None:
+        raise ValueError("on_display needs display_each")
+    lib = _lib.load()
+    means = history = None
+    per_batch = []
+    count = 0
+    for index, batch in enumerate(batches):
+        losses_t = _lib.dev_f32(step.validation_losses(batch), "validation losses")
+        if means is None:
+            means = torch.tensor(initial, dtype=torch.float64, device=losses_t.device)
+            history = torch.empty((max(1, len(batches)) if hasattr(batches, "__len__") else 64, 3), dtype=torch.float64, device=losses_t.device)
+        if index >= history.shape[0]:
+            grown = torch.empty((2 * history.shape[0], 3), dtype=torch.float64, device=history.device)
+            grown[:history.shape[0]].copy_(history)
+            history = grown
+        _lib.check(lib.endo_validation_accumulate(_lib.ptr(losses_t), index, _lib.ptr(means), _lib.ptr(history), _lib.stream()),
+                   "endo_validation_accumulate")
+        per_batch.append(losses_t[:3])
+        if display_each is not None and index % display_each == 0:
+            on_display(index, step.display_panels())
+        count = index + 1
+    if means is None:
+        return ValidationResult(initial[0], initial[1], initial[2], torch.empty((0, 3), dtype=torch.float64).numpy(),
+                                torch.empty((0, 3), dtype=torch.float32).numpy())
+    host = torch.cat([means, history[:count].reshape(-1), torch.stack(per_batch).double().reshape(-1)]).cpu()          # the one read
+    mean = host[:3].tolist()
+    running = host[3:3 + 3 * count].reshape(count, 3).numpy()
+    losses_host = host[3 + 3 * count:].reshape(count, 3).float().numpy()
+    return ValidationResult(mean[0], mean[1], mean[2], running, losses_host)
 
 
 class _ReadbackSlot(object):

@@ -43,7 +43,8 @@ extern "C" {
  * endo_sgd_clip_step takes a `skip_flag` device pointer; endo_net16_offset what = 7; adds endo_hsv_full.
  * 6: round 6 -- adds endo_warp_consistency_bytes, the option ENDO_OPT_TD_PERSIST and the value ENDO_OPT_WINO_DGRAD = 3; since then
  * (unchanged by additions) endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the endo_augment_frame
- * record; then endo_evaluate and endo_evaluate_workspace_bytes -- entry points only, no existing signature changes. */
+ * record; then endo_evaluate and endo_evaluate_workspace_bytes; then endo_loss_head_planes, endo_display, endo_display_workspace_bytes,
+ * endo_display_panel_shape and endo_validation_accumulate -- entry points only, no existing signature changes. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -160,6 +161,11 @@ int endo_loss_head(const float* pred_1, const float* pred_2, const float* bounda
                    const float* intrinsics, float sfl_weight, float dcl_weight, float eps,
                    float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace,
                    int n, int h, int w, void* stream);
+/* offsets[6] (host int64, in floats from `workspace`) of six planes endo_loss_head leaves in its workspace: the scaled depths 1 and 2
+ * (n x 1 x H x W each), the masked flows from depth 1 and 2 and the masked sparse flows 1 and 2 (n x 2 x H x W each) -- what
+ * endo_display renders after a training or validation call, without a recompute.  The head's own carving, one function for both.
+ * ENDO_E_BADARG for bad sizes or a null `offsets`. */
+int endo_loss_head_planes(int n, int h, int w, int64_t* offsets);
 
 /* Depth warp both ways + depth-consistency loss, forward AND backward, in one call -- reference models.py:454-554 (DepthWarpingLayer,
  * once per direction), losses.py:112-146 (NormalizedDistanceLoss, once per direction), train.py:305-314, and their backward:
@@ -464,6 +470,33 @@ int64_t endo_evaluate_workspace_bytes(int frames, int height, int width);
 int endo_evaluate(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics, int frames,
                   int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
                   int64_t* frame_offsets, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Display panel of a training or validation batch -- reference train.py:353-371 / 460-478 (utils.display_color_depth_sparse_flow_
+ * dense_flow for both frames, draw_flow, stack_and_display, utils.py:868-900, 965-994, over torchvision 0.7-era make_grid; always
+ * color_reverse = True, as train.py passes it).  out: [8 rows_per_section][cols][3] uint8 R, G, B (endo_display_panel_shape), the
+ * sections c1, d1, sf1, df1, c2, d2, sf2, df2 top to bottom, each make_grid(nrow = 8, padding = 2, pad_value = 0) of the batch
+ * (N = 1: the frame itself, unpadded) -- what a tensorboardX SummaryWriter.add_image stores for the reference's float image:
+ *   c   trunc(clip(255 (0.5 c + 0.5)))                         colors_k [N][3][H][W]: the masked network input (train.py:272-273)
+ *   d   COLORMAP_JET[u8(255 norm(b d))], B, G, R -> R, G, B    depths_k [N][1][H][W] (multiplied by `boundaries` [N][1][H][W] here),
+ *       norm per frame: (clamp(x) - min) / fl32(max - min + 1e-5)   padding: JET entry 0
+ *   sf  draw_flow(sparse_flows_k) [N][2][H][W]                  HSV (trunc(ang 90 / pi), 255, trunc(min(v / max_v, 1) 255)), cv2's
+ *   df  draw_flow(flows_k, max_v of sf)  [N][2][H][W]           8-bit COLOR_HSV2BGR then BGR -> RGB; padding black; max_v = 0: V = 0
+ * numpy's / torch's float32 roundings throughout, the angle the correctly rounded float32 atan2.  JET and the HSV conversion are
+ * restated (PARITY UNPINNED against cv2, not installed).  Two launches whatever N.  N <= 65535, N * H * W < 2^31.  workspace: 16-byte
+ * aligned, endo_display_workspace_bytes(n, h, w) bytes.  ENDO_E_BADARG for null pointers, bad sizes or a short workspace. */
+int64_t endo_display_workspace_bytes(int n, int h, int w);
+int endo_display_panel_shape(int n, int h, int w, int* rows, int* cols);
+int endo_display(const float* colors_1, const float* colors_2, const float* depths_1, const float* depths_2, const float* boundaries,
+                 const float* sparse_flows_1, const float* sparse_flows_2, const float* flows_1, const float* flows_2, int n, int h, int w,
+                 uint8_t* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Running means of the validation pass -- reference train.py:446-456, in fp64 with the Python float's roundings.  losses: the
+ * device [total, dcl, sfl] floats of batch `batch_index` (endo_loss_head's first three); means: 3 fp64 on the device, updated in
+ * place: unchanged when the total is NaN (Inf is accumulated), the losses at batch 0, (mean k + loss) / (k + 1.0) at batch k > 0.
+ * history: null, or fp64 [>= batch_index + 1][3] whose row batch_index receives the means after the update (train.py:481-483 logs
+ * them per batch).  One single-thread launch. */
+int endo_validation_accumulate(const float* losses, int batch_index, double* means, double* history, void* stream);
 
 /* live per-kernel-family timing for bench.py's roofline line: HIP events recorded on the launch
  * stream around every entry of the selected families.  family_mask: bit f enables family f
