@@ -19,6 +19,24 @@
  *   - return value: 0 = ok, > 0 = hipError_t, < 0 = argument error (ENDO_E_*)
  *   - `stats` / `work` arguments are small fp64 device scratch arrays that the call zeroes itself;
  *     the forward call's `stats` must be handed unchanged to the matching backward call
+ *
+ * Workspace contract (every entry point; tests/test_gpu_workspace_contract.py holds the library to it with guard bands around, and
+ * NaN poison inside, every buffer the Python side allocates -- DESIGN.md 2.1)
+ *   1. A call writes nothing outside [ptr, ptr + size) of the buffers it is given, where size is what the matching endo_*_floats /
+ *      endo_*_bytes query returned (for an output tensor: its documented shape).  Where an argument carries the size
+ *      (workspace_bytes), a short buffer is ENDO_E_BADARG, not an overrun.
+ *   2. The contents of a workspace or output buffer ON ENTRY are ignored: whatever a call reads from one, it has written itself
+ *      earlier in the same call.  NaN, stale results of another shape, or zeros give the same result.
+ *   SCRATCH (no meaning once the call's work has passed `stream`): gradws, the 16-bit families' `ws`, winner_scratch, row_offsets, and
+ *   the workspaces of endo_warp_consistency, endo_jpeg_decode_crop, endo_augment, endo_evaluate and endo_display.
+ *   STATE, i.e. written by one call and read by a later one, so the caller must leave it untouched in between:
+ *     - `tape` (both network families): written by *_fwd, read (never written) by the matching *_bwd;
+ *     - `stats` of the geometry / loss modules, forward to backward (above);
+ *     - the workspace of endo_loss_head: on return it holds the six planes endo_loss_head_planes describes, which endo_display
+ *       reads; scratch again from the next endo_loss_head on it;
+ *     - `grads` (ACCUMULATED into), `params`, `momentum`, `bn_running`, and the means / history of endo_validation_accumulate.
+ *   An output whose documented extent depends on the data (the point rows of endo_point_cloud / endo_evaluate: *count_out,
+ *   frame_offsets) is written up to that extent only; rows behind it keep whatever they held.
  */
 #ifndef ENDO_HIP_H
 #define ENDO_HIP_H
@@ -146,7 +164,8 @@ int endo_scale_inv_bwd(const float* grad_loss, const float* pred, const float* g
  * that want the pieces).  pred_*: n x 1 x H x W network outputs; the other inputs are the batch tensors of train.py:245-270
  * (sparse flows n x 2 x H x W; t n x 3, R / K n x 9).  losses: FOUR fp32 on the device = total, depth-consistency, sparse-flow
  * (weights applied: w * 0.5 * (term_1 + term_2)) and the guard flag of train.py:317 (1.0 when the total is NaN / Inf, else 0.0).
- * grad_pred_*: n x 1 x H x W, written.  workspace: 16-byte aligned, endo_loss_head_workspace_floats(n, h, w) floats.  The caller
+ * grad_pred_*: n x 1 x H x W, written.  workspace: 16-byte aligned, endo_loss_head_workspace_floats(n, h, w) floats; its contents on entry
+ * are ignored and nothing outside those floats is written; on return it is STATE until the next call on it (endo_loss_head_planes).  The caller
  * feeds grad_pred_* to endo_net_bwd without waiting for the host and hands &losses[3] (or its all-reduced sum) to
  * endo_sgd_clip_step as `skip_flag`: the reference's guarded branch also runs backward() and then a step() that changes nothing
  * (train.py:318-321).
@@ -172,7 +191,8 @@ int endo_loss_head_planes(int n, int h, int w, int64_t* offsets);
  *   loss[0] = dcl_weight * 0.5 * (NDL(depth_1, warp(depth_2 -> 1)) + NDL(depth_2, warp(depth_1 -> 2)))
  *   grad_depth_k = d loss / d depth_k  (through the loss terms, the sampling grids and the sampled images)
  * depth_k: the (scaled) depth maps N x 1 x H x W; poses and intrinsics as endo_loss_head.  This is the chain BASELINE.json's second
- * metric times ("depth-warp fwd+bwd ms / pair").  workspace: endo_warp_consistency_workspace_floats(n, h, w) floats, 16-byte aligned. */
+ * metric times ("depth-warp fwd+bwd ms / pair").  workspace: endo_warp_consistency_workspace_floats(n, h, w) floats, 16-byte aligned:
+ * scratch -- contents on entry ignored, nothing outside those floats written, as for loss and grad_depth_k (every element written). */
 int64_t endo_warp_consistency_workspace_floats(int n, int h, int w);
 /* algorithmic HBM bytes of one call (160 B per pixel of a frame pair, both directions, forward and backward) */
 int64_t endo_warp_consistency_bytes(int n, int h, int w);
@@ -199,8 +219,16 @@ int endo_mask_mul(const float* a, const float* mask, float* out, int n, int c, i
  *              backward accumulation per step, train.py:276-277, 325)
  *   bn_running fp32, running_mean then running_var of the 49 BN layers in module order
  *   tape       fp32 activation workspace of endo_net_tape_floats() elements, written by fwd and
- *              read by bwd (one tape per forward call that will be differentiated)
- *   gradws     fp32 gradient workspace of endo_net_gradws_floats() elements (scratch for bwd)
+ *              read by bwd (one tape per forward call that will be differentiated).  fwd ignores what it
+ *              held on entry (it clears the regions it accumulates into) and writes nothing outside those
+ *              elements; between fwd and bwd it is STATE; bwd does not write it.
+ *   gradws     fp32 gradient workspace of endo_net_gradws_floats() elements (scratch for bwd: contents on
+ *              entry ignored, nothing outside those elements written, nothing kept from call to call).
+ *              With several sample groups both sizes are groups x endo_net_group_stride() and each group
+ *              works inside its own stride.  The fixed-size scratch regions inside both (split-K partials,
+ *              weight-gradient partials, bias and final-convolution partials) are bounds over every input
+ *              endo_net_create_grouped accepts; DESIGN.md 2.1 lists the inputs that come closest to each.
+ *   out        n x 1 x H x W, every element written.
  * ------------------------------------------------------------------------------------------- */
 typedef struct endo_net endo_net;
 
@@ -330,7 +358,8 @@ int endo_sgd_clip_step(float* params, float* grads, float* momentum, double* nor
  * [2][B][1][H][W], flows [2][B][2][H][W] (u then v, divided by W and H; entries with |flow| > 5 zeroed,
  * utils.py:566-569,603-606).  depths are multiplied by depth_multiplier (1 = the reference function;
  * 1 / global_scale folds in dataset.py:391-392).  Pixel collisions: the highest point index wins (numpy
- * fancy-index assignment).  winner_scratch: 2*B*H*W int32 of workspace.
+ * fancy-index assignment).  winner_scratch: 2*B*H*W int32 of workspace (scratch: contents on entry ignored,
+ * nothing outside it written; the four outputs are written in full).
  * ------------------------------------------------------------------------------------------- */
 int endo_sparse_scatter(const double* points, int n_points, const double* projections, const double* extrinsics,
                         const float* visibility, const float* clean, const uint8_t* mask, int batch, int height, int width,
@@ -351,7 +380,8 @@ int endo_relative_poses(const double* pair_extrinsics, int batch, double scale,
  * intrinsics [3][3] fp32.  A pixel is kept when h % downsampling == 0, w % downsampling == 0, mask > 0.5 and, with
  * use_threshold != 0, max(r,g,b) >= max_threshold && min(r,g,b) <= min_threshold.  points receives
  * (x, y, z, r, g, b) = ((w - cx) / fx * z, (h - cy) / fy * z, z, r, g, b) per kept pixel in row-major pixel order
- * (capacity H * W rows of 6 floats); *count_out the number of rows written.  row_offsets: H + 1 int32 of workspace.
+ * (capacity H * W rows of 6 floats); *count_out the number of rows written.  row_offsets: H + 1 int32 of workspace
+ * (scratch: contents on entry ignored, nothing outside it written; rows of `points` behind *count_out are not written).
  * ------------------------------------------------------------------------------------------- */
 int endo_point_cloud(const float* depth, const uint8_t* color_bgr, const float* mask, const float* intrinsics, int height,
                      int width, int downsampling, int use_threshold, float min_threshold, float max_threshold,
@@ -368,7 +398,8 @@ int endo_point_cloud(const float* depth, const uint8_t* color_bgr, const float* 
  *   endo_jpeg_entropy_decode  host only: the coefficient blocks the device stage starts from -- total_blocks x 64 int16,
  *                             component planes one after the other, blocks row-major inside a plane, coefficients in
  *                             natural (row-major, de-zigzagged) order, not dequantised; quant: [3][64] uint16, natural order.
- *   endo_jpeg_workspace_bytes bytes of `staging` (host; pinned for an asynchronous copy) and of `workspace` (device).
+ *   endo_jpeg_workspace_bytes bytes of `staging` (host; pinned for an asynchronous copy) and of `workspace` (device).  Both are
+ *                             scratch: contents on entry ignored, nothing outside workspace_bytes written.
  *   endo_jpeg_decode_crop     parses and Huffman-decodes on the calling thread into `staging`, copies to `workspace` on
  *                             `stream` and launches the inverse DCT and the resize/crop kernels there.  out_hwc: device
  *                             uint8 [H][W][3] (rgb_order != 0: R,G,B as rgb_mode "rgb"; 0: B,G,R as cv2.imread) or NULL;
@@ -437,7 +468,8 @@ typedef struct endo_augment_frame {
 } endo_augment_frame;
 /* sizeof(endo_augment_frame) (1344), for bindings that mirror the record */
 int endo_augment_frame_bytes(void);
-/* device workspace bytes of endo_augment for `frames` frames of height x width (-1 for bad sizes) */
+/* device workspace bytes of endo_augment for `frames` frames of height x width (-1 for bad sizes).  The workspace is scratch: contents on
+ * entry ignored, nothing outside workspace_bytes written; out_u8 / out_f32 are written in full. */
 int64_t endo_augment_workspace_bytes(int frames, int height, int width);
 /* src: device uint8 [frames][H][W][3] RGB (read only); params: HOST array of `frames` records, copied to the workspace on `stream`
  * (pinned memory for an asynchronous copy; untouched until `stream` has passed the call); out_u8: device uint8 [frames][H][W][3]
@@ -465,7 +497,8 @@ int endo_augment(const uint8_t* src, const endo_augment_frame* params, int frame
  *   frame_offsets  [N + 1] int64       frame f's rows are [frame_offsets[f], frame_offsets[f + 1])
  * Three launches whatever N.  N <= 65535, N * H * W < 2^31.  ENDO_E_BADARG for null pointers, bad sizes, is_hsv not 0 / 1,
  * downsampling < 1 or a short workspace. */
-/* device workspace bytes of endo_evaluate (-1 for bad sizes) */
+/* device workspace bytes of endo_evaluate (-1 for bad sizes).  The workspace is scratch: contents on entry ignored, nothing outside
+ * workspace_bytes written; depth, panels and frame_offsets are written in full, `points` up to frame_offsets[frames] rows. */
 int64_t endo_evaluate_workspace_bytes(int frames, int height, int width);
 int endo_evaluate(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics, int frames,
                   int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
@@ -484,7 +517,8 @@ int endo_evaluate(const float* colors, const float* boundaries, const float* pre
  *   df  draw_flow(flows_k, max_v of sf)  [N][2][H][W]           8-bit COLOR_HSV2BGR then BGR -> RGB; padding black; max_v = 0: V = 0
  * numpy's / torch's float32 roundings throughout, the angle the correctly rounded float32 atan2.  JET and the HSV conversion are
  * restated (PARITY UNPINNED against cv2, not installed).  Two launches whatever N.  N <= 65535, N * H * W < 2^31.  workspace: 16-byte
- * aligned, endo_display_workspace_bytes(n, h, w) bytes.  ENDO_E_BADARG for null pointers, bad sizes or a short workspace. */
+ * aligned, endo_display_workspace_bytes(n, h, w) bytes, scratch: contents on entry ignored, nothing outside those bytes written; `out` is
+ * written in full.  ENDO_E_BADARG for null pointers, bad sizes or a short workspace. */
 int64_t endo_display_workspace_bytes(int n, int h, int w);
 int endo_display_panel_shape(int n, int h, int w, int* rows, int* cols);
 int endo_display(const float* colors_1, const float* colors_2, const float* depths_1, const float* depths_2, const float* boundaries,
@@ -535,7 +569,8 @@ int endo_bf16_conv(const void* in, int in_t, int in_blk, int ic0, int cin, const
  * rounded to bf16 on the way in.  training != 0: batch statistics + running-statistics update; 0: running statistics (the
  * evaluate.py path).  tape: endo_net16_tape_bytes() bytes of device memory, 256-byte aligned.  H and W multiples of 32.
  * endo_net16_bwd: its backward pass.  tape: the forward call's tape, untouched since; grad_out: fp32 [n][1][H][W]; grads: the flat
- * fp32 parameter-gradient buffer (offsets of endo_net_param_offset), ACCUMULATED into; ws: endo_net16_bwd_workspace_bytes() bytes,
+ * fp32 parameter-gradient buffer (offsets of endo_net_param_offset), ACCUMULATED into; ws: endo_net16_bwd_workspace_bytes() bytes (scratch: contents on entry ignored, nothing outside them written -- every
+ * launch is checked against that size),
  * 256-byte aligned; training as in the forward call (0: BatchNorm as a fixed affine map).  Gradients between layers are stored as
  * bf16; BatchNorm sums (fp64), parameter gradients and the deferred BatchNorm terms (fp32) are not. */
 typedef struct endo_net16 endo_net16;
