@@ -35,9 +35,9 @@ struct WinoDgradTable {
 // U[group][xi][c][j] = (G g' G^T)[xi],  g'[a][b] = W[c][16 group + j][2 - a][2 - b]  (the flipped filter of the data gradient)
 // layout 0: [group][xi][c][j] (dgrad_wino8_kernel: dword B reads);  layout 1: [group][c][a][j][i], xi = 4 a + i (dgrad_wino3_kernel:
 // one 16-byte B read per transform row)
-// layout1_max_groups: layers whose block has at most this many base-channel groups get layout 1 (0: layout 0 everywhere)
+// layout1_blocks: bit b set = the four layers of dense block b (table entries 4 b .. 4 b + 3) get layout 1 (0: layout 0 everywhere)
 static __global__ void __launch_bounds__(256) dgrad_wino_weights_kernel(const WinoDgradTable t, const float* __restrict__ params, float* __restrict__ u,
-                                                                 int layout1_max_groups = 0) {
+                                                                 int layout1_blocks = 0) {
     const int total = t.start[t.layers];
     for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < total; item += gridDim.x * blockDim.x) {
         int l = 0;
@@ -65,7 +65,7 @@ static __global__ void __launch_bounds__(256) dgrad_wino_weights_kernel(const Wi
             h[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
             h[3][b] = g[2][b];
         }
-        if (t.groups[l] <= layout1_max_groups) {
+        if ((layout1_blocks >> (l >> 2)) & 1) {
             float* dst = u + t.u_off[l] + static_cast<int64_t>(grp) * kWinoDgradSlice + (c * 64 + j) * 4;
 #pragma unroll
             for (int a = 0; a < 4; ++a)

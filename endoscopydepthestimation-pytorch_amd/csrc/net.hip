@@ -33,7 +33,6 @@
 #include "dgrad_wino_kernels.h"
 #include "dgrad_wino3_kernels.h"
 
-#include <cstdlib>
 
 namespace endo {
 
@@ -578,6 +577,63 @@ __global__ void __launch_bounds__(64) final_w_reduce_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// the plan: which kernel form every launch of a pass takes
+// ---------------------------------------------------------------------------------------------
+// Filled once at the top of endo_net_fwd / endo_net_bwd by plan_fwd / plan_bwd (below the parameter fillers they share with the launch
+// functions) from the network, its options (documented in include/endo_hip.h), the pass's pointers and the training flag.  The launch
+// functions switch on it and the weight-preparation launches read the same entries, so a layer's prepared weights are in the layout the
+// kernel that runs reads, by construction.  Dense blocks are numbered the way the weight tables are laid out: 0-4 the down path,
+// 5 the bottleneck, 6-10 the up path (coarsest first); dense layer j of block b is entry 4 b + j.
+constexpr int kBlocks = 2 * kLevels + 1, kDense = kBlocks * kLayers;
+
+enum class DenseFwd { Wino4, Wino2_32x16, Wino2_32x8, SplitK, Direct32x8, Direct16x8, DirectAuto };          // F(4x4, 3x3) | F(2x2, 3x3) by tile | direct kernels
+struct FwdPlan {
+    struct Dense {
+        DenseFwd form;
+        int stages;                   // LDS stages of the F(2x2, 3x3) forms
+        int ksplit;                   // K slices of SplitK
+        bool chunk_weights;           // the layer's slot of the prepared weights holds the direct kernel's K-chunk order (WinoWeightTable::mode 1)
+    } dense[kDense];
+    bool bf16;                        // bf16 MFMA operands: direct kernels only, no prepared weights
+    bool wino4_weights;               // the F(4x4, 3x3) weights are prepared
+    bool fuse_final;                  // the network's last dense layer also forms the final convolution's sum over its 180 input channels
+    bool td_persistent[kLevels];      // td_fwd_kernels.h instead of the per-tile kernel
+    bool tu_subpix[kLevels];          // by the level the transition writes: the sub-pixel form instead of upsample-then-convolve
+};
+
+enum class NewMap { Bf16, Persistent, Vec16, Dword };
+enum class BasePass { Block8, Block8Bf16, Wino3, Wino3Persistent, Wino8 };
+enum class DenseWgrad { F34, X3, NSplit, Taps, Direct };
+enum class TdDgrad { Persistent, Runs128, Dma, Staged };
+enum class TuWgrad { Subpix, Taps, Direct };
+enum class TuDgrad { Subpix32x8, Subpix16x8, Subpix16x4, Plain };
+enum class FirstWgrad { F34Prep, F34, Taps, Direct };
+struct BwdPlan {
+    struct Block {
+        bool fused;                   // new-map passes + one base pass (dgrad_block_kernels.h) instead of four per-layer data gradients
+        NewMap newmap[kLayers];       // [j]: the pass into layer j-1's maps from layers j..3 (j = 1..3)
+        BasePass base;
+        bool wino3_layout;            // its layers' data-gradient weights in the phase-skewed kernels' U layout (dgrad_wino_weights_kernel, layout 1)
+    } block[kBlocks];
+    DenseWgrad wgrad[kDense];
+    bool td_wgrad_dma[kLevels];
+    TdDgrad td_dgrad[kLevels];
+    TuWgrad tu_wgrad[kLevels];        // both by the level whose gradient the transition reads
+    TuDgrad tu_dgrad[kLevels];
+    int overlap;                      // ENDO_OPT_WGRAD_OVERLAP as set
+    bool bf16_wgrad, bf16_dgrad;      // operands rounded to bf16 in the kernels that have such a form
+    int f34_blocks;                   // blocks of a dense F(3x3, 4x4) weight-gradient launch
+    bool dgrad_weights;               // the Winograd-domain data-gradient weights are prepared
+    // final convolution (FinalVirt) and first convolution
+    bool use_virt;                    // the last up block forms the final convolution's data gradient where it first touches a channel ...
+    bool virt_base;                   // ... its base pass too
+    bool virt_base_w;                 // ... which then also forms that convolution's weight gradient of the base channels
+    int materialise;                  // channels [0, materialise) are written out by final_bwd_data_kernel
+    int c_first;                      // final_bwd_weight_kernel starts at this channel
+    FirstWgrad first;
+};
+
+// ---------------------------------------------------------------------------------------------
 // schedule helpers
 // ---------------------------------------------------------------------------------------------
 struct Ctx {
@@ -590,12 +646,15 @@ struct Ctx {
     int training;
     hipStream_t stream;
     BiasParts* bias_parts = nullptr;
+    const float* x = nullptr;              // endo_net_bwd: the caller's image tensor
+    const FwdPlan* fwd = nullptr;          // the pass's plan (one of the two)
+    const BwdPlan* bwd = nullptr;
 
     int nt() const { return net->n * net->groups; }      // samples of all groups
     // context of the weight-gradient side stream, ordered after everything issued so far on the main stream
     int fork_wgrad(Ctx& side, int level) const {
         side = *this;
-        if (!net->wstream || !net->opt[ENDO_OPT_WGRAD_OVERLAP] || level < kSideStreamFromLevel) return 0;          // run in line
+        if (!net->wstream || !bwd->overlap || level < kSideStreamFromLevel) return 0;          // run in line
         ENDO_CHECK(hipEventRecord(net->ev_fork, stream));
         ENDO_CHECK(hipStreamWaitEvent(net->wstream, net->ev_fork, 0));
         side.stream = net->wstream;
@@ -656,22 +715,7 @@ static double conv_flops(const endo_net* net, int level, int cin, int cout, int 
     return 2.0 * net->n * net->groups * net->lv[level].plane * cin * cout * ks * ks;
 }
 
-// Tuning options, per network handle (endo_net_set_option; defaults set by endo_net_create*, no environment variables):
-//   ENDO_OPT_WINO_FWD        dense-layer forward at the fine levels: 0 = direct convolution, 1 = Winograd F(2x2, 3x3) (2 LDS stages), 3 / 4 = the same
-//                            with 3 / 4 stages, 5 (default) = F(4x4, 3x3) for the launches that fill the chip with 64 x 16 blocks, F(2x2, 3x3) for the rest
-//   ENDO_OPT_WINO_DGRAD      fused base-channel data gradient at the fine levels: 0 = direct, 1 = Winograd, phase-skewed (dgrad_wino3_kernels.h),
-//                            2 = Winograd, round-2 kernel (dgrad_wino_kernels.h), 3 (default) = 1 as persistent blocks where that form applies
-//                            (dgrad_wino3p_kernels.h: at most 144 base channels), the per-tile kernel elsewhere
-//   ENDO_OPT_DGRAD_VEC       new-channel passes: 2 (default) = persistent blocks (dgrad_newmap_kernels.h), 1 / 0 = one block per tile with 16-byte / dword
-//                            DMA of the gradient tiles (dgrad_block_kernels.h)
-//   ENDO_OPT_MFMA_BF16       1 = bf16 MFMA operands in the dense layers' kernels (a different function: DESIGN.md 4.10)
-//   ENDO_OPT_WINO_MIN_TILES  a Winograd kernel is used from this many tiles per launch on (default 1024: the levels whose launches fill
-//                            the chip several times; tests set 1 to reach the kernels at small sizes)
-//   ENDO_OPT_MFMA_X3         bit mask of the kernel families (1 wgrad, 2 forward, 4 dgrad) that evaluate fp32 products as three-term bf16 splits (common.h)
-//   ENDO_OPT_WGRAD_OVERLAP   1 = weight gradients on the side stream, 0 = in line on the caller's stream
-//   ENDO_OPT_WGRAD_F34       1 = dense weight gradients of the fine levels in the Winograd domain F(3x3, 4x4) (wgrad_f34_kernels.h)
-//   ENDO_OPT_FINAL_VIRTUAL   1 = the final convolution's data gradient is not written out: the last up block's kernels form g * w[c] (FinalVirt)
-//   ENDO_OPT_TD_PERSIST      transition-down layers as persistent blocks: bit 0 the data gradient (td_dgrad_kernels.h), bit 1 the forward (td_fwd_kernels.h)
+// Defaults of the per-handle options (endo_net_set_option; include/endo_hip.h documents every value).  plan_fwd / plan_bwd are their only readers.
 static void default_options(int (&opt)[ENDO_OPT_COUNT]) {
     opt[ENDO_OPT_WINO_FWD] = 5;          // F(4x4, 3x3) where its 64 x 16 blocks fill the chip (level 0 of configs[1]), F(2x2, 3x3) below: depth 5e-6 of its maximum from fp64 against the 1e-4 of the parity target
     opt[ENDO_OPT_WINO_DGRAD] = 3;
@@ -684,147 +728,45 @@ static void default_options(int (&opt)[ENDO_OPT_COUNT]) {
     opt[ENDO_OPT_FINAL_VIRTUAL] = 1;
     opt[ENDO_OPT_TD_PERSIST] = 3;
 }
-static int wino_fwd_mode(const Ctx& c) { return c.net->opt[ENDO_OPT_WINO_FWD]; }
-static bool wino_fwd_enabled(const Ctx& c) { return wino_fwd_mode(c) != 0; }
-static int wino_dgrad_mode(const Ctx& c) { return c.net->opt[ENDO_OPT_WINO_DGRAD]; }
-static bool wino_dgrad_enabled(const Ctx& c) { return wino_dgrad_mode(c) != 0; }
-static bool dgrad_vec_enabled(const Ctx& c) { return c.net->opt[ENDO_OPT_DGRAD_VEC] != 0; }
-// bit 0: weight gradients, bit 1: forward, bit 2: data gradients of the dense layers (1 = all three)
-static int mfma_bf16_mask(const Ctx& c) { const int v = c.net->opt[ENDO_OPT_MFMA_BF16]; return v == 1 ? 7 : (v >> 1); }
-static bool mfma_bf16_wgrad(const Ctx& c) { return (mfma_bf16_mask(c) & 1) != 0; }
-// operand mode of a dense-layer weight gradient: 0 fp32 MFMA, 1 operands rounded to bf16, 2 fp32 operands as three-term bf16 splits
-static int wgrad_mfma_mode(const Ctx& c) { return mfma_bf16_wgrad(c) ? 1 : ((c.net->opt[ENDO_OPT_MFMA_X3] & 1) ? 2 : 0); }
-static bool mfma_bf16_fwd(const Ctx& c) { return (mfma_bf16_mask(c) & 2) != 0; }
-static bool mfma_bf16_dgrad(const Ctx& c) { return (mfma_bf16_mask(c) & 4) != 0; }
+// ENDO_OPT_MFMA_BF16 as a mask of kernel families -- bit 0: weight gradients, bit 1: forward, bit 2: data gradients of the dense layers (1 = all three)
+static int bf16_mask(const int* opt) { const int v = opt[ENDO_OPT_MFMA_BF16]; return v == 1 ? 7 : (v >> 1); }
 
-// dense layer forward: BN -> ReLU -> conv3x3 -> +12 channels (reference models.py:19-28, 44-52)
-// fin_w / fin_pre / fused_final: the network's last dense layer may also form the final convolution's sum over its input channels
-// (ConvParams::fin_w); *fused_final says whether the kernel form that ran did
-// The tile-count part of dense_fwd's choice of a Winograd form at a level (the kernels' own shape checks can still send a layer to the direct
-// kernel).  Where neither holds the level's dense layers run the direct kernel, and the forward pass prepares their weights in the K-chunk
-// pipeline's order instead of the Winograd domain (WinoWeightTable::mode 1, ConvParams::wgt_chunks).
-static bool dense_fwd_wino4_tiles(const Ctx& c, int level) {
-    const auto& lv = c.net->lv[level];
-    const long t4 = static_cast<long>((lv.w + 63) / 64) * ((lv.h + 15) / 16) * c.nt();
-    return wino_fwd_mode(c) == 5 && !mfma_bf16_fwd(c) && 2 * t4 >= c.net->opt[ENDO_OPT_WINO_MIN_TILES];
+// Dense block b (numbering: FwdPlan): level-buffer channels [ic0, ic0 + c0) are its input ("base"), layer j reads [ic0, ic0 + c0 + 12 j)
+// and writes the 12 maps behind them
+struct DenseBlock { int level, ic0, c0; const BnP* bn; const ConvP* cv; bool base_overwrite; };          // base_overwrite: the backward pass is the first writer of the base channels' gradient
+static DenseBlock dense_block(int b) {
+    const Table& tb = table();
+    if (b < kLevels) return {b, 48, down_in(b), tb.down_bn[b], tb.down_conv[b], false};
+    if (b == kLevels) return {kLevels, 0, 288, tb.bott_bn, tb.bott_conv, true};
+    const int i = b - kLevels - 1, l = kLevels - 1 - i;
+    return {l, 0, 96 + down_in(l), tb.up_bn[i], tb.up_conv[i], l > 0};
 }
-static bool dense_fwd_wino2_tiles(const Ctx& c, int level) {
+static long tile_count(const Ctx& c, int level, int tx, int ty) {          // tx x ty pixel tiles of a launch over the level, partial ones included
     const auto& lv = c.net->lv[level];
-    const long t16 = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 15) / 16) * c.nt();
-    const long t8 = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 7) / 8) * c.nt();
-    const long min_tiles = c.net->opt[ENDO_OPT_WINO_MIN_TILES];
-    return wino_fwd_enabled(c) && !mfma_bf16_fwd(c) && (t16 >= min_tiles || t8 >= (min_tiles * 3) / 4);
-}
-static bool dense_fwd_chunk_weights(const Ctx& c, int level) {
-    return !mfma_bf16_fwd(c) && !dense_fwd_wino4_tiles(c, level) && !dense_fwd_wino2_tiles(c, level);
+    return static_cast<long>((lv.w + tx - 1) / tx) * ((lv.h + ty - 1) / ty) * c.nt();
 }
 
-static int dense_fwd(const Ctx& c, int level, int ic0, int oc0, const BnP& b, const ConvP& cv, const float* fin_w = nullptr, float* fin_pre = nullptr,
-                     bool* fused_final = nullptr) {
-    const auto& lv = c.net->lv[level];
+// dense layer forward: BN -> ReLU -> conv3x3 -> +12 channels (reference models.py:19-28, 44-52), with the weights where `form` reads them
+static ConvParams dense_fwd_params(const Ctx& c, const DenseBlock& k, int j, DenseFwd form) {
+    const ConvP& cv = k.cv[j];
+    const int oc0 = k.ic0 + k.c0 + kGrowth * j;
     ConvParams p{};
-    fill_grid(c, p, level);
-    fill_in(c, p, c.act(level), level, ic0, cv.cin);
-    fill_bn_in(c, p, b, level, ic0);
+    fill_grid(c, p, k.level);
+    fill_in(c, p, c.act(k.level), k.level, k.ic0, cv.cin);
+    fill_bn_in(c, p, k.bn[j], k.level, k.ic0);
     p.wgt = c.params + cv.w; p.bias = c.params + cv.b; p.w_cout = cv.cout; p.w_cin = cv.cin;
-    fill_out(c, p, c.act(level), level, oc0, cv.cout);
-    p.out_sums = c.out_sums(level, oc0);
-    ProfScope prof(kProfConv3x3Dense, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3),
-                   4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
-    // Fine levels: Winograd F(2x2, 3x3) on the matrix cores -- 4/9 of the multiply-accumulates (wino_fwd_kernels.h).
-    // 32 x 16 pixel tiles while they fill the chip several times over, 32 x 8 below that.
-    if (cv.u >= 0 && dense_fwd_wino4_tiles(c, level)) {          // F(4x4, 3x3): 36 instead of 64 products per 16 pixels (wino4_fwd_kernels.h)
-        ConvParams p4 = p;
-        p4.wgt = c.tape + c.net->wino4_off + cv.u / kWinoUStride * kW4UStride;
-        if (wino4_fwd_ok(p4)) {          // (level 0 of configs[1]: at level 1 the 64 x 16 blocks no longer fill the chip, measured slower)
-            if (fin_w && fused_final && c.net->opt[ENDO_OPT_FINAL_VIRTUAL]) { p4.fin_w = fin_w + ic0; p4.fin_out = fin_pre; *fused_final = true; }
-            return launch_wino4_fwd(p4, c.stream);
-        }
-    }
-    if (cv.u >= 0 && dense_fwd_wino2_tiles(c, level)) {
-        ConvParams pw = p;
-        pw.wgt = c.tape + c.net->wino_off + cv.u;          // group 0's tape: weights are shared by the groups
-        const long t16 = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 15) / 16) * c.nt();
-        const long t8 = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 7) / 8) * c.nt();
-        if (wino_fwd_ok(pw)) {
-            const int mode = wino_fwd_mode(c);          // in-job A/B: 1 = 2 LDS stages (default), 3 = 3 stages, 4 = 4 stages
-            const long min_tiles = c.net->opt[ENDO_OPT_WINO_MIN_TILES];
-            const bool big = t16 >= min_tiles, small = t8 >= (min_tiles * 3) / 4;
-            if (mode == 4) {
-                if (big) return launch_wino_fwd<2, 4, 2, 4>(pw, c.stream);
-                if (small) return launch_wino_fwd<1, 4, 3, 4>(pw, c.stream);
-            }
-            if (mode == 3) {
-                if (big) return launch_wino_fwd<2, 4, 2, 3>(pw, c.stream);
-                if (small) return launch_wino_fwd<1, 4, 3, 3>(pw, c.stream);
-            }
-#ifdef ENDO_WINO_DIAG          // stub-out timing variants of the level-0 kernel (wrong results): -DENDO_WINO_DIAG, ENDO_WINO_EXP=<mask>
-            if (big) {
-                static const int exp = [] { const char* e = std::getenv("ENDO_WINO_EXP"); return e ? std::atoi(e) : 0; }();
-                switch (exp) {
-                    case 14: return launch_wino_fwd<2, 4, 2, 2, 14>(pw, c.stream);
-                    case 30: return launch_wino_fwd<2, 4, 2, 2, 30>(pw, c.stream);
-                    case 31: return launch_wino_fwd<2, 4, 2, 2, 31>(pw, c.stream);
-                    case 63: return launch_wino_fwd<2, 4, 2, 2, 63>(pw, c.stream);
-                    case 64: return launch_wino_fwd<2, 4, 2, 2, 64>(pw, c.stream);
-                    default: break;
-                }
-            }
-#endif
-            if (big) return launch_wino_fwd<2, 4, 2, 2>(pw, c.stream);
-            // (round 5, in-job A/B of the level-1 launch: K-chunks of 8 channels, 3 or 4 LDS stages, 4 blocks per CU -- all within +-0.2 % of this form)
-            if (small) return launch_wino_fwd<1, 4, 3, 2>(pw, c.stream);
-        }
-    }
-    // Coarse levels have too few 16x8 tiles to fill 256 CUs and a long K loop (Cin up to 372): slice K over
-    // blockIdx.y, write raw partial sums, and let a small kernel add them up (+ bias, + BN statistics).
-    // Scratch bound: slices * N * plane <= (768 / tiles + 1) * 128 * tiles <= 98304 + 65536 floats per channel.
-    const long tiles_big = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 15) / 16) * c.nt();
-    const long tiles_mid = static_cast<long>((lv.w + 15) / 16) * ((lv.h + 15) / 16) * c.nt();
-    const long tiles_small = static_cast<long>((lv.w + 15) / 16) * ((lv.h + 7) / 8) * c.nt();
-    const int nchunks = (cv.cin + 15) / 16;
-    // both launches below that run on K-chunks of 16 channels take the chunk-ordered copy of the weights the pass prepared for this level
-    const float* chunk_weights = (cv.u >= 0 && dense_fwd_chunk_weights(c, level)) ? c.tape + c.net->wino_off + cv.u : nullptr;
-    if (tiles_big < 512 && tiles_mid < 384 && tiles_small < 512 && nchunks >= 4) {
-        int want = static_cast<int>(((tiles_small < 256 ? 512 : 768) + tiles_small - 1) / tiles_small);
-        if (want > nchunks) want = nchunks;
-        const int per = (nchunks + want - 1) / want;
-        const int ksplit = (nchunks + per - 1) / per;
-        float* partial = c.tape + c.net->partial_off;
-        p.ksplit = ksplit;
-        p.split_stride = static_cast<int64_t>(c.net->n) * cv.cout * lv.plane;      // inside one group's tape
-        p.out = partial; p.out_ns = static_cast<int64_t>(cv.cout) * lv.plane;
-        p.bias = nullptr; p.out_sums = nullptr;
-        p.wgt_chunks = chunk_weights;
-        int rc = mfma_bf16_fwd(c) ? launch_conv_dma<3, 16, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream)
-                             : launch_conv_dma<3, 16, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1>(p, c.stream);
-        if (rc) return rc;
-        int bx = static_cast<int>((lv.plane + 255) / 256);
-        bx = bx > 8 ? 8 : bx;
-        finalize_partial_kernel<<<dim3(bx, cv.cout, c.nt()), 256, 0, c.stream>>>(
-            partial, p.split_stride, ksplit, p.out_ns, static_cast<int>(lv.plane), c.params + cv.b, c.act(level) + oc0 * lv.plane,
-            lv.t * lv.plane, c.out_sums(level, oc0), c.net->n, c.net->gs);
-        ENDO_LAUNCH_CHECK();
-        return 0;
-    }
-    // Tile shape by block count (tools/conv_bench, Cin = 228 at 128x160): the launch wants >= ~1000 blocks.
-    //   16 samples: 32x16 (640 blocks) 257 us, 32x8 (1280) 216 us;   8 samples: 16x16 (640) 143 us, 16x8 (1280) 125 us
-    const long tiles_wide = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 7) / 8) * c.nt();
-    // level 0 stays on 32x16: in the training step (A/B of two library builds inside one job) it is 5 % faster than 32x8,
-    // although the isolated microbenchmark prefers 32x8 by 5 %
-    if (mfma_bf16_fwd(c)) {          // bf16 MFMA operands (ENDO_OPT_MFMA_BF16): the same tile shapes
-        if (tiles_big < 1024 && tiles_wide >= 1024) return launch_conv_dma<3, 4, 1, IN_BNRELU, EPI_FWD, 2, 4, 2, 1, 1>(p, c.stream);
-        if (tiles_big < 1024 && tiles_small >= 768) return launch_conv_dma<3, 8, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream);
-        return launch_conv_dma_auto<3, 4, 1, IN_BNRELU, EPI_FWD, 8, 2, 1, 1>(p, c.stream);
-    }
-    if (tiles_big < 1024 && tiles_wide >= 1024) return launch_conv_dma<3, 4, 1, IN_BNRELU, EPI_FWD, 2, 4, 2, 1>(p, c.stream);
-    if (tiles_big < 1024 && tiles_small >= 768) return launch_conv_dma<3, 8, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1>(p, c.stream);
-    p.wgt_chunks = chunk_weights;          // (only the KC = 16 instantiation the auto choice ends in for few tiles reads it)
-    return launch_conv_dma_auto<3, 4, 1, IN_BNRELU, EPI_FWD, 8, 2, 1>(p, c.stream);
+    fill_out(c, p, c.act(k.level), k.level, oc0, cv.cout);
+    p.out_sums = c.out_sums(k.level, oc0);
+    // the prepared weights live in group 0's tape: they are shared by the groups
+    if (form == DenseFwd::Wino4) p.wgt = c.tape + c.net->wino4_off + cv.u / kWinoUStride * kW4UStride;
+    if (form == DenseFwd::Wino2_32x16 || form == DenseFwd::Wino2_32x8) p.wgt = c.tape + c.net->wino_off + cv.u;
+    return p;
 }
 
 // transition down: BN -> ReLU -> conv1x1 -> maxpool2 into the next level (models.py:56-67)
-static int td_fwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
+static ConvParams td_fwd_params(const Ctx& c, int level) {
+    const BnP& b = table().td_bn[level];
+    const ConvP& cv = table().td_conv[level];
     const int next = level + 1;
     const int oc0 = next < kLevels ? 48 : 0;
     ConvParams p{};
@@ -836,35 +778,148 @@ static int td_fwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
     p.out_idx = c.idx(level);      // [n][cout][pooled plane] bytes, channel index relative to `out`
     p.idx_ns = static_cast<int64_t>(cv.cout) * c.net->lv[next].plane;
     p.out_sums = c.out_sums(next, oc0);
+    return p;
+}
+
+static FwdPlan plan_fwd(const Ctx& c) {
+    const int* opt = c.net->opt;
+    const int mode = opt[ENDO_OPT_WINO_FWD];
+    const long min_tiles = opt[ENDO_OPT_WINO_MIN_TILES];
+    FwdPlan pl{};
+    pl.bf16 = (bf16_mask(opt) & 2) != 0;
+    // mode 5 prepares the F(4x4, 3x3) weights whether or not a layer takes that form this pass (at small sizes none does)
+    pl.wino4_weights = !pl.bf16 && mode == 5;
+    for (int b = 0; b < kBlocks; ++b) {
+        const DenseBlock k = dense_block(b);
+        // Fine levels: Winograd on the matrix cores, from ENDO_OPT_WINO_MIN_TILES tiles per launch on.  F(4x4, 3x3), 36 instead of 64 products
+        // per 16 pixels (wino4_fwd_kernels.h), while its 64 x 16 blocks fill the chip (level 0 of configs[1]: at level 1 they no longer do, measured
+        // slower); below that F(2x2, 3x3), 4/9 of the multiply-accumulates (wino_fwd_kernels.h), on 32 x 16 pixel tiles while they fill the chip
+        // several times over, 32 x 8 below that.
+        const long t64x16 = tile_count(c, k.level, 64, 16), t32x16 = tile_count(c, k.level, 32, 16), t32x8 = tile_count(c, k.level, 32, 8);
+        const long t16x16 = tile_count(c, k.level, 16, 16), t16x8 = tile_count(c, k.level, 16, 8);
+        const bool big = t32x16 >= min_tiles, small = t32x8 >= (min_tiles * 3) / 4;
+        const bool wino4_tiles = mode == 5 && !pl.bf16 && 2 * t64x16 >= min_tiles;
+        const bool wino2_tiles = mode != 0 && !pl.bf16 && (big || small);
+        for (int j = 0; j < kLayers; ++j) {
+            FwdPlan::Dense& d = pl.dense[b * kLayers + j];
+            const int nchunks = (k.cv[j].cin + 15) / 16;
+            // Where the tile counts rule Winograd out the level's layers run a direct kernel and their weights are prepared in its K-chunk order.  (A
+            // layer that a Winograd kernel's own shape check sends to the direct kernel reads the original weights.)
+            d.chunk_weights = !pl.bf16 && !wino4_tiles && !wino2_tiles;
+            d.stages = mode == 4 ? 4 : (mode == 3 ? 3 : 2);          // in-job A/B: 2 LDS stages (default), 3, 4
+            if (wino4_tiles && wino4_fwd_ok(dense_fwd_params(c, k, j, DenseFwd::Wino4))) {
+                d.form = DenseFwd::Wino4;
+            } else if (wino2_tiles && wino_fwd_ok(dense_fwd_params(c, k, j, DenseFwd::Wino2_32x16))) {
+                // (round 5, in-job A/B of the level-1 launch: K-chunks of 8 channels, 3 or 4 LDS stages, 4 blocks per CU -- all within +-0.2 % of 32 x 8 with 2 stages)
+                d.form = big ? DenseFwd::Wino2_32x16 : DenseFwd::Wino2_32x8;
+            } else if (t32x16 < 512 && t16x16 < 384 && t16x8 < 512 && nchunks >= 4) {
+                // Coarse levels have too few 16x8 tiles to fill 256 CUs and a long K loop (Cin up to 372): slice K over
+                // blockIdx.y, write raw partial sums, and let a small kernel add them up (+ bias, + BN statistics).
+                // Scratch bound: slices * N * plane <= (768 / tiles + 1) * 128 * tiles <= 98304 + 65536 floats per channel.
+                int want = static_cast<int>(((t16x8 < 256 ? 512 : 768) + t16x8 - 1) / t16x8);
+                if (want > nchunks) want = nchunks;
+                const int per = (nchunks + want - 1) / want;
+                d.form = DenseFwd::SplitK;
+                d.ksplit = (nchunks + per - 1) / per;
+            } else {
+                // Tile shape by block count (tools/conv_bench, Cin = 228 at 128x160): the launch wants >= ~1000 blocks.
+                //   16 samples: 32x16 (640 blocks) 257 us, 32x8 (1280) 216 us;   8 samples: 16x16 (640) 143 us, 16x8 (1280) 125 us
+                // level 0 stays on 32x16: in the training step (A/B of two library builds inside one job) it is 5 % faster than 32x8,
+                // although the isolated microbenchmark prefers 32x8 by 5 %
+                d.form = (t32x16 < 1024 && t32x8 >= 1024) ? DenseFwd::Direct32x8
+                       : (t32x16 < 1024 && t16x8 >= 768) ? DenseFwd::Direct16x8 : DenseFwd::DirectAuto;
+            }
+        }
+    }
+    pl.fuse_final = opt[ENDO_OPT_FINAL_VIRTUAL] && pl.dense[kDense - 1].form == DenseFwd::Wino4;
+    for (int l = 0; l < kLevels; ++l) {
+        // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, all output channels per tile (td_fwd_kernels.h)
+        pl.td_persistent[l] = (opt[ENDO_OPT_TD_PERSIST] & 2) && !pl.bf16 && c.training && td_fwd_ok(td_fwd_params(c, l));
+        const ConvP& tu = table().tu_conv[kLevels - 1 - l];
+        pl.tu_subpix[l] = c.net->lv[l + 1].w % 4 == 0 && tu.cout == kNew && tu.cin % 4 == 0;
+    }
+    return pl;
+}
+
+static int dense_fwd(const Ctx& c, int b, int j) {
+    const DenseBlock k = dense_block(b);
+    const FwdPlan::Dense& d = c.fwd->dense[b * kLayers + j];
+    const ConvP& cv = k.cv[j];
+    const auto& lv = c.net->lv[k.level];
+    const int oc0 = k.ic0 + k.c0 + kGrowth * j;
+    ConvParams p = dense_fwd_params(c, k, j, d.form);
+    ProfScope prof(kProfConv3x3Dense, c.stream, conv_flops(c.net, k.level, cv.cin, cv.cout, 3),
+                   4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
+    // the launches that run on K-chunks of 16 channels take the chunk-ordered copy of the weights the pass prepared for this layer
+    const float* chunk_weights = d.chunk_weights ? c.tape + c.net->wino_off + cv.u : nullptr;
+    const bool bf16 = c.fwd->bf16;          // (the same tile shapes)
+    switch (d.form) {
+        case DenseFwd::Wino4:
+            if (c.fwd->fuse_final && b == kBlocks - 1 && j == kLayers - 1) { p.fin_w = c.params + table().final_.w + k.ic0; p.fin_out = c.tape + c.net->pre_off; }
+            return launch_wino4_fwd(p, c.stream);
+        case DenseFwd::Wino2_32x16:
+            return d.stages == 4 ? launch_wino_fwd<2, 4, 2, 4>(p, c.stream) : d.stages == 3 ? launch_wino_fwd<2, 4, 2, 3>(p, c.stream) : launch_wino_fwd<2, 4, 2, 2>(p, c.stream);
+        case DenseFwd::Wino2_32x8:
+            return d.stages == 4 ? launch_wino_fwd<1, 4, 3, 4>(p, c.stream) : d.stages == 3 ? launch_wino_fwd<1, 4, 3, 3>(p, c.stream) : launch_wino_fwd<1, 4, 3, 2>(p, c.stream);
+        case DenseFwd::SplitK: {
+            float* partial = c.tape + c.net->partial_off;
+            p.ksplit = d.ksplit;
+            p.split_stride = static_cast<int64_t>(c.net->n) * cv.cout * lv.plane;      // inside one group's tape
+            p.out = partial; p.out_ns = static_cast<int64_t>(cv.cout) * lv.plane;
+            p.bias = nullptr; p.out_sums = nullptr;
+            p.wgt_chunks = chunk_weights;
+            int rc = bf16 ? launch_conv_dma<3, 16, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream)
+                          : launch_conv_dma<3, 16, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1>(p, c.stream);
+            if (rc) return rc;
+            int bx = static_cast<int>((lv.plane + 255) / 256);
+            bx = bx > 8 ? 8 : bx;
+            finalize_partial_kernel<<<dim3(bx, cv.cout, c.nt()), 256, 0, c.stream>>>(
+                partial, p.split_stride, d.ksplit, p.out_ns, static_cast<int>(lv.plane), c.params + cv.b, c.act(k.level) + oc0 * lv.plane,
+                lv.t * lv.plane, c.out_sums(k.level, oc0), c.net->n, c.net->gs);
+            ENDO_LAUNCH_CHECK();
+            return 0;
+        }
+        case DenseFwd::Direct32x8:
+            return bf16 ? launch_conv_dma<3, 4, 1, IN_BNRELU, EPI_FWD, 2, 4, 2, 1, 1>(p, c.stream) : launch_conv_dma<3, 4, 1, IN_BNRELU, EPI_FWD, 2, 4, 2, 1>(p, c.stream);
+        case DenseFwd::Direct16x8:
+            return bf16 ? launch_conv_dma<3, 8, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream) : launch_conv_dma<3, 8, 1, IN_BNRELU, EPI_FWD, 1, 2, 2, 1>(p, c.stream);
+        case DenseFwd::DirectAuto:
+            if (bf16) return launch_conv_dma_auto<3, 4, 1, IN_BNRELU, EPI_FWD, 8, 2, 1, 1>(p, c.stream);
+            p.wgt_chunks = chunk_weights;          // (only the KC = 16 instantiation the auto choice ends in for few tiles reads it)
+            return launch_conv_dma_auto<3, 4, 1, IN_BNRELU, EPI_FWD, 8, 2, 1>(p, c.stream);
+    }
+    return ENDO_E_BADARG;
+}
+
+static int td_fwd(const Ctx& c, int level) {
+    const ConvP& cv = table().td_conv[level];
+    const ConvParams p = td_fwd_params(c, level);
     ProfScope prof(kProfConv1x1Pool, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1),
                    4.0 * c.nt() * c.net->lv[level].plane * (cv.cin + cv.cout / 4.0));
-    // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, all output channels per tile (td_fwd_kernels.h)
-    if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 2) && !mfma_bf16_fwd(c) && c.training && td_fwd_ok(p)) return launch_td_fwd(p, device_cu_count(), c.stream);
-    if (mfma_bf16_fwd(c)) return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4, 2, 1, 1>(p, c.stream);
+    if (c.fwd->td_persistent[level]) return launch_td_fwd(p, device_cu_count(), c.stream);
+    if (c.fwd->bf16) return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4, 2, 1, 1>(p, c.stream);
     return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4>(p, c.stream);    // 32x8 tiles: -6 % in the in-job A/B (Q = 6 was 10 % slower; round 5: K-chunks of 16 channels +-0, of 32 +40 % on the family, Q = 6 with 16 +14 %)
 }
 
 // transition up: nearest x2 -> conv3x3 48->48 into channels [0,48) of the finer level (models.py:70-80)
 static int tu_fwd(const Ctx& c, int level, int src_level, int src_c0, const ConvP& cv) {
-    const auto& sv = c.net->lv[src_level];
     ProfScope prof(kProfConv3x3Up, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3),
                    4.0 * c.nt() * c.net->lv[level].plane * (cv.cin / 4.0 + cv.cout));
-    if (sv.w % 4 == 0 && cv.cout == kNew && cv.cin % 4 == 0) {
+    if (c.fwd->tu_subpix[level]) {
         // sub-pixel form: the two row phases on the low-resolution grid, 4/9 of the MACs.  The tap-summed weights
         // go to the (idle) split-K scratch of group 0's tape; they are shared by all groups.
         float* w3 = c.tape + c.net->partial_off;
         tu_phase_weights_kernel<<<(2 * cv.cin * 384 + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, w3);
         ENDO_LAUNCH_CHECK();
-        {   // ONE launch for both row phases (gridDim.y = 2, conv_dma_kernel<.., PH = 2>)
-            ConvParams p{};
-            fill_grid(c, p, src_level);                     // the launch runs over the low-resolution pixels
-            fill_in(c, p, c.act(src_level), src_level, src_c0, cv.cin);
-            p.wgt = w3; p.w_cout = 2 * cv.cout; p.w_cin = cv.cin;
-            p.bias = c.params + cv.b;
-            fill_out(c, p, c.act(level), level, 0, cv.cout);
-            p.out_sums = c.out_sums(level, 0);
-            return launch_conv_dma_vec<3, 4, 6, IN_PLAIN, EPI_FWD, 2, 4, 2, 1, 4, 0, 0, 2>(p, c.stream);
-        }
+        // ONE launch for both row phases (gridDim.y = 2, conv_dma_kernel<.., PH = 2>)
+        ConvParams p{};
+        fill_grid(c, p, src_level);                     // the launch runs over the low-resolution pixels
+        fill_in(c, p, c.act(src_level), src_level, src_c0, cv.cin);
+        p.wgt = w3; p.w_cout = 2 * cv.cout; p.w_cin = cv.cin;
+        p.bias = c.params + cv.b;
+        fill_out(c, p, c.act(level), level, 0, cv.cout);
+        p.out_sums = c.out_sums(level, 0);
+        return launch_conv_dma_vec<3, 4, 6, IN_PLAIN, EPI_FWD, 2, 4, 2, 1, 4, 0, 0, 2>(p, c.stream);
     }
     ConvParams p{};
     fill_grid(c, p, level);
@@ -876,9 +931,9 @@ static int tu_fwd(const Ctx& c, int level, int src_level, int src_c0, const Conv
 }
 
 // The final convolution's data gradient as the "virtual" content of the level-0 gradient buffer (DgradBlockParams::vg): vg = the plane
-// g = grad_out * sign(pre) in the gradient workspace, vw = the 192 final-conv weights; base: the base-channel pass forms it too
-// (otherwise final_bwd_data_kernel has materialised the block's base channels)
-struct FinalVirt { const float* vg; const float* vw; bool base; bool base_w; float* gw; };          // base_w: the base pass also forms the final convolution's weight gradient of its channels (gw: that tensor's gradient)
+// g = grad_out * sign(pre) in the gradient workspace, vw = the 192 final-conv weights, gw = that tensor's gradient.  Which passes of the last up
+// block form it is in the plan (BwdPlan::use_virt, virt_base, virt_base_w); what is left has been materialised by final_bwd_data_kernel.
+struct FinalVirt { const float* vg; const float* vw; float* gw; };
 
 static int prep_dy(const Ctx& c, int level, int c0, int count, float* bias_grad, const BnFin4* fin = nullptr, int nl = 0, const FinalVirt* fv = nullptr) {
     const auto& lv = c.net->lv[level];
@@ -927,29 +982,243 @@ static void fill_wgrad_grid(const Ctx& c, WgradParams& p, int level) {
     p.tiles_y = (lv.h + kWgTileY - 1) / kWgTileY;
 }
 
-// batch / slice: the F(3x3, 4x4) form leaves its partial sums in scratch slice `slice` and its reduction to the caller's batched launch
-static int dense_wgrad(const Ctx& c, int level, int ic0, int oc0, const BnP& b, const ConvP& cv, F34ReduceBatch* batch = nullptr, int slice = 0) {
+// ---- parameter fillers of the backward launches whose form the plan decides (plan_bwd asks the kernels' _ok predicates on what they return) ----
+static WgradParams dense_wgrad_params(const Ctx& c, const DenseBlock& k, int j) {
+    const auto& lv = c.net->lv[k.level];
+    const BnP& b = k.bn[j];
+    const ConvP& cv = k.cv[j];
+    const int oc0 = k.ic0 + k.c0 + kGrowth * j;
+    WgradParams p{};
+    fill_wgrad_grid(c, p, k.level);
+    p.in = c.act(k.level) + k.ic0 * lv.plane; p.in_ns = lv.t * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = cv.cin;
+    p.saved = c.saved(b); p.gamma = c.params + b.g; p.beta = c.params + b.b;
+    p.dy = c.gbuf(k.level) + oc0 * lv.plane; p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = cv.cout;
+    p.dw = c.grads + cv.w;
+    return p;
+}
+
+static void fill_dgrad_block(const Ctx& c, DgradBlockParams& p, int level) {
     const auto& lv = c.net->lv[level];
+    p.n = c.nt(); p.h = lv.h; p.w = lv.w;
+    p.group_n = c.net->n; p.gs = c.net->gs; p.slot_stride = c.net->slot_stride;
+    p.g_ns = lv.t * lv.plane; p.g_cs = static_cast<int>(lv.plane); p.g_w = lv.w;
+    p.ns = lv.t * lv.plane; p.cs = static_cast<int>(lv.plane);
+}
+
+// Gradient into the 12 new maps of layer j-1 of a dense block from ALL its consumers inside the block (layers j..3) in one pass.
+// a: the same BN layers for the prep_dy that folds their finalize.  (vg / vw are the launch's to set: no predicate reads them.)
+static DgradBlockParams newmap_params(const Ctx& c, const DenseBlock& k, int j, BnFin4* a = nullptr) {
+    const auto& lv = c.net->lv[k.level];
+    const int nl = kLayers - j;
+    const int t0 = k.c0 + kGrowth * (j - 1);          // index of the target channels inside the consumers' inputs
+    DgradBlockParams p{};
+    fill_dgrad_block(c, p, k.level);
+    p.g = c.gbuf(k.level) + (k.ic0 + k.c0 + kGrowth * j) * lv.plane;
+    p.x = c.act(k.level) + (k.ic0 + t0) * lv.plane;
+    p.out = c.gbuf(k.level) + (k.ic0 + t0) * lv.plane;
+    p.count = kGrowth;
+    p.acc_from = 0;          // a later consumer (next block / transition) wrote these maps first -- or nobody, where the final convolution's gradient is formed here
+    p.w_ci_off = t0;
+    for (int l = 0; l < nl; ++l) {
+        const BnP& b = k.bn[j + l];
+        p.wgt[l] = c.params + k.cv[j + l].w; p.w_cin[l] = k.cv[j + l].cin;
+        p.saved[l] = c.saved(b) + 2 * t0; p.gamma[l] = c.params + b.g + t0; p.beta[l] = c.params + b.b + t0;
+        p.scratch[l] = c.scratch(b) + 2 * t0;
+        if (a) { a->scratch[l] = p.scratch[l]; a->saved[l] = p.saved[l]; a->gamma[l] = p.gamma[l]; a->ggamma[l] = c.grads + b.g + t0; a->gbeta[l] = c.grads + b.b + t0; }
+    }
+    return p;
+}
+
+// base channels of a dense block, all four layers in one pass
+static DgradBlockParams base_pass_params(const Ctx& c, const DenseBlock& k) {
+    const auto& lv = c.net->lv[k.level];
+    DgradBlockParams p{};
+    fill_dgrad_block(c, p, k.level);
+    p.g = c.gbuf(k.level) + (k.ic0 + k.c0) * lv.plane;
+    p.x = c.act(k.level) + k.ic0 * lv.plane;
+    p.out = c.gbuf(k.level) + k.ic0 * lv.plane;
+    p.count = k.c0;
+    p.acc_from = k.base_overwrite ? k.c0 : 0;
+    p.w_ci_off = 0;
+    for (int j = 0; j < kLayers; ++j) {
+        p.wgt[j] = c.params + k.cv[j].w; p.w_cin[j] = k.cv[j].cin;
+        p.saved[j] = c.saved(k.bn[j]); p.gamma[j] = c.params + k.bn[j].g; p.beta[j] = c.params + k.bn[j].b;
+        p.scratch[j] = c.scratch(k.bn[j]);
+    }
+    return p;
+}
+
+static WgradParams td_wgrad_params(const Ctx& c, int level) {
+    const BnP& b = table().td_bn[level];
+    const ConvP& cv = table().td_conv[level];
+    const int next = level + 1, oc0 = next < kLevels ? 48 : 0;
+    const auto& lv = c.net->lv[level];
+    const auto& nx = c.net->lv[next];
     WgradParams p{};
     fill_wgrad_grid(c, p, level);
-    p.in = c.act(level) + ic0 * lv.plane; p.in_ns = lv.t * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = cv.cin;
+    p.in = c.act(level) + 48 * lv.plane; p.in_ns = lv.t * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = cv.cin;
     p.saved = c.saved(b); p.gamma = c.params + b.g; p.beta = c.params + b.b;
-    p.dy = c.gbuf(level) + oc0 * lv.plane; p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = cv.cout;
+    p.dy = c.gbuf(next) + oc0 * nx.plane; p.dy_ns = nx.t * nx.plane; p.dy_cs = static_cast<int>(nx.plane); p.dy_w = nx.w; p.cout = cv.cout;
+    p.dy_idx = c.idx(level); p.idx_ns = static_cast<int64_t>(cv.cout) * nx.plane;
     p.dw = c.grads + cv.w;
-    ProfScope prof(kProfWgradDense, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
-    if (c.net->opt[ENDO_OPT_WGRAD_F34] && wgrad_mfma_mode(c) == 0 && wgrad_f34_ok(p, c.net->opt[ENDO_OPT_WINO_MIN_TILES] / 4l))          // from 256 tiles of 4 x 4 pixels: levels 0-4 of configs[1] (level 5 is 8 x 10)
-        return launch_wgrad_f34(p, c.gradws + c.net->wg_scratch_off + (batch ? slice : 0) * kF34ScratchFloats, c.stream,
-                                c.net->opt[ENDO_OPT_WGRAD_F34] == 2 ? 256 : kF34Blocks, batch);          // Winograd F(3x3, 4x4)
-    if (wgrad_nsplit_ok(p)) {
-        if (wgrad_mfma_mode(c) == 2) return launch_wgrad_x3(p, c.gradws + c.net->wg_scratch_off, c.stream);          // fp32 products as bf16 splits (wgrad_x3_kernels.h)
-        return launch_wgrad_nsplit(p, c.gradws + c.net->wg_scratch_off, c.stream, wgrad_mfma_mode(c));
+    return p;
+}
+
+static ConvParams td_dgrad_params(const Ctx& c, int level) {
+    const BnP& b = table().td_bn[level];
+    const ConvP& cv = table().td_conv[level];
+    const int next = level + 1, oc0 = next < kLevels ? 48 : 0;
+    const auto& lv = c.net->lv[level];
+    ConvParams p{};
+    fill_grid(c, p, level);
+    fill_in(c, p, c.gbuf(next), next, oc0, cv.cout);
+    p.in_idx = c.idx(level); p.idx_ns = static_cast<int64_t>(cv.cout) * c.net->lv[next].plane;   // channel index relative to p.in
+    p.wgt = c.params + cv.w; p.w_cout = cv.cout; p.w_cin = cv.cin;
+    fill_out(c, p, c.gbuf(level), level, 48, cv.cin);
+    p.x = c.act(level) + 48 * lv.plane; p.x_ns = lv.t * lv.plane; p.x_cs = static_cast<int>(lv.plane);
+    p.bn_saved = c.saved(b); p.bn_gamma = c.params + b.g; p.bn_beta = c.params + b.b;
+    p.bn_scratch = c.scratch(b); p.bn_slot_stride = c.net->slot_stride;
+    p.acc_from = 0;
+    return p;
+}
+
+// weight gradient of the transition up that wrote channels [0, 48) of `level`; subpix: as the sub-pixel form takes it (it walks the low-resolution grid)
+static WgradParams tu_wgrad_params(const Ctx& c, int level, bool subpix) {
+    const ConvP& cv = table().tu_conv[kLevels - 1 - level];
+    const int src_level = level + 1, src_c0 = src_level == kLevels ? 288 : 96 + down_in(src_level);
+    const auto& lv = c.net->lv[level];
+    const auto& sv = c.net->lv[src_level];
+    WgradParams p{};
+    fill_wgrad_grid(c, p, level);
+    p.in = c.act(src_level) + src_c0 * sv.plane; p.in_ns = sv.t * sv.plane; p.in_cs = static_cast<int>(sv.plane); p.in_w = sv.w; p.cin = cv.cin;
+    p.dy = c.gbuf(level); p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = cv.cout;
+    p.dw = c.grads + cv.w;
+    if (subpix) { p.h = sv.h; p.w = sv.w; }
+    return p;
+}
+
+// first conv 3 -> 48: weight gradient (the image needs no data gradient)
+static WgradParams first_wgrad_params(const Ctx& c) {
+    const auto& lv = c.net->lv[0];
+    WgradParams p{};
+    fill_wgrad_grid(c, p, 0);
+    p.in = c.x; p.in_ns = 3 * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = 3;
+    p.in_gs = c.net->n * p.in_ns;                 // the caller's image tensor
+    p.dy = c.gbuf(0) + 48 * lv.plane; p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = kFirst;
+    p.dw = c.grads + table().first.w;
+    return p;
+}
+
+static BwdPlan plan_bwd(const Ctx& c) {
+    const int* opt = c.net->opt;
+    const int wino_dgrad = opt[ENDO_OPT_WINO_DGRAD];
+    const long min_tiles = opt[ENDO_OPT_WINO_MIN_TILES];
+    BwdPlan pl{};
+    pl.overlap = opt[ENDO_OPT_WGRAD_OVERLAP];
+    pl.bf16_wgrad = (bf16_mask(opt) & 1) != 0;
+    pl.bf16_dgrad = (bf16_mask(opt) & 4) != 0;
+    // operands of a dense-layer weight gradient: rounded to bf16, else fp32 as three-term bf16 splits (ENDO_OPT_MFMA_X3 bit 0), else fp32 MFMA -- and
+    // only the last has a Winograd-domain form
+    const bool x3 = !pl.bf16_wgrad && (opt[ENDO_OPT_MFMA_X3] & 1);
+    const bool f34 = opt[ENDO_OPT_WGRAD_F34] && !pl.bf16_wgrad && !x3;
+    const long f34_min_tiles = min_tiles / 4;          // from 256 tiles of 4 x 4 pixels: levels 0-4 of configs[1] (level 5 is 8 x 10)
+    pl.f34_blocks = opt[ENDO_OPT_WGRAD_F34] == 2 ? 256 : kF34Blocks;
+    // the data-gradient weights are transformed whenever a Winograd form is selected, whether or not a block takes one this pass (at small sizes none does)
+    pl.dgrad_weights = wino_dgrad != 0 && !pl.bf16_dgrad;
+    for (int b = 0; b < kBlocks; ++b) {
+        const DenseBlock k = dense_block(b);
+        const auto& lv = c.net->lv[k.level];
+        BwdPlan::Block& bl = pl.block[b];
+        //   fine levels : per layer (last to first) prep + wgrad + a dgrad restricted to the NEW channels the layer
+        //                 reads (they carry the layer-to-layer dependency); then ONE fused dgrad for the base channels
+        //                 of all four layers (dgrad_block_kernels.h) -- 3x less HBM traffic than four full dgrads
+        //   otherwise   : the per-layer path (few tiles: parallelism comes from splitting channels over blocks)
+        const DgradBlockParams base = base_pass_params(c, k);
+        bl.fused = dgrad_block_ok(base);
+        // base pass at the fine levels: Winograd F(2x2, 3x3), 48 instead of 108 MFMAs per 64 pixels and step (dgrad_wino_kernels.h) -- the phase-skewed
+        // kernel (ENDO_OPT_WINO_DGRAD 1 / 3, at most DgradWino3Geom::kMaxCount base channels), as persistent blocks where that form applies (3), else the round-2 kernel
+        const long wtiles = static_cast<long>(lv.w / 32) * (lv.h / 8) * c.nt();
+        if (pl.bf16_dgrad) bl.base = BasePass::Block8Bf16;
+        else if (wino_dgrad != 0 && dgrad_wino_ok(base) && wtiles >= min_tiles)
+            bl.base = !((wino_dgrad == 1 || wino_dgrad == 3) && dgrad_wino3_ok(base)) ? BasePass::Wino8
+                    : (wino_dgrad == 3 && dgrad_wino3p_applies(base)) ? BasePass::Wino3Persistent : BasePass::Wino3;
+        else bl.base = BasePass::Block8;          // 512-thread blocks: +15 % over the 4-wave kernel (tools/conv_bench)
+        bl.wino3_layout = bl.base == BasePass::Wino3 || bl.base == BasePass::Wino3Persistent;
+        for (int j = 1; j < kLayers; ++j) {
+            const DgradBlockParams p = newmap_params(c, k, j);
+            const bool vec = dgrad_block_vec_ok(p);          // 16-byte DMA of the gradient tiles
+            bl.newmap[j] = (pl.bf16_dgrad && vec) ? NewMap::Bf16 : (vec && opt[ENDO_OPT_DGRAD_VEC] >= 2 && dgrad_newmap_ok(p)) ? NewMap::Persistent
+                         : (vec && opt[ENDO_OPT_DGRAD_VEC] != 0) ? NewMap::Vec16 : NewMap::Dword;
+        }
+        for (int j = 0; j < kLayers; ++j) {
+            const WgradParams p = dense_wgrad_params(c, k, j);
+            pl.wgrad[b * kLayers + j] = (f34 && wgrad_f34_ok(p, f34_min_tiles)) ? DenseWgrad::F34 : wgrad_nsplit_ok(p) ? (x3 ? DenseWgrad::X3 : DenseWgrad::NSplit)
+                                      : wgrad_taps_ok(p) ? DenseWgrad::Taps : DenseWgrad::Direct;
+        }
     }
-    if (wgrad_taps_ok(p)) return mfma_bf16_wgrad(c) ? launch_wgrad_taps<12, IN_BNRELU, 1>(p, c.stream) : launch_wgrad_taps<12, IN_BNRELU>(p, c.stream);
-    return launch_wgrad<3, 1, IN_BNRELU, DY_PLAIN>(p, c.stream);
+    for (int l = 0; l < kLevels; ++l) {
+        const auto& sv = c.net->lv[l + 1];
+        pl.td_wgrad_dma[l] = wgrad1x1_dma_ok(td_wgrad_params(c, l));
+        // pooled rows of whole code dwords -> LDS-DMA kernel; otherwise the register-staged one
+        // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, 16-byte DMA (td_dgrad_kernels.h)
+        // pooled rows without whole code dwords (level 4 of configs[1]: 8 x 10): 128-pixel runs, the routed gradient expanded on its way into
+        // LDS -- 46 instead of the register-staged kernel's 100 us.  (At levels 2 / 3 the LDS-DMA kernel stays: 103 / 63 against 139 / 69 us, tools/td_bench)
+        const ConvParams td = td_dgrad_params(c, l);
+        const bool persist = (opt[ENDO_OPT_TD_PERSIST] & 1) && !pl.bf16_dgrad;
+        pl.td_dgrad[l] = (persist && td_dgrad_ok(td)) ? TdDgrad::Persistent : (persist && sv.w % 4 != 0 && td_dgrad_small_ok(td)) ? TdDgrad::Runs128
+                       : sv.w % 4 == 0 ? TdDgrad::Dma : TdDgrad::Staged;
+        const ConvP& tu = table().tu_conv[kLevels - 1 - l];
+        pl.tu_wgrad[l] = tu_wgrad_subpix_ok(tu_wgrad_params(c, l, true)) ? TuWgrad::Subpix : wgrad_taps_ok(tu_wgrad_params(c, l, false), true) ? TuWgrad::Taps : TuWgrad::Direct;
+        // Sub-pixel data gradient, tile shape by block count (round 6): on 32 x 8 tiles the launch of level 4 is 32 blocks and that of level 3 128 -- each walking all 24 K-chunks,
+        // 93 and 103 us for 0.1 and 0.4 GFLOP.  16 x 8 / 16 x 4 tiles where 32 x 8 ones leave the chip under-filled.
+        pl.tu_dgrad[l] = !(sv.w % 4 == 0 && tu.cin == kNew && tu.cout == kNew) ? TuDgrad::Plain : tile_count(c, l + 1, 32, 8) >= 1024 ? TuDgrad::Subpix32x8
+                       : tile_count(c, l + 1, 16, 8) >= 512 ? TuDgrad::Subpix16x8 : TuDgrad::Subpix16x4;
+    }
+    // The final convolution's data gradient is rank one: dX[c] = g * w[c], g = grad_out * sign(pre).  Writing it out (192 planes, 1 GB
+    // at 16 x 256 x 320) only for the last up block to read it back costs two passes over the level-0 buffer; instead g goes to one
+    // plane and that block's kernels form the products where they first touch a channel (FinalVirt) -- where the block takes the
+    // fused path, and for its base channels where the phase-skewed Winograd kernel runs; what is left is materialised as before.
+    // ... and where that kernel runs as persistent blocks it also forms sum g * x[c] of the base channels it streams: the final
+    // convolution's weight gradient of those channels (round 6: final_bwd_weight_kernel then reads 48 + 1 instead of 192 + 1 planes)
+    const BwdPlan::Block& last = pl.block[kBlocks - 1];
+    const int last_base = dense_block(kBlocks - 1).c0;
+    pl.use_virt = opt[ENDO_OPT_FINAL_VIRTUAL] && last.fused;
+    pl.virt_base = pl.use_virt && last.wino3_layout;
+    pl.virt_base_w = pl.use_virt && last.base == BasePass::Wino3Persistent;
+    pl.materialise = !pl.use_virt ? 192 : (pl.virt_base ? 0 : last_base);
+    pl.c_first = pl.virt_base_w ? last_base : 0;
+    // First convolution: the F(3x3, 4x4) form can prepare the gradient itself (G = d + P x + Q, bias gradient = sum G: WgradParams::prep_x): this is the LAST kernel
+    // of the backward pass, nothing else is on the chip, and prep_dy's own pass over 3 x 48 planes would be 0.1 ms of the step
+    const WgradParams first = first_wgrad_params(c);
+    pl.first = (f34 && wgrad_f34_raw_ok(first, f34_min_tiles)) ? (opt[ENDO_OPT_FINAL_VIRTUAL] ? FirstWgrad::F34Prep : FirstWgrad::F34)
+             : wgrad_taps_ok(first) ? FirstWgrad::Taps : FirstWgrad::Direct;
+    return pl;
+}
+
+// batch / slice: the F(3x3, 4x4) form leaves its partial sums in scratch slice `slice` and its reduction to the caller's batched launch
+static int dense_wgrad(const Ctx& c, int b, int j, F34ReduceBatch* batch = nullptr, int slice = 0) {
+    const DenseBlock k = dense_block(b);
+    const ConvP& cv = k.cv[j];
+    const auto& lv = c.net->lv[k.level];
+    const WgradParams p = dense_wgrad_params(c, k, j);
+    float* scratch = c.gradws + c.net->wg_scratch_off;
+    ProfScope prof(kProfWgradDense, c.stream, conv_flops(c.net, k.level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
+    switch (c.bwd->wgrad[b * kLayers + j]) {
+        case DenseWgrad::F34: return launch_wgrad_f34(p, scratch + (batch ? slice : 0) * kF34ScratchFloats, c.stream, c.bwd->f34_blocks, batch);          // Winograd F(3x3, 4x4)
+        case DenseWgrad::X3: return launch_wgrad_x3(p, scratch, c.stream);          // fp32 products as bf16 splits (wgrad_x3_kernels.h)
+        case DenseWgrad::NSplit: return launch_wgrad_nsplit(p, scratch, c.stream, c.bwd->bf16_wgrad ? 1 : 0);
+        case DenseWgrad::Taps: return c.bwd->bf16_wgrad ? launch_wgrad_taps<12, IN_BNRELU, 1>(p, c.stream) : launch_wgrad_taps<12, IN_BNRELU>(p, c.stream);
+        case DenseWgrad::Direct: return launch_wgrad<3, 1, IN_BNRELU, DY_PLAIN>(p, c.stream);
+    }
+    return ENDO_E_BADARG;
 }
 
 // dense layer backward: bias grad + deferred-term fold, wgrad, dgrad fused with ReLU/BN backward
-static int dense_bwd(const Ctx& c, int level, int ic0, int oc0, const BnP& b, const ConvP& cv, int acc_from) {
+static int dense_bwd(const Ctx& c, int b, int j, int acc_from) {
+    const DenseBlock k = dense_block(b);
+    const BnP& bn = k.bn[j];
+    const ConvP& cv = k.cv[j];
+    const int level = k.level, ic0 = k.ic0, oc0 = k.ic0 + k.c0 + kGrowth * j;
     const auto& lv = c.net->lv[level];
     int rc = prep_dy(c, level, oc0, cv.cout, c.grads + cv.b);
     if (rc) return rc;
@@ -957,7 +1226,7 @@ static int dense_bwd(const Ctx& c, int level, int ic0, int oc0, const BnP& b, co
         Ctx cw;
         rc = c.fork_wgrad(cw, level);
         if (rc) return rc;
-        rc = dense_wgrad(cw, level, ic0, oc0, b, cv);
+        rc = dense_wgrad(cw, b, j);
         if (rc) return rc;
     }
     {
@@ -967,57 +1236,44 @@ static int dense_bwd(const Ctx& c, int level, int ic0, int oc0, const BnP& b, co
         p.wgt = c.params + cv.w; p.w_cout = cv.cout; p.w_cin = cv.cin;
         fill_out(c, p, c.gbuf(level), level, ic0, cv.cin);
         p.x = c.act(level) + ic0 * lv.plane; p.x_ns = lv.t * lv.plane; p.x_cs = static_cast<int>(lv.plane);
-        p.bn_saved = c.saved(b); p.bn_gamma = c.params + b.g; p.bn_beta = c.params + b.b;
-        p.bn_scratch = c.scratch(b); p.bn_slot_stride = c.net->slot_stride;
+        p.bn_saved = c.saved(bn); p.bn_gamma = c.params + bn.g; p.bn_beta = c.params + bn.b;
+        p.bn_scratch = c.scratch(bn); p.bn_slot_stride = c.net->slot_stride;
         p.acc_from = acc_from - ic0;
         ProfScope prof(kProfDgradDense, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (3.0 * cv.cin + cv.cout));
         rc = launch_dgrad_dense_auto(p, c.stream);
         if (rc) return rc;
     }
-    return bn_finalize(c, b, level, ic0);
+    return bn_finalize(c, bn, level, ic0);
 }
 
-// Backward of a whole dense block (4 layers) whose input ("base") is level-buffer channels [ic0, ic0 + c0)
-// and whose 4 x 12 new maps follow at [ic0 + c0, ic0 + c0 + 48).  base_overwrite: the base channels have
-// no gradient yet (first writer) instead of accumulating.
-//   fine levels : per layer (last to first) prep + wgrad + a dgrad restricted to the NEW channels the layer
-//                 reads (they carry the layer-to-layer dependency); then ONE fused dgrad for the base channels
-//                 of all four layers (dgrad_block_kernels.h) -- 3x less HBM traffic than four full dgrads
-//   coarse levels: the per-layer path (few tiles: parallelism comes from splitting channels over blocks)
-// Which base-channel kernel the fused path takes (0 = dgrad_block8, 1 = phase-skewed Winograd, 2 = round-2 Winograd)
-static int base_pass_form(const Ctx& c, int level, const DgradBlockParams& p, const ConvP* cv) {
-    const auto& lv = c.net->lv[level];
-    const long wtiles = static_cast<long>(lv.w / 32) * (lv.h / 8) * c.nt();
-    if (mfma_bf16_dgrad(c)) return 0;
-    if (wino_dgrad_enabled(c) && dgrad_wino_ok(p) && wtiles >= c.net->opt[ENDO_OPT_WINO_MIN_TILES] && cv[0].ud >= 0)
-        return ((wino_dgrad_mode(c) == 1 || wino_dgrad_mode(c) == 3) && dgrad_wino3_ok(p)) ? 1 : 2;
-    return 0;
+template <int NL>
+static int launch_newmap(NewMap form, const DgradBlockParams& p, hipStream_t stream) {
+    switch (form) {
+        case NewMap::Bf16: return launch_dgrad_block<NL, 2, 3, 1, 0, 1, 4, 1>(p, stream);
+        case NewMap::Persistent: return launch_dgrad_newmap<NL>(p, stream);          // dgrad_newmap_kernels.h
+        case NewMap::Vec16: return launch_dgrad_block<NL, 2, 3, 1, 0, 1, 4>(p, stream);
+        case NewMap::Dword: return launch_dgrad_block<NL, 2, 3>(p, stream);
+    }
+    return ENDO_E_BADARG;
 }
 
+// Backward of a whole dense block (4 layers), fused path or per-layer path as planned (BwdPlan::Block); DenseBlock::base_overwrite: the base
+// channels have no gradient yet (first writer) instead of accumulating.
 // fv: the block's gradient-buffer range starts out as the final convolution's rank-one data gradient (the last up block, level 0), which
 // is never written: the first touch of every channel forms it (FinalVirt)
-static int dense_block_bwd(const Ctx& c, int level, int ic0, int c0, const BnP* bn, const ConvP* cv, bool base_overwrite, const FinalVirt* fv = nullptr) {
+static int dense_block_bwd(const Ctx& c, int b, const FinalVirt* fv = nullptr) {
+    const DenseBlock k = dense_block(b);
+    const BwdPlan::Block& bl = c.bwd->block[b];
+    const int level = k.level, ic0 = k.ic0, c0 = k.c0, new0 = ic0 + c0;
     const auto& lv = c.net->lv[level];
-    const int new0 = ic0 + c0;
-    DgradBlockParams probe{};
-    probe.w = lv.w; probe.cs = static_cast<int>(lv.plane); probe.ns = lv.t * lv.plane;
-    probe.x = c.act(level) + ic0 * lv.plane; probe.out = c.gbuf(level) + ic0 * lv.plane;
-    const long tiles = static_cast<long>((lv.w + 31) / 32) * ((lv.h + 5) / 6) * c.nt();
-    (void)tiles;          // few tiles: the fused kernel slices the channel groups over blockIdx.y
-    if (!dgrad_block_ok(probe)) {
+    if (!bl.fused) {
         for (int j = kLayers - 1; j >= 0; --j) {
-            const int acc_from = (j == kLayers - 1 && base_overwrite) ? new0 : 0;
-            int rc = dense_bwd(c, level, ic0, new0 + kGrowth * j, bn[j], cv[j], acc_from < ic0 ? ic0 : acc_from);
+            const int acc_from = (j == kLayers - 1 && k.base_overwrite) ? new0 : 0;
+            int rc = dense_bwd(c, b, j, acc_from < ic0 ? ic0 : acc_from);
             if (rc) return rc;
         }
         return 0;
     }
-    auto fill_common = [&](DgradBlockParams& p) {
-        p.n = c.nt(); p.h = lv.h; p.w = lv.w;
-        p.group_n = c.net->n; p.gs = c.net->gs; p.slot_stride = c.net->slot_stride;
-        p.g_ns = lv.t * lv.plane; p.g_cs = static_cast<int>(lv.plane); p.g_w = lv.w;
-        p.ns = lv.t * lv.plane; p.cs = static_cast<int>(lv.plane);
-    };
     BnFin4 pending{};          // BN layers whose sums over the next prepared maps the last new-channel pass produced (folded into prep_dy)
     int pending_nl = 0;
     F34ReduceBatch red{};      // the block's F(3x3, 4x4) weight gradients reduce their partial sums in ONE launch behind the last of them
@@ -1026,17 +1282,17 @@ static int dense_block_bwd(const Ctx& c, int level, int ic0, int c0, const BnP* 
         // written, from the virtual content, by the new-channel passes below)
         // (round 5, in-job A/B: a separate one-block finalize launch in front of a prologue-free prep_dy makes this kernel family 0.15 ms per step
         // faster and the step none: 18.15 against 18.15 ms -- the 33 extra launches cost what the prologues did)
-        int rc = prep_dy(c, level, new0 + kGrowth * j, kGrowth, c.grads + cv[j].b, &pending, pending_nl, (fv && j == kLayers - 1) ? fv : nullptr);
+        int rc = prep_dy(c, level, new0 + kGrowth * j, kGrowth, c.grads + k.cv[j].b, &pending, pending_nl, (fv && j == kLayers - 1) ? fv : nullptr);
         if (rc) return rc;
         // ENDO_OPT_WGRAD_OVERLAP 1: fork after every prep_dy; 2: ONE fork per dense block, after its last prep_dy (nothing rewrites a
         // prepared G before the join, so the four weight gradients may start late; 55 -> 22 event record / wait pairs per backward pass)
-        const bool defer = c.net->opt[ENDO_OPT_WGRAD_OVERLAP] == 2;
+        const bool defer = c.bwd->overlap == 2;
         if (!defer || j == 0) {
             Ctx cw;
             rc = c.fork_wgrad(cw, level);
             if (rc) return rc;
             for (int jj = defer ? kLayers - 1 : j; jj >= j; --jj) {
-                rc = dense_wgrad(cw, level, ic0, new0 + kGrowth * jj, bn[jj], cv[jj], &red, jj);
+                rc = dense_wgrad(cw, b, jj, &red, jj);
                 if (rc) return rc;
             }
             if (j == 0 && red.count > 0) {          // (the side stream runs its launches in order: all four are ahead of this one)
@@ -1046,101 +1302,54 @@ static int dense_block_bwd(const Ctx& c, int level, int ic0, int c0, const BnP* 
             }
         }
         if (j > 0) {
-            // Gradient into the 12 new maps of layer j-1 from ALL its consumers inside the block (layers j..3) in one pass:
-            // the layer-to-layer dependency only needs G_j..G_3 final, and this way every new map is read (x) and
+            // The layer-to-layer dependency only needs G_j..G_3 final, and this way every new map is read (x) and
             // read-modify-written (gradient) once instead of once per consumer -- 180 instead of 252 plane passes per block.
             const int nl = kLayers - j;
-            const int t0 = c0 + kGrowth * (j - 1);          // index of the target channels inside the consumers' inputs
-            DgradBlockParams p{};
-            fill_common(p);
-            p.g = c.gbuf(level) + (new0 + kGrowth * j) * lv.plane;
-            p.x = c.act(level) + (ic0 + t0) * lv.plane;
-            p.out = c.gbuf(level) + (ic0 + t0) * lv.plane;
-            p.count = kGrowth;
-            p.acc_from = 0;          // a later consumer (next block / transition) wrote these maps first
-            if (fv) { p.vg = fv->vg; p.vw = fv->vw + ic0 + t0; }          // ... or nobody: the final convolution's gradient is formed here
-            p.w_ci_off = t0;
             BnFin4 a{};
-            for (int l = 0; l < nl; ++l) {
-                const BnP& b = bn[j + l];
-                p.wgt[l] = c.params + cv[j + l].w; p.w_cin[l] = cv[j + l].cin;
-                p.saved[l] = c.saved(b) + 2 * t0; p.gamma[l] = c.params + b.g + t0; p.beta[l] = c.params + b.b + t0;
-                p.scratch[l] = c.scratch(b) + 2 * t0;
-                a.scratch[l] = p.scratch[l]; a.saved[l] = p.saved[l]; a.gamma[l] = p.gamma[l];
-                a.ggamma[l] = c.grads + b.g + t0; a.gbeta[l] = c.grads + b.b + t0;
-            }
-            {
-                ProfScope prof(kProfDgradDense, c.stream, 2.0 * c.nt() * lv.plane * kGrowth * kGrowth * 9 * nl,
-                               4.0 * c.nt() * lv.plane * (3.0 * kGrowth + kGrowth * nl));
-                if (mfma_bf16_dgrad(c) && dgrad_block_vec_ok(p))
-                    rc = nl == 1 ? launch_dgrad_block<1, 2, 3, 1, 0, 1, 4, 1>(p, c.stream)
-                       : nl == 2 ? launch_dgrad_block<2, 2, 3, 1, 0, 1, 4, 1>(p, c.stream) : launch_dgrad_block<3, 2, 3, 1, 0, 1, 4, 1>(p, c.stream);
-                else if (dgrad_block_vec_ok(p) && c.net->opt[ENDO_OPT_DGRAD_VEC] >= 2 && dgrad_newmap_ok(p))
-                    rc = nl == 1 ? launch_dgrad_newmap<1>(p, c.stream) : nl == 2 ? launch_dgrad_newmap<2>(p, c.stream) : launch_dgrad_newmap<3>(p, c.stream);
-                else if (dgrad_block_vec_ok(p) && dgrad_vec_enabled(c))
-                    rc = nl == 1 ? launch_dgrad_block<1, 2, 3, 1, 0, 1, 4>(p, c.stream)
-                       : nl == 2 ? launch_dgrad_block<2, 2, 3, 1, 0, 1, 4>(p, c.stream) : launch_dgrad_block<3, 2, 3, 1, 0, 1, 4>(p, c.stream);
-                else
-                    rc = nl == 1 ? launch_dgrad_block<1, 2, 3>(p, c.stream)
-                       : nl == 2 ? launch_dgrad_block<2, 2, 3>(p, c.stream) : launch_dgrad_block<3, 2, 3>(p, c.stream);
-                if (rc) return rc;
-            }
+            DgradBlockParams p = newmap_params(c, k, j, &a);
+            if (fv) { p.vg = fv->vg; p.vw = fv->vw + ic0 + p.w_ci_off; }
+            ProfScope prof(kProfDgradDense, c.stream, 2.0 * c.nt() * lv.plane * kGrowth * kGrowth * 9 * nl,
+                           4.0 * c.nt() * lv.plane * (3.0 * kGrowth + kGrowth * nl));
+            rc = nl == 1 ? launch_newmap<1>(bl.newmap[j], p, c.stream) : nl == 2 ? launch_newmap<2>(bl.newmap[j], p, c.stream) : launch_newmap<3>(bl.newmap[j], p, c.stream);
+            if (rc) return rc;
             pending = a;          // consumed by the prep_dy of these 12 maps at the top of the next iteration
             pending_nl = nl;
         }
     }
-    {   // base channels, all four layers in one pass
-        DgradBlockParams p{};
-        fill_common(p);
-        p.g = c.gbuf(level) + new0 * lv.plane;
-        p.x = c.act(level) + ic0 * lv.plane;
-        p.out = c.gbuf(level) + ic0 * lv.plane;
-        p.count = c0;
-        p.acc_from = base_overwrite ? c0 : 0;
-        p.w_ci_off = 0;
-        for (int j = 0; j < kLayers; ++j) {
-            p.wgt[j] = c.params + cv[j].w; p.w_cin[j] = cv[j].cin;
-            p.saved[j] = c.saved(bn[j]); p.gamma[j] = c.params + bn[j].g; p.beta[j] = c.params + bn[j].b;
-            p.scratch[j] = c.scratch(bn[j]);
-        }
+    {
+        DgradBlockParams p = base_pass_params(c, k);
+        const bool virt = fv && c.bwd->virt_base;
+        if (virt) { p.vg = fv->vg; p.vw = fv->vw + ic0; }
         ProfScope prof(kProfDgradDense, c.stream, 2.0 * c.nt() * lv.plane * c0 * kGrowth * 9 * kLayers,
                        4.0 * c.nt() * lv.plane * (3.0 * c0 + kGrowth * kLayers));
-        int rc;
-        const int form = base_pass_form(c, level, p, cv);
-        if (fv && fv->base) {
-            if (form != 1) return ENDO_E_BADARG;          // endo_net_bwd asked for a virtual base only where the phase-skewed kernel runs
-            p.vg = fv->vg; p.vw = fv->vw + ic0;
-        }
-        if (mfma_bf16_dgrad(c)) {
-            rc = launch_dgrad_block8<4, 1>(p, c.stream);
-        } else if (form != 0) {
-            // fine levels: Winograd F(2x2, 3x3), 48 instead of 108 MFMAs per 64 pixels and step (dgrad_wino_kernels.h)
-            const float* ub = c.gradws + c.net->wd_off;
-            const float* const u[4] = {ub + cv[0].ud, ub + cv[1].ud, ub + cv[2].ud, ub + cv[3].ud};
-            // form 1: the phase-skewed kernel (its U layout; endo_net_bwd transforms the weights to match), 2: the round-2 kernel
-            if (form == 1 && wino_dgrad_mode(c) == 3 && dgrad_wino3p_applies(p)) {
-                // persistent blocks, one per CU; with fv->base_w they leave per-block partials of dW_final[ic0 .. ic0 + c0), added up here
-                double* fwp = (fv && fv->base && fv->base_w) ? reinterpret_cast<double*>(c.gradws + c.net->fw_parts_off) : nullptr;
+        // the layers' Winograd-domain weights, in the U layout the plan had endo_net_bwd transform them to (BwdPlan::Block::wino3_layout)
+        const float* ub = c.gradws + c.net->wd_off;
+        const float* const u[4] = {ub + k.cv[0].ud, ub + k.cv[1].ud, ub + k.cv[2].ud, ub + k.cv[3].ud};
+        int rc = 0;
+        switch (bl.base) {
+            case BasePass::Block8Bf16: rc = launch_dgrad_block8<4, 1>(p, c.stream); break;
+            case BasePass::Block8: rc = launch_dgrad_block8<4>(p, c.stream); break;
+            case BasePass::Wino8: rc = launch_dgrad_wino8<4>(p, u, c.stream); break;
+            case BasePass::Wino3: rc = run_dgrad_wino3_nl4(p, u, c.stream); break;
+            case BasePass::Wino3Persistent: {
+                // persistent blocks, one per CU; with virt_base_w they leave per-block partials of dW_final[ic0 .. ic0 + c0), added up here
+                double* fwp = (virt && c.bwd->virt_base_w) ? reinterpret_cast<double*>(c.gradws + c.net->fw_parts_off) : nullptr;
                 int used = 0;
                 rc = run_dgrad_wino3p_nl4(p, u, std::min(device_cu_count(), kFwPartBlocks), fwp, &used, c.stream);
                 if (rc == 0 && fwp) {
                     final_w_reduce_kernel<<<c0, 64, 0, c.stream>>>(fwp, used, c0, fv->gw + ic0);
                     ENDO_LAUNCH_CHECK();
                 }
-            } else {
-                if (fv && fv->base && fv->base_w) return ENDO_E_BADARG;          // endo_net_bwd left these channels' final-conv weight gradient to the persistent kernel
-                rc = form == 1 ? run_dgrad_wino3_nl4(p, u, c.stream) : launch_dgrad_wino8<4>(p, u, c.stream);
+                break;
             }
-        } else {
-            rc = launch_dgrad_block8<4>(p, c.stream);       // 512-thread blocks: +15 % over the 4-wave kernel (tools/conv_bench)
         }
         if (rc) return rc;
     }
     {
         BnFin4 a;
         for (int j = 0; j < kLayers; ++j) {
-            a.scratch[j] = c.scratch(bn[j]); a.saved[j] = c.saved(bn[j]); a.gamma[j] = c.params + bn[j].g;
-            a.ggamma[j] = c.grads + bn[j].g; a.gbeta[j] = c.grads + bn[j].b;
+            a.scratch[j] = c.scratch(k.bn[j]); a.saved[j] = c.saved(k.bn[j]); a.gamma[j] = c.params + k.bn[j].g;
+            a.ggamma[j] = c.grads + k.bn[j].g; a.gbeta[j] = c.grads + k.bn[j].b;
         }
         ProfScope prof(kProfSmall, c.stream, 0.0, 0.0);
         bn_bwd_finalize4_kernel<<<dim3((c0 + 127) / 128, c.net->groups), 128, 0, c.stream>>>(a, kLayers, c.pq_p(level) + ic0, c.pq_q(level) + ic0, c0,
@@ -1151,53 +1360,32 @@ static int dense_block_bwd(const Ctx& c, int level, int ic0, int c0, const BnP* 
     return 0;
 }
 
-static int td_bwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
+static int td_bwd(const Ctx& c, int level) {
+    const BnP& b = table().td_bn[level];
+    const ConvP& cv = table().td_conv[level];
     const int next = level + 1;
-    const int oc0 = next < kLevels ? 48 : 0;
     const auto& lv = c.net->lv[level];
-    const auto& nx = c.net->lv[next];
-    int rc = prep_dy(c, next, oc0, cv.cout, c.grads + cv.b);
+    int rc = prep_dy(c, next, next < kLevels ? 48 : 0, cv.cout, c.grads + cv.b);
     if (rc) return rc;
     {
-        WgradParams p{};
-        fill_wgrad_grid(c, p, level);
-        p.in = c.act(level) + 48 * lv.plane; p.in_ns = lv.t * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = cv.cin;
-        p.saved = c.saved(b); p.gamma = c.params + b.g; p.beta = c.params + b.b;
-        p.dy = c.gbuf(next) + oc0 * nx.plane; p.dy_ns = nx.t * nx.plane; p.dy_cs = static_cast<int>(nx.plane); p.dy_w = nx.w; p.cout = cv.cout;
-        p.dy_idx = c.idx(level); p.idx_ns = static_cast<int64_t>(cv.cout) * nx.plane;
-        p.dw = c.grads + cv.w;
+        const WgradParams p = td_wgrad_params(c, level);
         Ctx cw;
         rc = c.fork_wgrad(cw, level);
         if (rc) return rc;
         ProfScope prof(kProfWgradOther, cw.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1), 4.0 * c.nt() * lv.plane * cv.cin);
-        rc = wgrad1x1_dma_ok(p) ? (mfma_bf16_wgrad(c) ? launch_wgrad1x1_dma<1>(p, cw.stream) : launch_wgrad1x1_dma<0>(p, cw.stream))
-                                : launch_wgrad1x1(p, cw.stream);
+        rc = !c.bwd->td_wgrad_dma[level] ? launch_wgrad1x1(p, cw.stream) : c.bwd->bf16_wgrad ? launch_wgrad1x1_dma<1>(p, cw.stream) : launch_wgrad1x1_dma<0>(p, cw.stream);
         if (rc) return rc;
     }
     {
-        ConvParams p{};
-        fill_grid(c, p, level);
-        fill_in(c, p, c.gbuf(next), next, oc0, cv.cout);
-        p.in_idx = c.idx(level); p.idx_ns = static_cast<int64_t>(cv.cout) * nx.plane;   // channel index relative to p.in
-        p.wgt = c.params + cv.w; p.w_cout = cv.cout; p.w_cin = cv.cin;
-        fill_out(c, p, c.gbuf(level), level, 48, cv.cin);
-        p.x = c.act(level) + 48 * lv.plane; p.x_ns = lv.t * lv.plane; p.x_cs = static_cast<int>(lv.plane);
-        p.bn_saved = c.saved(b); p.bn_gamma = c.params + b.g; p.bn_beta = c.params + b.b;
-        p.bn_scratch = c.scratch(b); p.bn_slot_stride = c.net->slot_stride;
-        p.acc_from = 0;
+        const ConvParams p = td_dgrad_params(c, level);
         ProfScope prof(kProfDgradOther, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1), 4.0 * c.nt() * lv.plane * 3.0 * cv.cin);
-        // pooled rows of whole code dwords -> LDS-DMA kernel; otherwise the register-staged one
-        // levels 0 / 1 of configs[1] (96 / 144 channels, whole 32 x 8 tiles): persistent blocks, weights LDS-resident, 16-byte DMA (td_dgrad_kernels.h)
-        if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 1) && !mfma_bf16_dgrad(c) && td_dgrad_ok(p))
-            rc = launch_td_dgrad(p, device_cu_count(), c.stream);
-        else if ((c.net->opt[ENDO_OPT_TD_PERSIST] & 1) && !mfma_bf16_dgrad(c) && nx.w % 4 != 0 && td_dgrad_small_ok(p))
-            // pooled rows without whole code dwords (level 4 of configs[1]: 8 x 10): 128-pixel runs, the routed gradient expanded on its way into
-            // LDS -- 46 instead of the register-staged kernel's 100 us.  (At levels 2 / 3 the LDS-DMA kernel stays: 103 / 63 against 139 / 69 us, tools/td_bench)
-            rc = launch_td_dgrad_small(p, c.stream);
-        else
-        rc = (nx.w % 4 == 0) ? (mfma_bf16_dgrad(c) ? launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4, 2, 1, 1>(p, c.stream)
-                                                  : launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4>(p, c.stream))
-                             : launch_conv_auto<1, 16, 3, IN_UNPOOL, EPI_DGRAD_BN, 4>(p, c.stream);
+        switch (c.bwd->td_dgrad[level]) {
+            case TdDgrad::Persistent: rc = launch_td_dgrad(p, device_cu_count(), c.stream); break;
+            case TdDgrad::Runs128: rc = launch_td_dgrad_small(p, c.stream); break;
+            case TdDgrad::Dma: rc = c.bwd->bf16_dgrad ? launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4, 2, 1, 1>(p, c.stream)
+                                                      : launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4>(p, c.stream); break;
+            case TdDgrad::Staged: rc = launch_conv_auto<1, 16, 3, IN_UNPOOL, EPI_DGRAD_BN, 4>(p, c.stream); break;
+        }
         if (rc) return rc;
     }
     return bn_finalize(c, b, level, 48);
@@ -1205,52 +1393,43 @@ static int td_bwd(const Ctx& c, int level, const BnP& b, const ConvP& cv) {
 
 static int tu_bwd(const Ctx& c, int level, int src_level, int src_c0, const ConvP& cv) {
     const auto& lv = c.net->lv[level];
-    const auto& sv = c.net->lv[src_level];
     int rc = prep_dy(c, level, 0, cv.cout, c.grads + cv.b);
     if (rc) return rc;
     {
-        WgradParams p{};
-        fill_wgrad_grid(c, p, level);
-        p.in = c.act(src_level) + src_c0 * sv.plane; p.in_ns = sv.t * sv.plane; p.in_cs = static_cast<int>(sv.plane); p.in_w = sv.w; p.cin = cv.cin;
-        p.dy = c.gbuf(level); p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = cv.cout;
-        p.dw = c.grads + cv.w;
+        const TuWgrad form = c.bwd->tu_wgrad[level];
+        const WgradParams p = tu_wgrad_params(c, level, form == TuWgrad::Subpix);
         Ctx cw;
         rc = c.fork_wgrad(cw, level);
         if (rc) return rc;
         ProfScope prof(kProfWgradOther, cw.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin / 4.0 + cv.cout));
-        WgradParams ps = p;                    // sub-pixel form walks the low-resolution grid
-        ps.h = sv.h; ps.w = sv.w;
-        if (tu_wgrad_subpix_ok(ps)) rc = launch_tu_wgrad_subpix(ps, c.gradws + c.net->wg_scratch_off, cw.stream);
-        else rc = wgrad_taps_ok(p, true) ? launch_wgrad_taps<12, IN_UPSAMPLE>(p, cw.stream) : launch_wgrad<3, 1, IN_UPSAMPLE, DY_PLAIN>(p, cw.stream);
+        rc = form == TuWgrad::Subpix ? launch_tu_wgrad_subpix(p, c.gradws + c.net->wg_scratch_off, cw.stream)
+           : form == TuWgrad::Taps ? launch_wgrad_taps<12, IN_UPSAMPLE>(p, cw.stream) : launch_wgrad<3, 1, IN_UPSAMPLE, DY_PLAIN>(p, cw.stream);
         if (rc) return rc;
     }
     ProfScope prof(kProfDgradOther, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cout + cv.cin / 4.0));
-    if (sv.w % 4 == 0 && cv.cin == kNew && cv.cout == kNew) {
-        // sub-pixel form on the low-resolution grid: the four stride-2 phases of dY are 4 x 48 pseudo input channels of a
-        // 3x3 convolution that uses 2x2 of its taps per phase (4/9 of the MACs); the weights have their own scratch (the n-split scratch belongs to the side stream)
-        float* wd = c.gradws + c.net->tuw_scratch_off;
-        tu_subpix_dgrad_weights_kernel<<<(16 * cv.cout * cv.cin + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, wd);
-        ENDO_LAUNCH_CHECK();
+    const TuDgrad form = c.bwd->tu_dgrad[level];
+    if (form == TuDgrad::Plain) {
         ConvParams p{};
-        fill_grid(c, p, src_level);
-        fill_in(c, p, c.gbuf(level), level, 0, 4 * cv.cout);      // strides of the full-resolution gradient buffer
-        p.sub_c = cv.cout;
-        p.wgt = wd; p.w_cout = cv.cin; p.w_cin = 4 * cv.cout;
+        fill_grid(c, p, level);
+        fill_in(c, p, c.gbuf(level), level, 0, cv.cout);
+        p.wgt = c.params + cv.w; p.w_cout = cv.cout; p.w_cin = cv.cin;
         fill_out(c, p, c.gbuf(src_level), src_level, src_c0, cv.cin);
-        // Tile shape by block count (round 6): on 32 x 8 tiles the launch of level 4 is 32 blocks and that of level 3 128 -- each walking all 24 K-chunks,
-        // 93 and 103 us for 0.1 and 0.4 GFLOP.  16 x 8 / 16 x 4 tiles where 32 x 8 ones leave the chip under-filled.
-        const long t32 = static_cast<long>((sv.w + 31) / 32) * ((sv.h + 7) / 8) * c.nt();
-        const long t16 = static_cast<long>((sv.w + 15) / 16) * ((sv.h + 7) / 8) * c.nt();
-        if (t32 >= 1024) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 2, 4, 2, 1, 1>(p, c.stream);
-        if (t16 >= 512) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream);
-        return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 1, 2, 1, 1>(p, c.stream);
+        return launch_conv_dma_auto<3, 4, 3, IN_PLAIN, EPI_DGRAD_SUMPOOL, 4>(p, c.stream);
     }
+    // sub-pixel form on the low-resolution grid: the four stride-2 phases of dY are 4 x 48 pseudo input channels of a
+    // 3x3 convolution that uses 2x2 of its taps per phase (4/9 of the MACs); the weights have their own scratch (the n-split scratch belongs to the side stream)
+    float* wd = c.gradws + c.net->tuw_scratch_off;
+    tu_subpix_dgrad_weights_kernel<<<(16 * cv.cout * cv.cin + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, wd);
+    ENDO_LAUNCH_CHECK();
     ConvParams p{};
-    fill_grid(c, p, level);
-    fill_in(c, p, c.gbuf(level), level, 0, cv.cout);
-    p.wgt = c.params + cv.w; p.w_cout = cv.cout; p.w_cin = cv.cin;
+    fill_grid(c, p, src_level);
+    fill_in(c, p, c.gbuf(level), level, 0, 4 * cv.cout);      // strides of the full-resolution gradient buffer
+    p.sub_c = cv.cout;
+    p.wgt = wd; p.w_cout = cv.cin; p.w_cin = 4 * cv.cout;
     fill_out(c, p, c.gbuf(src_level), src_level, src_c0, cv.cin);
-    return launch_conv_dma_auto<3, 4, 3, IN_PLAIN, EPI_DGRAD_SUMPOOL, 4>(p, c.stream);
+    if (form == TuDgrad::Subpix32x8) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 2, 4, 2, 1, 1>(p, c.stream);
+    if (form == TuDgrad::Subpix16x8) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream);
+    return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 1, 2, 1, 1>(p, c.stream);
 }
 
 static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -1387,22 +1566,20 @@ extern "C" int endo_net_fwd(endo_net* net, const float* params, float* bn_runnin
     if (!net || !params || !bn_running || !x || !out || !tape) return ENDO_E_BADARG;
     const Table& tb = table();
     Ctx c{net, params, bn_running, tape, nullptr, nullptr, training, static_cast<hipStream_t>(stream_)};
+    const FwdPlan plan = plan_fwd(c);
+    c.fwd = &plan;
     for (int g = 0; g < net->groups; ++g)
         ENDO_CHECK(hipMemsetAsync(reinterpret_cast<char*>(tape + g * net->gs) + net->sums_off, 0, net->sums_bytes, c.stream));
-    if (!mfma_bf16_fwd(c)) {          // dense-layer weights in Winograd form or in the direct kernel's chunk order, all 44 layers in one launch
+    if (!plan.bf16) {          // dense-layer weights in Winograd form or in the direct kernel's chunk order, as each layer's planned form reads them: all 44 layers in one launch
         ProfScope prof(kProfSmall, c.stream, 0.0, 4.0 * (tb.wino_floats + tb.wino_floats * 9 / 16));
-        WinoWeightTable wt = tb.wino;          // per pass: which layers want their weights in the direct kernel's chunk order (table order: down, bottleneck, up)
-        for (int l = 0; l < wt.layers; ++l) {
-            const int level = l < kLevels * kLayers ? l / kLayers : (l < (kLevels + 1) * kLayers ? kLevels : kLevels - 1 - (l - (kLevels + 1) * kLayers) / kLayers);
-            wt.mode[l] = dense_fwd_chunk_weights(c, level) ? 1 : 0;
-        }
+        WinoWeightTable wt = tb.wino;
+        for (int l = 0; l < wt.layers; ++l) wt.mode[l] = plan.dense[l].chunk_weights ? 1 : 0;
         wino_fwd_weights_kernel<<<(wt.start[wt.layers] + 255) / 256, 256, 0, c.stream>>>(wt, params, tape + net->wino_off);
         ENDO_LAUNCH_CHECK();
-        if (wino_fwd_mode(c) == 5) wino4_fwd_weights_kernel<<<(tb.wino4.start[tb.wino4.layers] + 255) / 256, 256, 0, c.stream>>>(tb.wino4, params, tape + net->wino4_off);
+        if (plan.wino4_weights) wino4_fwd_weights_kernel<<<(tb.wino4.start[tb.wino4.layers] + 255) / 256, 256, 0, c.stream>>>(tb.wino4, params, tape + net->wino4_off);
         ENDO_LAUNCH_CHECK();
     }
     int rc;
-    bool fused_final = false;
     {   // first conv 3 -> 48 into level-0 channels [48, 96)
         ConvParams p{};
         fill_grid(c, p, 0);
@@ -1415,34 +1592,24 @@ extern "C" int endo_net_fwd(endo_net* net, const float* params, float* bn_runnin
         rc = launch_conv_dma_auto<3, 4, 3, IN_PLAIN, EPI_FWD>(p, c.stream);
         if (rc) return rc;
     }
-    for (int l = 0; l < kLevels; ++l) {
-        for (int j = 0; j < kLayers; ++j) {
-            rc = dense_fwd(c, l, 48, 48 + down_in(l) + kGrowth * j, tb.down_bn[l][j], tb.down_conv[l][j]);
+    for (int b = 0; b < kBlocks; ++b) {          // down path: block, transition down; bottleneck; up path: transition up, block
+        if (b > kLevels) {
+            const int i = b - kLevels - 1, l = kLevels - 1 - i;
+            rc = tu_fwd(c, l, l + 1, (i == 0) ? 288 : 96 + down_in(l + 1), tb.tu_conv[i]);
             if (rc) return rc;
         }
-        rc = td_fwd(c, l, tb.td_bn[l], tb.td_conv[l]);
-        if (rc) return rc;
-    }
-    for (int j = 0; j < kLayers; ++j) {
-        rc = dense_fwd(c, kLevels, 0, 288 + kGrowth * j, tb.bott_bn[j], tb.bott_conv[j]);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < kLevels; ++i) {
-        const int l = kLevels - 1 - i;
-        const int src = l + 1;
-        const int src_c0 = (i == 0) ? 288 : 96 + down_in(src);
-        rc = tu_fwd(c, l, src, src_c0, tb.tu_conv[i]);
-        if (rc) return rc;
         for (int j = 0; j < kLayers; ++j) {
-            const bool last = l == 0 && j == kLayers - 1;          // the layer whose 180 input channels are all but 12 of the final convolution's
-            rc = dense_fwd(c, l, 0, 96 + down_in(l) + kGrowth * j, tb.up_bn[i][j], tb.up_conv[i][j], last ? params + tb.final_.w : nullptr,
-                           last ? tape + net->pre_off : nullptr, last ? &fused_final : nullptr);
+            rc = dense_fwd(c, b, j);
+            if (rc) return rc;
+        }
+        if (b < kLevels) {
+            rc = td_fwd(c, b);
             if (rc) return rc;
         }
     }
     {
         const auto& lv = net->lv[0];
-        const int c_first = fused_final ? 96 + down_in(0) + kGrowth * (kLayers - 1) : 0;          // 180: the last layer's launch has summed channels [0, 180) into `pre`
+        const int c_first = plan.fuse_final ? 96 + down_in(0) + kGrowth * (kLayers - 1) : 0;          // 180: the last layer's launch has summed channels [0, 180) into `pre`
         ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * 192, 4.0 * c.nt() * lv.plane * (194 - c_first));
         int bx = static_cast<int>((lv.plane / 4 + 255) / 256);
         bx = bx < 1 ? 1 : bx;
@@ -1459,6 +1626,9 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
     if (!net || !params || !x || !tape || !grad_out || !grads || !gradws) return ENDO_E_BADARG;
     const Table& tb = table();
     Ctx c{net, params, nullptr, const_cast<float*>(tape), grads, gradws, training, static_cast<hipStream_t>(stream_)};
+    c.x = x;
+    const BwdPlan plan = plan_bwd(c);
+    c.bwd = &plan;
     BiasParts bias_parts{};
     c.bias_parts = &bias_parts;
     if (!net->wstream) {          // side stream of the weight gradients (see endo_net), created on first use on the caller's device
@@ -1470,42 +1640,23 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
     for (int g = 0; g < net->groups; ++g)
         ENDO_CHECK(hipMemsetAsync(gradws + g * net->gs + net->pq_off, 0,
                                   static_cast<size_t>(net->scratch_off + net->scratch_bytes - net->pq_off * 4), c.stream));
-    if (wino_dgrad_enabled(c) && !mfma_bf16_dgrad(c)) {          // data-gradient weights of the dense layers in Winograd form, one launch
+    if (plan.dgrad_weights) {          // data-gradient weights of the dense layers in Winograd form, each block's in the U layout its planned base pass reads: one launch
         ProfScope prof(kProfSmall, c.stream, 0.0, 4.0 * 2.0 * tb.wino_dgrad_floats);
-        // mode 1: blocks the phase-skewed kernel takes (dgrad_wino3_ok: at most 12 base-channel groups) get its U layout
-        dgrad_wino_weights_kernel<<<(tb.wino_dgrad.start[tb.wino_dgrad.layers] + 255) / 256, 256, 0, c.stream>>>(
-            tb.wino_dgrad, params, gradws + net->wd_off, (wino_dgrad_mode(c) == 1 || wino_dgrad_mode(c) == 3) ? DgradWino3Geom<4>::kMaxCount / 16 : 0);
+        int layout1_blocks = 0;
+        for (int b = 0; b < kBlocks; ++b) layout1_blocks |= plan.block[b].wino3_layout ? 1 << b : 0;
+        dgrad_wino_weights_kernel<<<(tb.wino_dgrad.start[tb.wino_dgrad.layers] + 255) / 256, 256, 0, c.stream>>>(tb.wino_dgrad, params, gradws + net->wd_off, layout1_blocks);
         ENDO_LAUNCH_CHECK();
     }
     int rc;
-    FinalVirt virt{};
-    bool use_virt = false;
-    {
+    const FinalVirt virt{gradws + net->gplane_off, params + tb.final_.w, grads + tb.final_.w};
+    {   // final convolution (what the last up block forms itself: BwdPlan::use_virt)
         const auto& lv = net->lv[0];
-        // The final convolution's data gradient is rank one: dX[c] = g * w[c], g = grad_out * sign(pre).  Writing it out (192 planes, 1 GB
-        // at 16 x 256 x 320) only for the last up block to read it back costs two passes over the level-0 buffer; instead g goes to one
-        // plane and that block's kernels form the products where they first touch a channel (FinalVirt) -- where the block takes the
-        // fused path, and for its base channels where the phase-skewed Winograd kernel runs; what is left is materialised as before.
-        DgradBlockParams probe{};
-        probe.n = c.nt(); probe.h = lv.h; probe.w = lv.w; probe.count = 96 + down_in(0);
-        probe.cs = static_cast<int>(lv.plane); probe.ns = lv.t * lv.plane;
-        probe.g_cs = static_cast<int>(lv.plane);
-        probe.x = c.act(0); probe.out = c.gbuf(0);
-        virt.vg = gradws + net->gplane_off; virt.vw = params + tb.final_.w; virt.base = false; virt.base_w = false; virt.gw = grads + tb.final_.w;
-        int materialise = 192;          // channels [0, materialise) are written by final_bwd_data_kernel
-        if (c.net->opt[ENDO_OPT_FINAL_VIRTUAL] && dgrad_block_ok(probe)) {
-            use_virt = true;
-            virt.base = base_pass_form(c, 0, probe, tb.up_conv[kLevels - 1]) == 1;
-            materialise = virt.base ? 0 : 96 + down_in(0);
-            // ... and where that kernel runs as persistent blocks it also forms sum g * x[c] of the base channels it streams: the final
-            // convolution's weight gradient of those channels (round 6: final_bwd_weight_kernel then reads 48 + 1 instead of 192 + 1 planes)
-            virt.base_w = virt.base && wino_dgrad_mode(c) == 3 && dgrad_wino3p_applies(probe);
-        }
+        const int materialise = plan.materialise;
         {   // final conv weight / bias gradient: reads only grad_out and the tape, so it goes to the side stream first
             Ctx cw;
             rc = c.fork_wgrad(cw, 0);
             if (rc) return rc;
-            const int c_first = virt.base_w ? 96 + down_in(0) : 0;
+            const int c_first = plan.c_first;          // (the channels below it are the persistent base pass's)
             int by = static_cast<int>((lv.plane + 256 * 16 - 1) / (256 * 16));       // 16 pixels per thread
             by = by < 1 ? 1 : (by > 16 ? 16 : by);
             ProfScope prof(kProfConvFinal, cw.stream, 2.0 * c.nt() * lv.plane * (192 - c_first), 4.0 * c.nt() * lv.plane * (192 - c_first + 2));
@@ -1515,7 +1666,7 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
             ENDO_LAUNCH_CHECK();
         }
         ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * 192, 4.0 * c.nt() * lv.plane * (materialise + 2));
-        if (use_virt) {
+        if (plan.use_virt) {
             int bx = static_cast<int>((lv.plane + 1023) / 1024);
             final_g_kernel<<<dim3(bx, c.nt()), 256, 0, c.stream>>>(grad_out, tape + net->pre_off, gradws + net->gplane_off, static_cast<int>(lv.plane), net->n, net->gs);
             ENDO_LAUNCH_CHECK();
@@ -1527,36 +1678,23 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
             ENDO_LAUNCH_CHECK();
         }
     }
-    for (int i = kLevels - 1; i >= 0; --i) {
-        const int l = kLevels - 1 - i;
-        rc = dense_block_bwd(c, l, 0, 96 + down_in(l), tb.up_bn[i], tb.up_conv[i], l > 0, (l == 0 && use_virt) ? &virt : nullptr);
+    for (int b = kBlocks - 1; b >= 0; --b) {          // the forward pass's order, backwards
+        if (b < kLevels) {
+            rc = td_bwd(c, b);
+            if (rc) return rc;
+        }
+        rc = dense_block_bwd(c, b, (b == kBlocks - 1 && plan.use_virt) ? &virt : nullptr);
         if (rc) return rc;
-        const int src = l + 1;
-        const int src_c0 = (i == 0) ? 288 : 96 + down_in(src);
-        rc = tu_bwd(c, l, src, src_c0, tb.tu_conv[i]);
-        if (rc) return rc;
-    }
-    rc = dense_block_bwd(c, kLevels, 0, 288, tb.bott_bn, tb.bott_conv, true);
-    if (rc) return rc;
-    for (int l = kLevels - 1; l >= 0; --l) {
-        rc = td_bwd(c, l, tb.td_bn[l], tb.td_conv[l]);
-        if (rc) return rc;
-        rc = dense_block_bwd(c, l, 48, down_in(l), tb.down_bn[l], tb.down_conv[l], false);
-        if (rc) return rc;
+        if (b > kLevels) {
+            const int i = b - kLevels - 1, l = kLevels - 1 - i;
+            rc = tu_bwd(c, l, l + 1, (i == 0) ? 288 : 96 + down_in(l + 1), tb.tu_conv[i]);
+            if (rc) return rc;
+        }
     }
     {   // first conv: bias grad + weight grad (the image needs no gradient)
+        WgradParams p = first_wgrad_params(c);
         const auto& lv = net->lv[0];
-        WgradParams p{};
-        fill_wgrad_grid(c, p, 0);
-        p.in = x; p.in_ns = 3 * lv.plane; p.in_cs = static_cast<int>(lv.plane); p.in_w = lv.w; p.cin = 3;
-        p.in_gs = net->n * p.in_ns;                 // the caller's image tensor
-        p.dy = c.gbuf(0) + 48 * lv.plane; p.dy_ns = lv.t * lv.plane; p.dy_cs = static_cast<int>(lv.plane); p.dy_w = lv.w; p.cout = kFirst;
-        p.dw = grads + tb.first.w;
-        // The F(3x3, 4x4) form prepares the gradient itself (G = d + P x + Q, bias gradient = sum G: WgradParams::prep_x): this is the LAST kernel
-        // of the backward pass, nothing else is on the chip, and prep_dy's own pass over 3 x 48 planes would be 0.1 ms of the step
-        const bool f34 = c.net->opt[ENDO_OPT_WGRAD_F34] && wgrad_mfma_mode(c) == 0 && wgrad_f34_raw_ok(p, c.net->opt[ENDO_OPT_WINO_MIN_TILES] / 4l);
-        const bool fuse_prep = f34 && c.net->opt[ENDO_OPT_FINAL_VIRTUAL];
-        if (fuse_prep) {
+        if (plan.first == FirstWgrad::F34Prep) {
             p.prep_x = c.act(0) + 48 * lv.plane;
             p.prep_p = c.pq_p(0) + 48; p.prep_q = c.pq_q(0) + 48;
             p.prep_bias = grads + tb.first.b;
@@ -1567,18 +1705,16 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         Ctx cw;
         rc = c.fork_wgrad(cw, 0);
         if (rc) return rc;
-        {
-            ProfScope prof(kProfWgradOther, cw.stream, conv_flops(net, 0, 3, kFirst, 3), 4.0 * c.nt() * lv.plane * (3 + kFirst));
-            // 3 -> 48 channels: in the F(3x3, 4x4) form the four sets of 12 output channels share one launch (the tap-folded kernel runs a
-            // 108-row GEMM with 3 of 16 columns in use, four times: 216 us alone on the chip at the very end of the backward)
-            if (fuse_prep)
-                rc = launch_wgrad_f34<0, true, true>(p, c.gradws + c.net->wg_scratch_off, cw.stream);
-            else if (f34)
-                rc = launch_wgrad_f34<0, true>(p, c.gradws + c.net->wg_scratch_off, cw.stream);
-            else
-            rc = wgrad_taps_ok(p) ? launch_wgrad_taps<12, IN_PLAIN>(p, cw.stream) : launch_wgrad<3, 3, IN_PLAIN, DY_PLAIN>(p, cw.stream);
-            if (rc) return rc;
+        ProfScope prof(kProfWgradOther, cw.stream, conv_flops(net, 0, 3, kFirst, 3), 4.0 * c.nt() * lv.plane * (3 + kFirst));
+        // 3 -> 48 channels: in the F(3x3, 4x4) form the four sets of 12 output channels share one launch (the tap-folded kernel runs a
+        // 108-row GEMM with 3 of 16 columns in use, four times: 216 us alone on the chip at the very end of the backward)
+        switch (plan.first) {
+            case FirstWgrad::F34Prep: rc = launch_wgrad_f34<0, true, true>(p, gradws + net->wg_scratch_off, cw.stream); break;
+            case FirstWgrad::F34: rc = launch_wgrad_f34<0, true>(p, gradws + net->wg_scratch_off, cw.stream); break;
+            case FirstWgrad::Taps: rc = launch_wgrad_taps<12, IN_PLAIN>(p, cw.stream); break;
+            case FirstWgrad::Direct: rc = launch_wgrad<3, 3, IN_PLAIN, DY_PLAIN>(p, cw.stream); break;
         }
+        if (rc) return rc;
     }
     if (bias_parts.table.n > 0) {          // the conv-bias gradients from prep_dy's per-block sums (BiasParts): one launch for the whole pass
         ProfScope prof(kProfSmall, c.stream, 0.0, 4.0 * bias_parts.used);

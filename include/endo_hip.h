@@ -268,11 +268,14 @@ int endo_net_groups(const endo_net* net);
  *                            split_bf16x8) -- fp32 operands and fp32-level accuracy (held to the fp32 bounds by the parity tests) at
  *                            6 / 16 of the fp32 matrix instructions' issue time.  Ignored where ENDO_OPT_MFMA_BF16 selects rounded operands.
  *   ENDO_OPT_WGRAD_OVERLAP   endo_net_bwd runs the weight gradients on a side stream of its own, overlapped with the data-gradient
- *                            chain and joined before it returns: 1 (default); 0 puts them back in line on the
+ *                            chain and joined before it returns: 1 (default) = forked behind every gradient preparation;
+ *                            2 = in the fused dense blocks ONE fork per block, behind its last preparation (its four weight gradients
+ *                            start later; 22 instead of 55 event record / wait pairs per pass); 0 puts them back in line on the
  *                            caller's stream (clean per-kernel timings)
  *   ENDO_OPT_WGRAD_F34       dense-layer weight gradient where the height is a multiple of 16 and the width of 4 (levels 0-4 at 256 x 320): 1 (default) = in the
  *                            Winograd domain, F(3x3, 4x4) -- 36 multiplications per 4 x 4 tile of the output gradient instead of 144,
- *                            fp32 throughout (csrc/wgrad_f34_kernels.h); 0 = the direct kernels.  Ignored where ENDO_OPT_MFMA_BF16 or
+ *                            fp32 throughout (csrc/wgrad_f34_kernels.h); 2 = the same with 256 instead of 512 blocks per dense-layer
+ *                            launch (one instead of two per compute unit); 0 = the direct kernels.  Ignored where ENDO_OPT_MFMA_BF16 or
  *                            ENDO_OPT_MFMA_X3 select another operand form for the weight gradients.
  *   ENDO_OPT_FINAL_VIRTUAL   1 (default) = the data gradient of the final 1x1 convolution (models.py:167, 186), g(pixel) * w[channel] with
  *                            g = grad_out * sign(pre), is not written to the 192 level-0 gradient planes: g goes to one plane and the last up

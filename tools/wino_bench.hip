@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
     float* ubuf; CK(hipMalloc(&ubuf, uoff * sizeof(float)));
     float* ubuf1; CK(hipMalloc(&ubuf1, uoff * sizeof(float)));
     dgrad_wino_weights_kernel<<<(start + 255) / 256, 256>>>(tb, wgt, ubuf, 0);
-    dgrad_wino_weights_kernel<<<(start + 255) / 256, 256>>>(tb, wgt, ubuf1, 1 << 20);
+    dgrad_wino_weights_kernel<<<(start + 255) / 256, 256>>>(tb, wgt, ubuf1, 1);
     CK(hipDeviceSynchronize());
 
     DgradBlockParams p{};
