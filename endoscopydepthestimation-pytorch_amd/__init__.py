@@ -12,4 +12,4 @@ The directory name carries a hyphen, so import it with
 
 from . import _lib, augment, dataset, display, distributed, evaluate, losses, models, optim, reader, scatter, scheduler, synthetic, train_step, utils  # noqa: F401
 from .models import FCDenseNet57, DepthScalingLayer, DepthWarpingLayer, FlowfromDepthLayer  # noqa: F401
-from .losses import SparseMaskedL1Loss, NormalizedDistanceLoss, ScaleInvariantLoss  # noqa: F401
+from .losses import SparseMaskedL1Loss, NormalizedDistanceLoss, ScaleInvariantLoss, AbsRelError, Threshold  # noqa: F401

@@ -103,6 +103,10 @@ SIGNATURES = {
     "endo_display_panel_shape": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "endo_display": (_I, [_P] * 9 + [_I, _I, _I, _P, _P, _L, _P]),
     "endo_validation_accumulate": (_I, [_P, _I, _P, _P, _P]),
+    "endo_depth_metrics": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    "endo_evaluate_validation_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_evaluate_validation_panel_shape": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "endo_evaluate_validation": (_I, [_P] * 16 + [_I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "endo_point_brightness": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
     "endo_prof_enable": (_I, [_I]),
     "endo_prof_sample": (_I, [_I]),

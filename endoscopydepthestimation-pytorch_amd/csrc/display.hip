@@ -16,48 +16,14 @@
 #include <cmath>
 
 #include "common.h"
-#include "hsv_device.h"
+#include "display_device.h"          // the make_grid geometry and the depth / flow pixel forms, shared with evaluate_validation.hip
 #include "jet_device.h"
 
 namespace endo {
 
-constexpr int kDispThreads = 256;
-constexpr int kDispBandRows = 8;                // frame rows per reduce block
-constexpr int kDispNrow = 8, kDispPad = 2;      // make_grid(nrow = 8, padding = 2)
 constexpr int kDispPartial = 4;                 // floats per partial: depth min, depth max, sparse-flow max v, (unused)
 
-struct DisplayGeom {
-    int n, h, w;
-    int xmaps, ymaps, pad;      // make_grid: min(8, N) columns of frames, ceil(N / xmaps) rows, padding (0 when N = 1)
-    int gh, gw;                 // one section: (H + 2) ymaps + 2 by (W + 2) xmaps + 2, or H by W when N = 1
-    int bands;                  // reduce blocks per frame
-};
-
-static DisplayGeom display_geom(int n, int h, int w) {
-    DisplayGeom g;
-    g.n = n; g.h = h; g.w = w;
-    g.bands = (h + kDispBandRows - 1) / kDispBandRows;
-    if (n == 1) {
-        g.xmaps = g.ymaps = 1;
-        g.pad = 0;
-        g.gh = h;
-        g.gw = w;
-    } else {
-        g.xmaps = n < kDispNrow ? n : kDispNrow;
-        g.ymaps = (n + g.xmaps - 1) / g.xmaps;
-        g.pad = kDispPad;
-        g.gh = (h + kDispPad) * g.ymaps + kDispPad;
-        g.gw = (w + kDispPad) * g.xmaps + kDispPad;
-    }
-    return g;
-}
-
-static bool display_sizes_ok(int n, int h, int w) {
-    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || static_cast<int64_t>(n) * h * w > INT32_MAX) return false;
-    const int64_t xmaps = n < kDispNrow ? n : kDispNrow, ymaps = (n + xmaps - 1) / xmaps;
-    const int64_t gh = (static_cast<int64_t>(h) + kDispPad) * ymaps + kDispPad, gw = (static_cast<int64_t>(w) + kDispPad) * xmaps + kDispPad;
-    return 8 * gh <= INT32_MAX && 3 * gw <= INT32_MAX;
-}
+static bool display_sizes_ok(int n, int h, int w) { return display_sizes_in_range(n, h, w, 8); }
 
 static int64_t display_workspace_bytes(int n, int h) {
     const int64_t floats = 2 * static_cast<int64_t>(n) * ((h + kDispBandRows - 1) / kDispBandRows) * kDispPartial;
@@ -74,15 +40,6 @@ struct DisplayParams {
     float* partials;                                    // [2][N][bands][kDispPartial]
     uint8_t* out;                                       // [8 gh][gw][3] R, G, B
 };
-
-// draw_flow's y component on the grid: flows_display[..., 1] * h / w with the GRID's height and width (two float32 roundings)
-__device__ __forceinline__ float flow_fy(float y, float gh, float gw) { return __fdiv_rn(__fmul_rn(y, gh), gw); }
-
-// np.sqrt(fx * fx + fy * fy) in float32
-__device__ __forceinline__ float flow_v(float fx, float fy) { return sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy))); }
-
-// the larger of a and b, a NaN kept (np.max propagates it; v >= +0 otherwise)
-__device__ __forceinline__ float max_keep_nan(float a, float b) { return (b > a || b != b) ? b : a; }
 
 // trunc(clip(255 (0.5 c + 0.5), 0, 255)): torch's c * 0.5 + 0.5 (two roundings), then tensorboardX's float-image conversion
 __device__ __forceinline__ int panel_u8(float c) {
@@ -131,16 +88,6 @@ __global__ void __launch_bounds__(kDispThreads) display_reduce_kernel(const Disp
     }
 }
 
-// grid coordinate -> frame coordinate along one axis: the frame index along the axis and the position inside the frame, -1 on padding
-__device__ __forceinline__ int grid_axis(int at, int size, int pad, int& cell) {
-    if (pad == 0) { cell = 0; return at; }
-    const int t = at - pad;
-    if (t < 0) { cell = 0; return -1; }
-    cell = t / (size + pad);
-    const int inside = t - cell * (size + pad);
-    return inside < size ? inside : -1;
-}
-
 __global__ void __launch_bounds__(kDispThreads) display_write_kernel(const DisplayParams q) {
     __shared__ uint8_t s_jet[256][3];                                  // B G R
     __shared__ float s_lo[kDispNrow], s_hi[kDispNrow], s_den[kDispNrow];     // the depth range of each frame of this grid row
@@ -171,10 +118,9 @@ __global__ void __launch_bounds__(kDispThreads) display_write_kernel(const Displ
                 hi = fmaxf(hi, __shfl_down(hi, off, 64));
             }
             if (lane == 0) {
-                // norm_ip(img, float(t.min()), float(t.max())): the divisor max - min + 1e-5 is a Python float, rounded once to float32
                 s_lo[x] = lo;
                 s_hi[x] = hi;
-                s_den[x] = __double2float_rn(__dadd_rn(__dsub_rn(static_cast<double>(hi), static_cast<double>(lo)), 1.0e-5));
+                s_den[x] = norm_divisor(lo, hi);          // norm_ip(img, float(t.min()), float(t.max()))
             }
         }
         __syncthreads();
@@ -190,8 +136,6 @@ __global__ void __launch_bounds__(kDispThreads) display_write_kernel(const Displ
         for (int i = 1; i < kDispThreads / 64; ++i) vmax = max_keep_nan(vmax, s_v[i]);
     }
     const float ghf = static_cast<float>(g.gh), gwf = static_cast<float>(g.gw);
-    const float pi_f = static_cast<float>(M_PI);                       // np.pi added to a float32 array
-    const float hue_scale = static_cast<float>(180.0 / M_PI / 2.0);    // 180 / np.pi / 2 multiplied into a float32 array
     const float* colors = half ? q.colors_2 : q.colors_1;
     const float* depth = half ? q.depths_2 : q.depths_1;
     const float* flow = kind == 2 ? (half ? q.sparse_2 : q.sparse_1) : (half ? q.dense_2 : q.dense_1);
@@ -216,33 +160,19 @@ __global__ void __launch_bounds__(kDispThreads) display_write_kernel(const Displ
             int idx = 0;
             if (inside) {
                 const float d = __fmul_rn(depth[f * plane + at], q.boundaries[f * plane + at]);
-                const float lo = s_lo[gx], hi = s_hi[gx];
-                const float x = __fdiv_rn(__fsub_rn(fminf(fmaxf(d, lo), hi), lo), s_den[gx]);
-                const float v = __fmul_rn(255.0f, x);
-                idx = v > 0.0f ? min(static_cast<int>(v), 255) : 0;
+                idx = norm_jet_index(d, s_lo[gx], s_hi[gx], s_den[gx]);
             }
             rgb[0] = s_jet[idx][2];
             rgb[1] = s_jet[idx][1];
             rgb[2] = s_jet[idx][0];
         } else {
-            // draw_flow: fx = x, fy = y Hg / Wg, ang = atan2(fy, fx) + pi, v = |(fx, fy)|, H = ang 180 / pi / 2, S = 255,
-            // V = min(v / max_v, 1) 255 (0 where that is NaN: max_v = 0 and v = 0), cv2.COLOR_HSV2BGR then BGR -> RGB.  The padding
-            // is +0 in both components.  atan2 in fp64, rounded once: the correctly rounded float32 angle (ocml's atan2f may be an ulp off).
+            // draw_flow (flow_pixel_rgb); the padding is +0 in both components
             float fx = 0.0f, y = 0.0f;
             if (inside) {
                 fx = flow[2 * f * plane + at];
                 y = flow[(2 * f + 1) * plane + at];
             }
-            const float fy = flow_fy(y, ghf, gwf);
-            const float t = __fdiv_rn(flow_v(fx, fy), vmax);
-            int val = 0;
-            if (t == t) {
-                const float s = __fmul_rn(fminf(t, 1.0f), 255.0f);
-                val = s > 0.0f ? min(static_cast<int>(s), 255) : 0;
-            }
-            const float ang = __fadd_rn(__double2float_rn(atan2(static_cast<double>(fy), static_cast<double>(fx))), pi_f);
-            const int hue = static_cast<int>(__fmul_rn(ang, hue_scale));
-            hsv_to_rgb<180>(hue, 255, val, rgb);          // cv2.COLOR_HSV2BGR, then BGR -> RGB: rgb as it comes
+            flow_pixel_rgb(fx, y, ghf, gwf, vmax, rgb);
         }
         dst[3 * c] = static_cast<uint8_t>(rgb[0]);
         dst[3 * c + 1] = static_cast<uint8_t>(rgb[1]);

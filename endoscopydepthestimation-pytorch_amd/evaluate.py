@@ -6,15 +6,29 @@ coloured PLY point cloud, for batches of frames (dataset.TestFrames) on the devi
     per frame   utils.write_png / utils.write_point_cloud on a small writer pool, while the next batch is decoded and run
 
 The reference needs cv2 and plyfile here and runs one frame per batch with all per-pixel work on the host (evaluate.py:292, 329-345).
+
+The validation phase (evaluate.py:119-277) compares a trained network with the sparse reconstruction of a sequence, for batches of
+pairs (dataset.TrainingBatches(transform=None, shuffle=False): the reference's SfMDataset(phase="validation")):
+
+    per batch   validation_outputs: the masked pair through the network in eval mode, depth scaling, flows from depth and warped
+                depths in both directions with the training step's modules, then endo_evaluate_validation (csrc/
+                evaluate_validation.hip: three launches): the 12-section panel, AbsRelError / Threshold of both frames and the point
+                clouds of frame 1; one host read
+    per batch   run_validation_phase: ``<batch>.png`` and ``<batch>.ply`` on the writer pool, the metrics read once at the end
+
+The reference cannot run this phase as written: it unpacks 17 items from the loader's 18 (evaluate.py:167-171) and needs cv2,
+torchvision, plyfile and tensorboardX.
 """
 
 import os
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
-from . import _lib, utils
+from . import _lib, display, models, utils
+from .train_step import mask_mul
 
 
 def _device_f32(t, shape, name):
@@ -111,3 +125,111 @@ def run_test_phase(model, frames, out_dir, write_png=True, write_ply=True, ply_t
             while pending:
                 pending.popleft().result()
     return count
+
+
+VALIDATION_TITLE = "Results (c1, sd1, d1, wd1, sf1, df1, c2, sd2, d2, wd2, sf2, df2)"          # evaluate.py:258
+
+
+def validation_outputs(model, batch, epsilon=1.0e-8, is_hsv=False, point_cloud_downsampling=1):
+    """evaluate.py:189-274 for a TrainingBatches batch, on the device, under no_grad: the masked colours and sparse flows, the two
+    forward passes (one grouped call where the model has forward_pair), DepthScalingLayer, FlowfromDepthLayer in both directions
+    (masked) and DepthWarpingLayer in both directions, then one endo_evaluate_validation call.  The reference's torch.abs on the
+    predictions (evaluate.py:197, 199) is the identity: the network ends in an absolute value (models.py:186).
+    Returns a dictionary of device tensors -- colors_1/2 (masked), sparse_flows_1/2 (masked), predictions_1/2, scaled_depths_1/2,
+    flows_1/2 (masked), warped_depths_2_to_1 / _1_to_2, intersect_masks_1/2, panel (12 Hg, Wg, 3) uint8 R, G, B, metrics (N, 2, 4)
+    [abs rel, sigma 1, 2, 3] per pair and frame, points (capacity N H W rows) -- and offsets: the host list of N + 1 row offsets,
+    pair f's cloud (its frame 1) being points[offsets[f]:offsets[f + 1]] -- the batch's one read back to the host.
+    The point colours are the frame's own R, G, B (the reference converts them with COLOR_HSV2BGR_FULL whatever the colour space,
+    evaluate.py:202-203); is_hsv=True is not implemented (display.validation_panels)."""
+    if model.training:
+        raise RuntimeError("validation_outputs runs the network in eval mode: call model.eval() first (evaluate.py:164)")
+    if is_hsv:
+        raise NotImplementedError("HSV display panels: the reference converts the float colour grid with cv2.COLOR_HSV2RGB_FULL's float path, "
+                                  "which is not implemented")
+    b = _lib.dev_f32(batch["boundaries"], "boundaries")
+    eps = float(epsilon)
+    scaling, warping, flow_layer = models.DepthScalingLayer(epsilon=eps), models.DepthWarpingLayer(epsilon=eps), models.FlowfromDepthLayer()
+    with torch.no_grad(), torch.cuda.device(b.device):
+        colors_1 = mask_mul(batch["colors_1"], b)          # evaluate.py:189-192
+        colors_2 = mask_mul(batch["colors_2"], b)
+        sparse_flows_1 = mask_mul(batch["sparse_flows_1"], b)
+        sparse_flows_2 = mask_mul(batch["sparse_flows_2"], b)
+        if hasattr(model, "forward_pair"):
+            pred_1, pred_2 = model.forward_pair(colors_1, colors_2)
+        else:
+            pred_1, pred_2 = model(colors_1), model(colors_2)
+        scaled_1, _ = scaling([pred_1, batch["sparse_depths_1"], batch["sparse_depth_masks_1"]])
+        scaled_2, _ = scaling([pred_2, batch["sparse_depths_2"], batch["sparse_depth_masks_2"]])
+        t12, r12, t21, r21, k = (batch[name] for name in ("translations_1_wrt_2", "rotations_1_wrt_2", "translations_2_wrt_1",
+                                                          "rotations_2_wrt_1", "intrinsics"))
+        flows_1 = mask_mul(flow_layer([scaled_1, b, t12, r12, k]), b)
+        flows_2 = mask_mul(flow_layer([scaled_2, b, t21, r21, k]), b)
+        warped_21, inter_1 = warping([scaled_1, scaled_2, b, t12, r12, k])
+        warped_12, inter_2 = warping([scaled_2, scaled_1, b, t21, r21, k])
+        out = display.validation_panels(colors_1, colors_2, b, scaled_1, scaled_2, batch["sparse_depths_1"], batch["sparse_depths_2"],
+                                        batch["sparse_depth_masks_1"], batch["sparse_depth_masks_2"], warped_21, warped_12, sparse_flows_1,
+                                        sparse_flows_2, flows_1, flows_2, k, epsilon=eps, point_cloud_downsampling=point_cloud_downsampling)
+        out["offsets"] = out["offsets"].cpu().tolist()          # the batch's one read back (it waits for the stream)
+    out.update({"colors_1": colors_1, "colors_2": colors_2, "sparse_flows_1": sparse_flows_1, "sparse_flows_2": sparse_flows_2,
+                "predictions_1": pred_1, "predictions_2": pred_2, "scaled_depths_1": scaled_1, "scaled_depths_2": scaled_2,
+                "flows_1": flows_1, "flows_2": flows_2, "warped_depths_2_to_1": warped_21, "warped_depths_1_to_2": warped_12,
+                "intersect_masks_1": inter_1, "intersect_masks_2": inter_2})
+    return out
+
+
+def _write_validation_batch(ready, index, panel, points, offsets, samples, out_dir, ply_text):
+    """One batch's files, on a writer thread, once the device-to-host copies have landed."""
+    ready.synchronize()
+    if points is not None:
+        for i in samples:
+            name = "{}.ply".format(index) if i == 0 else "{}_{}.ply".format(index, i)
+            utils.write_point_cloud(os.path.join(out_dir, name), points[offsets[i]:offsets[i + 1]].numpy(), text=ply_text)
+    if panel is not None:
+        utils.write_png(os.path.join(out_dir, "{}.png".format(index)), panel.numpy()[:, :, ::-1])          # write_png takes B, G, R
+
+
+def run_validation_phase(model, batches, out_dir, write_png=True, write_ply=True, ply_text=True, all_samples=False, writer=None, step=0,
+                         writers=4):
+    """evaluate.py:167-274: every batch of ``batches`` (a dataset.TrainingBatches(transform=None, shuffle=False)) through
+    validation_outputs, then ``<batch>.png`` (the 12-section R, G, B panel) and ``<batch>.ply`` (the point cloud of sample 0's frame 1,
+    as the reference writes it; all_samples=True adds ``<batch>_<i>.ply`` for the samples i >= 1) in ``out_dir``, on run_test_phase's
+    writer pool.  writer: any object with tensorboardX's add_image; it receives stack_and_display's call (utils.py:894-896) per batch.
+    The per-pair measures stay on the device and are read once at the end.  Returns a dictionary: pairs (the number of frame pairs),
+    metrics (the (pairs, 2, 4) float32 array of [abs rel, sigma 1, 2, 3] per pair and frame), mean_metrics ((2, 4) float64: per frame
+    the means over the pairs whose four numbers are finite; NaN where there is none) and non_finite (the number of (pair, frame) rows
+    left out of them: pairs without sparse points in that frame)."""
+    out_dir = str(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    pending = deque()
+    collected = []
+    with ThreadPoolExecutor(max(1, int(writers))) as pool:
+        try:
+            for index, batch in enumerate(batches):
+                out = validation_outputs(model, batch, is_hsv=getattr(batches, "is_hsv", False))
+                collected.append(out["metrics"])
+                if writer is not None:
+                    display.stack_and_display("validation", VALIDATION_TITLE, step, writer, out["panel"])
+                if not (write_png or write_ply):
+                    continue
+                offsets = out["offsets"]
+                samples = range(len(offsets) - 1) if all_samples else range(1)
+                panel = out["panel"].to("cpu", non_blocking=True) if write_png else None
+                points = out["points"][:offsets[samples[-1] + 1]].to("cpu", non_blocking=True) if write_ply else None
+                ready = torch.cuda.Event()
+                ready.record()
+                pending.append(pool.submit(_write_validation_batch, ready, index, panel, points, offsets, samples, out_dir, ply_text))
+                while len(pending) > 2 * max(1, int(writers)):          # bound the host copies in flight
+                    pending.popleft().result()
+        finally:
+            while pending:
+                pending.popleft().result()
+    if collected:
+        metrics = torch.cat(collected, dim=0).cpu().numpy()          # the pass's one read of the measures
+    else:
+        metrics = np.zeros((0, 2, 4), np.float32)
+    finite = np.all(np.isfinite(metrics), axis=2)
+    means = np.full((2, 4), np.nan, np.float64)
+    for side in range(2):
+        if finite[:, side].any():
+            means[side] = metrics[finite[:, side], side].astype(np.float64).mean(axis=0)
+    return {"pairs": int(metrics.shape[0]), "metrics": metrics, "mean_metrics": means, "non_finite": int((~finite).sum())}

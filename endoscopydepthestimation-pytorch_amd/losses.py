@@ -2,7 +2,8 @@
 (SparseMaskedL1Loss, NormalizedDistanceLoss -- train.py:210-211) plus ScaleInvariantLoss, on HIP
 kernels.  ``forward(x)`` takes ONE list argument, as in the reference (losses.py:22-23, 62-63,
 122-123).  Per-sample sums are reduced with wave shuffles + one fp64 atomic per block; the batch
-mean happens in a one-wave finalize kernel.
+mean happens in a one-wave finalize kernel.  AbsRelError and Threshold (losses.py:189-227, the error measures against the sparse
+reconstruction that evaluate.validation_outputs reports) are forward only: one launch of endo_depth_metrics, no atomics.
 """
 
 import torch
@@ -141,6 +142,49 @@ class ScaleInvariantLoss(nn.Module):
 
 
 _consistency_ws = {}
+
+
+def depth_metrics(scaled_depth_maps, sparse_depth_maps, sparse_depth_masks, eps=1.0e-8):
+    """endo_depth_metrics on (N, 1, H, W) device tensors: the (N, 4) float32 tensor of [abs rel, sigma 1, sigma 2, sigma 3] per sample,
+    without a graph.  A sample whose mask is empty gives NaN in all four, as the reference's 0 / 0 does."""
+    lib = _lib.load()
+    depth = _lib.dev_f32(scaled_depth_maps.detach(), "scaled depth maps")
+    sparse = _lib.dev_f32(sparse_depth_maps.detach(), "sparse depth maps")
+    masks = _lib.dev_f32(sparse_depth_masks.detach(), "sparse depth masks")
+    if depth.dim() != 4 or depth.shape[1] != 1 or sparse.shape != depth.shape or masks.shape != depth.shape:
+        raise ValueError("depth metrics need three (N, 1, H, W) tensors")
+    n, _, h, w = (int(v) for v in depth.shape)
+    with torch.cuda.device(depth.device):
+        out = torch.empty((n, 4), dtype=torch.float32, device=depth.device)
+        _lib.check(lib.endo_depth_metrics(_lib.ptr(depth), _lib.ptr(sparse), _lib.ptr(masks), n, h, w, float(eps), _lib.ptr(out),
+                                          _lib.stream()), "endo_depth_metrics")
+    return out
+
+
+class AbsRelError(nn.Module):
+    """reference losses.py:189-199: the per-sample (N,) mean of |d - s| / (eps + s) over the sparse points.  Forward only."""
+
+    def __init__(self, eps=1.0e-8):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        scaled_depth_maps, sparse_depth_maps, sparse_depth_masks = x
+        return depth_metrics(scaled_depth_maps, sparse_depth_maps, sparse_depth_masks, self.eps)[:, 0].contiguous()
+
+
+class Threshold(nn.Module):
+    """reference losses.py:202-227: [sigma_1, sigma_2, sigma_3], each the per-sample (N,) share of sparse points whose
+    max(d / s, s / d) is below 1.25, 1.25^2, 1.25^3.  Forward only."""
+
+    def __init__(self, eps=1.0e-8):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        scaled_depth_maps, sparse_depth_maps, sparse_depth_masks = x
+        out = depth_metrics(scaled_depth_maps, sparse_depth_maps, sparse_depth_masks, self.eps)
+        return [out[:, 1].contiguous(), out[:, 2].contiguous(), out[:, 3].contiguous()]
 
 
 def warp_consistency(depth_maps_1, depth_maps_2, img_masks, translations_1_wrt_2, rotations_1_wrt_2, translations_2_wrt_1,

@@ -28,15 +28,17 @@
  *   2. The contents of a workspace or output buffer ON ENTRY are ignored: whatever a call reads from one, it has written itself
  *      earlier in the same call.  NaN, stale results of another shape, or zeros give the same result.
  *   SCRATCH (no meaning once the call's work has passed `stream`): gradws, the 16-bit families' `ws`, winner_scratch, row_offsets, and
- *   the workspaces of endo_warp_consistency, endo_jpeg_decode_crop, endo_augment, endo_evaluate and endo_display.
+ *   the workspaces of endo_warp_consistency, endo_jpeg_decode_crop, endo_augment, endo_evaluate, endo_display and
+ *   endo_evaluate_validation.
  *   STATE, i.e. written by one call and read by a later one, so the caller must leave it untouched in between:
  *     - `tape` (both network families): written by *_fwd, read (never written) by the matching *_bwd;
  *     - `stats` of the geometry / loss modules, forward to backward (above);
  *     - the workspace of endo_loss_head: on return it holds the six planes endo_loss_head_planes describes, which endo_display
  *       reads; scratch again from the next endo_loss_head on it;
  *     - `grads` (ACCUMULATED into), `params`, `momentum`, `bn_running`, and the means / history of endo_validation_accumulate.
- *   An output whose documented extent depends on the data (the point rows of endo_point_cloud / endo_evaluate: *count_out,
- *   frame_offsets) is written up to that extent only; rows behind it keep whatever they held.
+ *   An output whose documented extent depends on the data (the point rows of endo_point_cloud / endo_evaluate /
+ *   endo_evaluate_validation: *count_out, frame_offsets, offsets) is written up to that extent only; rows behind it keep whatever
+ *   they held.
  */
 #ifndef ENDO_HIP_H
 #define ENDO_HIP_H
@@ -62,7 +64,9 @@ extern "C" {
  * 6: round 6 -- adds endo_warp_consistency_bytes, the option ENDO_OPT_TD_PERSIST and the value ENDO_OPT_WINO_DGRAD = 3; since then
  * (unchanged by additions) endo_augment, endo_augment_workspace_bytes, endo_augment_frame_bytes and the endo_augment_frame
  * record; then endo_evaluate and endo_evaluate_workspace_bytes; then endo_loss_head_planes, endo_display, endo_display_workspace_bytes,
- * endo_display_panel_shape and endo_validation_accumulate -- entry points only, no existing signature changes. */
+ * endo_display_panel_shape and endo_validation_accumulate; then endo_depth_metrics, endo_evaluate_validation,
+ * endo_evaluate_validation_workspace_bytes and endo_evaluate_validation_panel_shape -- entry points only, no existing signature
+ * changes: additive, so the version stays 6. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -534,6 +538,62 @@ int endo_display(const float* colors_1, const float* colors_2, const float* dept
  * history: null, or fp64 [>= batch_index + 1][3] whose row batch_index receives the means after the update (train.py:481-483 logs
  * them per batch).  One single-thread launch. */
 int endo_validation_accumulate(const float* losses, int batch_index, double* means, double* history, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Depth error measures against the sparse reconstruction -- reference losses.py:189-227 (AbsRelError.forward, Threshold.forward; the
+ * reference defines them and calls them nowhere).  scaled_depths, sparse_depths, sparse_masks [N][1][H][W] fp32; out [N][4] fp32:
+ * per sample the absolute relative error and sigma 1, 2, 3 (the share of masked pixels whose ratio is below 1.25, 1.25^2, 1.25^3).
+ * Per-pixel terms with torch's float32 operations and IEEE division:
+ *   abs rel     (m |d - s|) / (eps + s)
+ *   threshold   m max(d m / (eps + s), s / (eps + d m)) + (1 - m) 10    (torch.max: a NaN side is kept; 0 * inf = NaN counts nowhere)
+ * The abs-rel terms and the mask are summed in fp64 and rounded once, the counts are integers, the four quotients are float32.  An
+ * empty mask gives NaN in all four (the reference's 0 / 0).  One launch, one block per sample; no workspace: nothing but out[N][4] is
+ * written, and all of it.  N <= 65535, N * H * W < 2^31.  ENDO_E_BADARG for null pointers or bad sizes. */
+int endo_depth_metrics(const float* scaled_depths, const float* sparse_depths, const float* sparse_masks, int n, int h, int w, float eps,
+                       float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Validation-phase outputs of a batch of pairs -- reference evaluate.py:201-274: the 12-section picture of
+ * utils.display_color_sparse_depth_dense_depth_warped_depth_sparse_flow_dense_flow (both frames) and stack_and_display
+ * (utils.py:894-954, over torchvision 0.7-era make_grid; color_reverse = True, rgb_mode = "rgb"), the point cloud of
+ * utils.point_cloud_from_depth (utils.py:825-852), and the measures of endo_depth_metrics for both frames.  Inputs, fp32:
+ *   colors_k [N][3][H][W] the masked network input (evaluate.py:189-190); boundaries [N][1][H][W]; depths_k [N][1][H][W] the scaled
+ *   depth, unmasked; sparse_depths_k, sparse_masks_k [N][1][H][W]; warped_2_to_1 / warped_1_to_2 [N][1][H][W] (evaluate.py:218-223);
+ *   sparse_flows_k, flows_k [N][2][H][W] the masked sparse flows and flows from depth (evaluate.py:191-192, 215-216); intrinsics
+ *   [N][3][3].
+ * Writes
+ *   panel    [12 rows_per_section][cols][3] uint8 R, G, B (endo_evaluate_validation_panel_shape): c1 sd1 d1 wd1 sf1 df1 c2 sd2 d2 wd2
+ *            sf2 df2 top to bottom, each make_grid(nrow = 8, padding = 2, pad_value = 0) of the batch (N = 1: the frame itself) -- the
+ *            bytes of evaluate.py:269-270's np.uint8(image_display * 255) and of the writer's add_image:
+ *     c        trunc(fl(fl(fl(0.5 c + 0.5) b) 255)): masked pixels are 0
+ *     sd d wd  COLORMAP_JET[u8(255 norm(x))], B, G, R -> R, G, B, x = sparse depth, b * depth, warped depth; norm(x) =
+ *              (clamp(x, min, max) - min) / fl32(max - min + 1e-5) with ONE (min, max) per frame side: of b * depth over the whole
+ *              batch (utils.py:921-922); padding: JET entry 0
+ *     df sf    draw_flow(flows_k), then draw_flow(sparse_flows_k, max_v of df) (utils.py:942-943: the dense flows set the scale,
+ *              the other way round from endo_display); HSV as endo_display's, padding black, max_v = 0: V = 0
+ *   metrics  [N][2][4] fp32: endo_depth_metrics' four numbers of (depths_k, sparse_depths_k, sparse_masks_k), the same bits
+ *   points   capacity N * H * W rows of (x, y, z, r, g, b) fp32: frame 1 of every pair, every pixel with h % downsampling == 0,
+ *            w % downsampling == 0 and boundary > 0.5, pair-major, row-major inside a frame: endo_point_cloud's rows of (depths_1
+ *            UNMASKED, u8(255 (0.5 c + 0.5)) of colors_1, boundaries, K) bit for bit
+ *   offsets  [N + 1] int64: pair f's rows are [offsets[f], offsets[f + 1])
+ * Deviations from the reference: it forms the point colours with cv2.COLOR_HSV2BGR_FULL whatever the colour space
+ * (evaluate.py:202-203), which scrambles RGB input; here they are the frame's own R, G, B, as the test phase takes them
+ * (evaluate.py:329-334).  is_hsv = 1 (the float COLOR_HSV2RGB_FULL path of the colour section) is not implemented: ENDO_E_BADARG.
+ * numpy's / torch's float32 roundings throughout; JET and the HSV conversion are restated (PARITY UNPINNED against cv2).
+ * Three launches whatever N.  Every H, W >= 1 with N <= 65535 and N * H * W < 2^31 (one section's rows and columns must be 32-bit
+ * numbers; endo_evaluate_validation_panel_shape also needs 12 rows_per_section to be one).  workspace: 16-byte aligned,
+ * endo_evaluate_validation_workspace_bytes(n, h, w) bytes (-1 for bad sizes), scratch: contents on entry ignored, nothing outside
+ * those bytes written; panel, metrics and offsets are written in full, `points` up to offsets[N] rows.  ENDO_E_BADARG for null
+ * pointers, bad sizes, is_hsv != 0, downsampling < 1, a misaligned or a short workspace. */
+int64_t endo_evaluate_validation_workspace_bytes(int n, int h, int w);
+int endo_evaluate_validation_panel_shape(int n, int h, int w, int* rows, int* cols);
+int endo_evaluate_validation(const float* colors_1, const float* colors_2, const float* boundaries, const float* depths_1,
+                             const float* depths_2, const float* sparse_depths_1, const float* sparse_depths_2,
+                             const float* sparse_masks_1, const float* sparse_masks_2, const float* warped_2_to_1,
+                             const float* warped_1_to_2, const float* sparse_flows_1, const float* sparse_flows_2, const float* flows_1,
+                             const float* flows_2, const float* intrinsics, int n, int h, int w, float eps, int is_hsv,
+                             int point_cloud_downsampling, uint8_t* panel, float* metrics, float* points, int64_t* offsets,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* live per-kernel-family timing for bench.py's roofline line: HIP events recorded on the launch
  * stream around every entry of the selected families.  family_mask: bit f enables family f

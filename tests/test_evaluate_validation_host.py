@@ -1,0 +1,70 @@
+"""CPU-only checks of evaluate.py's validation phase: the numpy restatement of AbsRelError and Threshold (tests/evaluate_validation_
+restate.py) against the outputs the reference's own classes gave (tests/golden/depth_metrics_4x16x24.npz, written by tests/golden/
+make_metrics_golden.py), the panel's shape, and the new entry points in the library, the header and the ctypes table."""
+
+import ctypes
+import importlib
+import os
+
+import numpy as np
+
+import evaluate_validation_restate as evr
+
+ea = importlib.import_module("endoscopydepthestimation-pytorch_amd")
+
+
+def test_restated_metrics_equal_the_reference(golden):
+    """sigma 1, 2, 3 exactly (integer counts over an integer mask sum, one float32 division each), the same NaN pattern (sample 2's mask
+    is empty), AbsRel within 1e-5 relative: torch's pairwise float32 sum of at most 384 terms is within about 1e-6 of the exact sum the
+    restatement rounds once, and 1e-5 is the project's float32 bound."""
+    g = golden("depth_metrics_4x16x24.npz")
+    depths, sparse, masks, eps = g["depths"], g["sparse"], g["masks"], float(g["eps"])
+    assert depths.shape == (4, 1, 16, 24) and masks[2].sum() == 0 and np.all(sparse[masks == 0] == 0)
+    sigmas = evr.threshold(depths, sparse, masks, eps)
+    for k, got in enumerate(sigmas):
+        want = g["sigma_%d" % (k + 1)]
+        assert got.dtype == np.float32 and np.array_equal(np.isnan(got), np.isnan(want)) and np.isnan(want).tolist() == [False, False, True, False]
+        assert np.array_equal(got[~np.isnan(want)], want[~np.isnan(want)]), (k, got, want)
+    # the three points of sample 1 that sit on 1.25, 1.25^2, 1.25^3 count for the next threshold only (strict <)
+    count = float(masks[1].sum())
+    on = [(1, 1), (5, 7), (9, 20)]
+    assert [float(depths[1, 0, y, x] / sparse[1, 0, y, x]) for y, x in on] == [1.25, 1.25 ** 2, 1.25 ** 3]
+    moved = depths.copy()
+    for y, x in on:
+        moved[1, 0, y, x] = np.nextafter(moved[1, 0, y, x], np.float32(0))
+    below = evr.threshold(moved, sparse, masks, eps)
+    assert [round(float(below[k][1] - sigmas[k][1]) * count) for k in range(3)] == [1, 1, 1]
+    got, want = evr.abs_rel_error(depths, sparse, masks, eps), g["abs_rel"]
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want)
+    assert np.all(np.abs(got[ok] - want[ok]) <= 1e-5 * np.abs(want[ok])), (got, want)
+    assert evr.metrics(depths, sparse, masks, eps).shape == (4, 4)
+
+
+def test_validation_panel_shape():
+    for n in (1, 8, 9):
+        gh, gw = ea.display.grid_shape(n, 64, 96)
+        assert ea.display.validation_panel_shape(n, 64, 96) == (12 * gh, gw, 3)
+    assert ea.display.validation_panel_shape(1, 64, 96) == (768, 96, 3)
+    assert ea.display.validation_panel_shape(9, 64, 96) == (12 * (2 * 66 + 2), 8 * 98 + 2, 3)
+
+
+def test_library_exports_the_validation_entries():
+    if not os.path.exists(ea._lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    raw = ctypes.CDLL(ea._lib.LIB_PATH)
+    names = ("endo_depth_metrics", "endo_evaluate_validation", "endo_evaluate_validation_workspace_bytes", "endo_evaluate_validation_panel_shape")
+    for name in names:
+        assert hasattr(raw, name) and name in ea._lib.SIGNATURES, name
+    lib = ea._lib.load()
+    assert lib.endo_abi_version() == 6          # additive: the version stays
+    # argument validation happens before any device work
+    assert lib.endo_depth_metrics(None, None, None, 1, 2, 2, 1e-8, None, None) == -1
+    assert lib.endo_evaluate_validation_workspace_bytes(0, 8, 8) == -1 and lib.endo_evaluate_validation_workspace_bytes(65536, 1, 1) == -1
+    assert lib.endo_evaluate_validation_workspace_bytes(65535, 32767, 1) > 0 and lib.endo_evaluate_validation_workspace_bytes(1, 1, 1) > 0
+    rows, cols = ctypes.c_int(), ctypes.c_int()
+    assert lib.endo_evaluate_validation_panel_shape(9, 64, 96, ctypes.byref(rows), ctypes.byref(cols)) == 0
+    assert (rows.value, cols.value, 3) == ea.display.validation_panel_shape(9, 64, 96)
+    assert lib.endo_evaluate_validation_panel_shape(0, 64, 96, ctypes.byref(rows), ctypes.byref(cols)) == -1
+    assert {"AbsRelError", "Threshold"} <= set(dir(ea.losses)) and callable(ea.evaluate.run_validation_phase)
