@@ -84,12 +84,13 @@ struct DgradBlockGeom {
 
 // GP: 16-channel groups per step.  Two groups share every A (dY) fragment read and halve the barriers per MFMA, but
 // measured (tools/conv_bench, level 0 / 1 / 2 shapes) GP = 2 is within +-3 % of GP = 1 and costs 80 more VGPRs;
-// the library instantiates GP = 1.
+// the library instantiates GP = 1.  (GP stays a parameter: with the [GP] arrays and loops written out for one group the compiler orders
+// the kernel's address arithmetic differently, and this kernel's instructions are not changed without a measurement.)
 // EXP: diagnostic bit mask for tools/conv_bench (0 in the library): 1 = no x / dbuf loads, 2 = no stores,
 // 4 = weight slice loaded once, 8 = no BN-sum reduction, 16 = no dY tile load, 32 = epilogue reduced to an add
 // BF: 1 = bf16 MFMA operands (ENDO_OPT_MFMA_BF16): the three row taps of a map and column tap in one v_mfma_f32_16x16x16_bf16
 // (conv_dma_kernels.h, BF), fp32 accumulation and epilogue
-template <int NL, int WX, int R, int GP, int EXP = 0, int PIPE = 1, int VEC = 1, int BF = 0>
+template <int NL, int WX, int R, int GP, int EXP = 0, int VEC = 1, int BF = 0>
 __global__ void __launch_bounds__(kConvThreads) dgrad_block_kernel(const DgradBlockParams p0) {
     using G = DgradBlockGeom<NL, WX, R, GP, VEC>;
     const int grp = p0.group_n > 0 ? blockIdx.z / p0.group_n : 0;
@@ -286,81 +287,55 @@ __global__ void __launch_bounds__(kConvThreads) dgrad_block_kernel(const DgradBl
 #pragma unroll
             for (int r = 0; r < R; ++r) acc[a][r] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* wb = s_w + buf * G::kWG;
-        if constexpr (PIPE) {
-            // fragments of map quad q+1 are requested before the 27 GP R MFMAs of quad q are issued, so the LDS
-            // latency hides under this wave's own MFMAs (left to itself the compiler reads each B value right
-            // before the 3 MFMAs that use it and stalls on lgkmcnt(0) every ~100 cycles)
-            float av[2][3][R + 2], bw[2][9][GP];
-            auto load_quad = [&](int quad, int set) {
-                const float* a_base = s_g + (l * 12 + quad * 4 + lk) * G::kCS + wy * G::kCols + wx + li + G::kColOff;
-                const float* b_base = wb + (quad * 4 + lk) * G::kNB + li;
-#pragma unroll
-                for (int r = 0; r < R + 2; ++r)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) av[set][dx][r] = a_base[r * G::kCols + dx];
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                    for (int a = 0; a < GP; ++a) bw[set][tap][a] = b_base[tap * 12 * G::kNB + a * 16];
-            };
-            load_quad(0, 0);
-#pragma unroll
-            for (int quad = 0; quad < 3; ++quad) {
-                const int set = quad & 1;
-                if (quad + 1 < 3) load_quad(quad + 1, set ^ 1);
-                __builtin_amdgcn_sched_barrier(0);        // keep the reads above, the MFMAs below
-                if constexpr (BF != 0) {
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        bf16x4_bits ap[R];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) ap[r] = pack_bf16x4(av[set][dx][r], av[set][dx][r + 1], av[set][dx][r + 2], 0.f);
-#pragma unroll
-                        for (int a = 0; a < GP; ++a)
-                            if (a == 0 || second) {
-                                const bf16x4_bits bp = pack_bf16x4(bw[set][dx][a], bw[set][3 + dx][a], bw[set][6 + dx][a], 0.f);
-#pragma unroll
-                                for (int r = 0; r < R; ++r) acc[a][r] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ap[r], bp, acc[a][r], 0, 0, 0);
-                            }
-                    }
-                } else
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                        for (int a = 0; a < GP; ++a)
-                            if (a == 0 || second) {
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-                                    acc[a][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[set][dx][r + dy], bw[set][dy * 3 + dx][a], acc[a][r], 0, 0, 0);
-                            }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
+        // fragments of map quad q+1 are requested before the 27 GP R MFMAs of quad q are issued, so the LDS
+        // latency hides under this wave's own MFMAs (left to itself the compiler reads each B value right
+        // before the 3 MFMAs that use it and stalls on lgkmcnt(0) every ~100 cycles)
+        float av[2][3][R + 2], bw[2][9][GP];
+        auto load_quad = [&](int quad, int set) {
             const float* a_base = s_g + (l * 12 + quad * 4 + lk) * G::kCS + wy * G::kCols + wx + li + G::kColOff;
             const float* b_base = wb + (quad * 4 + lk) * G::kNB + li;
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                float av[R + 2];
+            for (int r = 0; r < R + 2; ++r)
 #pragma unroll
-                for (int r = 0; r < R + 2; ++r) av[r] = a_base[r * G::kCols + dx];
+                for (int dx = 0; dx < 3; ++dx) av[set][dx][r] = a_base[r * G::kCols + dx];
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
+            for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-                    for (int a = 0; a < GP; ++a) {
+                for (int a = 0; a < GP; ++a) bw[set][tap][a] = b_base[tap * 12 * G::kNB + a * 16];
+        };
+        load_quad(0, 0);
+#pragma unroll
+        for (int quad = 0; quad < 3; ++quad) {
+            const int set = quad & 1;
+            if (quad + 1 < 3) load_quad(quad + 1, set ^ 1);
+            __builtin_amdgcn_sched_barrier(0);        // keep the reads above, the MFMAs below
+            if constexpr (BF != 0) {
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    bf16x4_bits ap[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) ap[r] = pack_bf16x4(av[set][dx][r], av[set][dx][r + 1], av[set][dx][r + 2], 0.f);
+#pragma unroll
+                    for (int a = 0; a < GP; ++a)
                         if (a == 0 || second) {
-                            const float b = b_base[(dy * 3 + dx) * 12 * G::kNB + a * 16];
+                            const bf16x4_bits bp = pack_bf16x4(bw[set][dx][a], bw[set][3 + dx][a], bw[set][6 + dx][a], 0.f);
+#pragma unroll
+                            for (int r = 0; r < R; ++r) acc[a][r] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ap[r], bp, acc[a][r], 0, 0, 0);
+                        }
+                }
+            } else
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int a = 0; a < GP; ++a)
+                        if (a == 0 || second) {
 #pragma unroll
                             for (int r = 0; r < R; ++r)
-                                acc[a][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[r + dy], b, acc[a][r], 0, 0, 0);
+                                acc[a][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[set][dx][r + dy], bw[set][dy * 3 + dx][a], acc[a][r], 0, 0, 0);
                         }
-                    }
-                }
-            }
-        }
+            __builtin_amdgcn_sched_barrier(0);
         }
         // ---- layer l's ReLU mask + BN backward, accumulated over the layers of the block ----
 #pragma unroll
@@ -420,7 +395,7 @@ __global__ void __launch_bounds__(kConvThreads) dgrad_block_kernel(const DgradBl
     if (po_gs >= 0) store_pending();
 }
 
-template <int NL, int WX, int R, int GP = 1, int EXP = 0, int PIPE = 1, int VEC = 1, int BF = 0>
+template <int NL, int WX, int R, int GP = 1, int EXP = 0, int VEC = 1, int BF = 0>
 inline int launch_dgrad_block(DgradBlockParams p, hipStream_t stream) {
     using G = DgradBlockGeom<NL, WX, R, GP, VEC>;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
@@ -431,7 +406,7 @@ inline int launch_dgrad_block(DgradBlockParams p, hipStream_t stream) {
     int ysplit = (768 + tiles - 1) / tiles;
     if (ysplit > gsets) ysplit = gsets;
     if (ysplit < 1) ysplit = 1;
-    return launch_dyn(dgrad_block_kernel<NL, WX, R, GP, EXP, PIPE, VEC, BF>, dim3(p.tiles_x * tiles_y, ysplit, p.n), kConvThreads, G::kBytes, stream, p);
+    return launch_dyn(dgrad_block_kernel<NL, WX, R, GP, EXP, VEC, BF>, dim3(p.tiles_x * tiles_y, ysplit, p.n), kConvThreads, G::kBytes, stream, p);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -55,9 +55,7 @@ struct DgradWino3Geom {
 // p.w % 32 == 0, p.h % 8 == 0, p.count % 16 == 0, 32 <= p.count <= 192; u[l]: the layer's transformed weights (layout 1), group-major.
 // EXP: diagnostic bit mask for tools/wino_bench (0 in the library; timing only): 1 = no x / gradient loads, 2 = no stores,
 // 4 = no BN-sum atomics, 8 = no dY tile load, 32 = no MFMAs
-// OPT (in-job A/B, tools/wino_bench; 0 in the library): 16 = weight DMA issued at the END of the V phases with a counted wait (M phases
-// then carry no memory instruction), 32 = s_setprio 1 around the MFMAs of an M phase.  Both measured neutral to slightly slower.
-template <int NL, int EXP = 0, int OPT = 0>
+template <int NL, int EXP = 0>
 __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockParams p, const float* __restrict__ u0, const float* __restrict__ u1,
                                                              const float* __restrict__ u2, const float* __restrict__ u3) {
     using G = DgradWino3Geom<NL>;
@@ -231,7 +229,6 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             for (int i = 0; i < 16; ++i) acc[i] = f32x4{av[0][i >> 1][i & 1], av[1][i >> 1][i & 1], av[2][i >> 1][i & 1], av[0][i >> 1][i & 1]};
             return;
         }
-        if constexpr ((OPT & 32) != 0) __builtin_amdgcn_s_setprio(1);
         const float* ub = s_u + (wk * 2 + buf) * G::kU;
 #pragma unroll
         for (int quad = 0; quad < 3; ++quad) {
@@ -252,7 +249,6 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
                 }
             }
         }
-        if constexpr ((OPT & 32) != 0) __builtin_amdgcn_s_setprio(0);
     };
 
     // ---- E: output transform A^T M A (tiles 4 lk + e), layer l's ReLU mask + BN backward, accumulated over the layers;
@@ -312,14 +308,6 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             *reinterpret_cast<f32x2*>(red + 2 * li) = f32x2{s1, s2};
         }
     };
-    // closing wait of a V phase that has just issued the 3 DMA instructions of a later weight slice: everything older has landed
-    // (vector memory reads retire in order; the parked stores were issued at the START of the phase, ahead of every load)
-    auto phase_end_v3 = [&]() {
-        __builtin_amdgcn_s_waitcnt(0x0073);          // vmcnt(3) lgkmcnt(0)
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
     // a phase ends at a block barrier; the two workers run one phase apart (worker 1 starts one barrier late, worker 0 ends one late)
     auto phase_end_v = [&]() {
         // the builtin, not inline assembly: the compiler's own wait-count bookkeeping sees it and adds no second vmcnt(0) where
@@ -343,12 +331,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
     __syncthreads();
     if (wk == 1) __builtin_amdgcn_s_barrier();          // the skew
     transform(0);
-    if constexpr ((OPT & 16) != 0) {
-        issue_weights(g_first, 1, 1);
-        phase_end_v3();
-    } else {
-        phase_end_v();
-    }
+    phase_end_v();
 
     int slot = 0;
     for (int gi = 0; gi < nfull; ++gi) {
@@ -361,16 +344,12 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
             // ---------------- M(gq, l): parked stores, next weight slice, 48 MFMAs ----------------
-            constexpr bool kLate = (OPT & 16) != 0;          // weight DMA at the end of the V phases, counted wait
-            if (!kLate && l == 0 && gi > 0) store_out(co - 32, dc);
-            if constexpr (!kLate) {
-                if (l + 1 < NL) issue_weights(gq, l + 1, (l + 1) & 1);
-                else if (has_next) issue_weights(g_next, l_next, 0);
-            }
+            if (l == 0 && gi > 0) store_out(co - 32, dc);
+            if (l + 1 < NL) issue_weights(gq, l + 1, (l + 1) & 1);
+            else if (has_next) issue_weights(g_next, l_next, 0);
             mfmas(l & 1);
             phase_end_m();
             // ---------------- V: loads, E(gq, l), T(next step) ----------------
-            if (kLate && l == 0 && gi > 0) store_out(co - 32, dc);
             float touched[4] = {0.f, 0.f, 0.f, 0.f};
             if (l == NL - 2) {
                 load_old(co, dc);
@@ -396,13 +375,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
                 }
             }
             asm volatile("" ::"v"(touched[0]), "v"(touched[1]), "v"(touched[2]), "v"(touched[3]));
-            if constexpr (kLate) {
-                if (l + 2 < NL) { issue_weights(gq, l + 2, l & 1); phase_end_v3(); }
-                else if (has_next && (l + 2 - NL < NL / 2 || gi + 1 < nfull)) { issue_weights(g_next, l_next + l + 2 - NL, l & 1); phase_end_v3(); }
-                else phase_end_v();
-            } else {
-                phase_end_v();
-            }
+            phase_end_v();
         }
         slot += NL;
     }
@@ -413,12 +386,10 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
 #pragma unroll
         for (int j = 0; j < NL / 2; ++j) {
             const int l = split_l0 + j;
-            constexpr bool kLate = (OPT & 16) != 0;
-            if (!kLate && j == 0 && nfull > 0) store_out((2 * (nfull - 1) + wk) * 16 + li, dc);
-            if (!kLate && j + 1 < NL / 2) issue_weights(gq, l + 1, (j + 1) & 1);
+            if (j == 0 && nfull > 0) store_out((2 * (nfull - 1) + wk) * 16 + li, dc);
+            if (j + 1 < NL / 2) issue_weights(gq, l + 1, (j + 1) & 1);
             mfmas(j & 1);
             phase_end_m();
-            if (kLate && j == 0 && nfull > 0) store_out((2 * (nfull - 1) + wk) * 16 + li, dc);
             if (j == 0 && wk == 0) load_old(co, dc);
             epilogue(gq, l, slot + j, read_bn(gq, l));
             __builtin_amdgcn_sched_barrier(0);
@@ -474,12 +445,12 @@ inline bool dgrad_wino3_ok(const DgradBlockParams& p) {
 }
 
 // u[l]: transformed weights of layer l of the block in layout 1 (group-major slices of kWinoDgradSlice floats)
-template <int NL, int EXP = 0, int OPT = 0>
+template <int NL, int EXP = 0>
 inline int launch_dgrad_wino3(DgradBlockParams p, const float* const (&u)[4], hipStream_t stream) {
     using G = DgradWino3Geom<NL>;
     p.tiles_x = p.w / G::kTileX;
     const int tiles_y = p.h / G::kTileY;
-    return launch_dyn(dgrad_wino3_kernel<NL, EXP, OPT>, dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream, p, u[0], u[1], u[2], u[3]);
+    return launch_dyn(dgrad_wino3_kernel<NL, EXP>, dim3(p.tiles_x * tiles_y, 1, p.n), G::kThreads, G::kBytes, stream, p, u[0], u[1], u[2], u[3]);
 }
 
 }  // namespace endo

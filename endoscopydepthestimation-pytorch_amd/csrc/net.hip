@@ -25,7 +25,6 @@
 #include "wgrad_taps_kernels.h"
 #include "wgrad1x1_kernels.h"
 #include "wgrad_nsplit_kernels.h"
-#include "wgrad_x3_kernels.h"
 #include "wgrad_f34_kernels.h"
 #include "wgrad_subpix_kernels.h"
 #include "wino_fwd_kernels.h"
@@ -590,7 +589,6 @@ enum class DenseFwd { Wino4, Wino2_32x16, Wino2_32x8, SplitK, Direct32x8, Direct
 struct FwdPlan {
     struct Dense {
         DenseFwd form;
-        int stages;                   // LDS stages of the F(2x2, 3x3) forms
         int ksplit;                   // K slices of SplitK
         bool chunk_weights;           // the layer's slot of the prepared weights holds the direct kernel's K-chunk order (WinoWeightTable::mode 1)
     } dense[kDense];
@@ -603,7 +601,7 @@ struct FwdPlan {
 
 enum class NewMap { Bf16, Persistent, Vec16, Dword };
 enum class BasePass { Block8, Block8Bf16, Wino3, Wino3Persistent, Wino8 };
-enum class DenseWgrad { F34, X3, NSplit, Taps, Direct };
+enum class DenseWgrad { F34, NSplit, Taps, Direct };
 enum class TdDgrad { Persistent, Runs128, Dma, Staged };
 enum class TuWgrad { Subpix, Taps, Direct };
 enum class TuDgrad { Subpix32x8, Subpix16x8, Subpix16x4, Plain };
@@ -622,7 +620,6 @@ struct BwdPlan {
     TuDgrad tu_dgrad[kLevels];
     int overlap;                      // ENDO_OPT_WGRAD_OVERLAP as set
     bool bf16_wgrad, bf16_dgrad;      // operands rounded to bf16 in the kernels that have such a form
-    int f34_blocks;                   // blocks of a dense F(3x3, 4x4) weight-gradient launch
     bool dgrad_weights;               // the Winograd-domain data-gradient weights are prepared
     // final convolution (FinalVirt) and first convolution
     bool use_virt;                    // the last up block forms the final convolution's data gradient where it first touches a channel ...
@@ -723,7 +720,6 @@ static void default_options(int (&opt)[ENDO_OPT_COUNT]) {
     opt[ENDO_OPT_WINO_MIN_TILES] = 1024;
     opt[ENDO_OPT_MFMA_BF16] = 0;
     opt[ENDO_OPT_WGRAD_OVERLAP] = 1;
-    opt[ENDO_OPT_MFMA_X3] = 0;
     opt[ENDO_OPT_WGRAD_F34] = 1;
     opt[ENDO_OPT_FINAL_VIRTUAL] = 1;
     opt[ENDO_OPT_TD_PERSIST] = 3;
@@ -806,7 +802,6 @@ static FwdPlan plan_fwd(const Ctx& c) {
             // Where the tile counts rule Winograd out the level's layers run a direct kernel and their weights are prepared in its K-chunk order.  (A
             // layer that a Winograd kernel's own shape check sends to the direct kernel reads the original weights.)
             d.chunk_weights = !pl.bf16 && !wino4_tiles && !wino2_tiles;
-            d.stages = mode == 4 ? 4 : (mode == 3 ? 3 : 2);          // in-job A/B: 2 LDS stages (default), 3, 4
             if (wino4_tiles && wino4_fwd_ok(dense_fwd_params(c, k, j, DenseFwd::Wino4))) {
                 d.form = DenseFwd::Wino4;
             } else if (wino2_tiles && wino_fwd_ok(dense_fwd_params(c, k, j, DenseFwd::Wino2_32x16))) {
@@ -858,9 +853,9 @@ static int dense_fwd(const Ctx& c, int b, int j) {
             if (c.fwd->fuse_final && b == kBlocks - 1 && j == kLayers - 1) { p.fin_w = c.params + table().final_.w + k.ic0; p.fin_out = c.tape + c.net->pre_off; }
             return launch_wino4_fwd(p, c.stream);
         case DenseFwd::Wino2_32x16:
-            return d.stages == 4 ? launch_wino_fwd<2, 4, 2, 4>(p, c.stream) : d.stages == 3 ? launch_wino_fwd<2, 4, 2, 3>(p, c.stream) : launch_wino_fwd<2, 4, 2, 2>(p, c.stream);
+            return launch_wino_fwd<2, 4, 2>(p, c.stream);
         case DenseFwd::Wino2_32x8:
-            return d.stages == 4 ? launch_wino_fwd<1, 4, 3, 4>(p, c.stream) : d.stages == 3 ? launch_wino_fwd<1, 4, 3, 3>(p, c.stream) : launch_wino_fwd<1, 4, 3, 2>(p, c.stream);
+            return launch_wino_fwd<1, 4, 3>(p, c.stream);
         case DenseFwd::SplitK: {
             float* partial = c.tape + c.net->partial_off;
             p.ksplit = d.ksplit;
@@ -1117,12 +1112,9 @@ static BwdPlan plan_bwd(const Ctx& c) {
     pl.overlap = opt[ENDO_OPT_WGRAD_OVERLAP];
     pl.bf16_wgrad = (bf16_mask(opt) & 1) != 0;
     pl.bf16_dgrad = (bf16_mask(opt) & 4) != 0;
-    // operands of a dense-layer weight gradient: rounded to bf16, else fp32 as three-term bf16 splits (ENDO_OPT_MFMA_X3 bit 0), else fp32 MFMA -- and
-    // only the last has a Winograd-domain form
-    const bool x3 = !pl.bf16_wgrad && (opt[ENDO_OPT_MFMA_X3] & 1);
-    const bool f34 = opt[ENDO_OPT_WGRAD_F34] && !pl.bf16_wgrad && !x3;
+    // operands of a dense-layer weight gradient: rounded to bf16, else fp32 MFMA -- and only the latter has a Winograd-domain form
+    const bool f34 = opt[ENDO_OPT_WGRAD_F34] && !pl.bf16_wgrad;
     const long f34_min_tiles = min_tiles / 4;          // from 256 tiles of 4 x 4 pixels: levels 0-4 of configs[1] (level 5 is 8 x 10)
-    pl.f34_blocks = opt[ENDO_OPT_WGRAD_F34] == 2 ? 256 : kF34Blocks;
     // the data-gradient weights are transformed whenever a Winograd form is selected, whether or not a block takes one this pass (at small sizes none does)
     pl.dgrad_weights = wino_dgrad != 0 && !pl.bf16_dgrad;
     for (int b = 0; b < kBlocks; ++b) {
@@ -1152,7 +1144,7 @@ static BwdPlan plan_bwd(const Ctx& c) {
         }
         for (int j = 0; j < kLayers; ++j) {
             const WgradParams p = dense_wgrad_params(c, k, j);
-            pl.wgrad[b * kLayers + j] = (f34 && wgrad_f34_ok(p, f34_min_tiles)) ? DenseWgrad::F34 : wgrad_nsplit_ok(p) ? (x3 ? DenseWgrad::X3 : DenseWgrad::NSplit)
+            pl.wgrad[b * kLayers + j] = (f34 && wgrad_f34_ok(p, f34_min_tiles)) ? DenseWgrad::F34 : wgrad_nsplit_ok(p) ? DenseWgrad::NSplit
                                       : wgrad_taps_ok(p) ? DenseWgrad::Taps : DenseWgrad::Direct;
         }
     }
@@ -1204,9 +1196,8 @@ static int dense_wgrad(const Ctx& c, int b, int j, F34ReduceBatch* batch = nullp
     float* scratch = c.gradws + c.net->wg_scratch_off;
     ProfScope prof(kProfWgradDense, c.stream, conv_flops(c.net, k.level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
     switch (c.bwd->wgrad[b * kLayers + j]) {
-        case DenseWgrad::F34: return launch_wgrad_f34(p, scratch + (batch ? slice : 0) * kF34ScratchFloats, c.stream, c.bwd->f34_blocks, batch);          // Winograd F(3x3, 4x4)
-        case DenseWgrad::X3: return launch_wgrad_x3(p, scratch, c.stream);          // fp32 products as bf16 splits (wgrad_x3_kernels.h)
-        case DenseWgrad::NSplit: return launch_wgrad_nsplit(p, scratch, c.stream, c.bwd->bf16_wgrad ? 1 : 0);
+        case DenseWgrad::F34: return launch_wgrad_f34(p, scratch + (batch ? slice : 0) * kF34ScratchFloats, c.stream, batch);          // Winograd F(3x3, 4x4)
+        case DenseWgrad::NSplit: return launch_wgrad_nsplit(p, scratch, c.stream, c.bwd->bf16_wgrad);
         case DenseWgrad::Taps: return c.bwd->bf16_wgrad ? launch_wgrad_taps<12, IN_BNRELU, 1>(p, c.stream) : launch_wgrad_taps<12, IN_BNRELU>(p, c.stream);
         case DenseWgrad::Direct: return launch_wgrad<3, 1, IN_BNRELU, DY_PLAIN>(p, c.stream);
     }
@@ -1249,9 +1240,9 @@ static int dense_bwd(const Ctx& c, int b, int j, int acc_from) {
 template <int NL>
 static int launch_newmap(NewMap form, const DgradBlockParams& p, hipStream_t stream) {
     switch (form) {
-        case NewMap::Bf16: return launch_dgrad_block<NL, 2, 3, 1, 0, 1, 4, 1>(p, stream);
+        case NewMap::Bf16: return launch_dgrad_block<NL, 2, 3, 1, 0, 4, 1>(p, stream);
         case NewMap::Persistent: return launch_dgrad_newmap<NL>(p, stream);          // dgrad_newmap_kernels.h
-        case NewMap::Vec16: return launch_dgrad_block<NL, 2, 3, 1, 0, 1, 4>(p, stream);
+        case NewMap::Vec16: return launch_dgrad_block<NL, 2, 3, 1, 0, 4>(p, stream);
         case NewMap::Dword: return launch_dgrad_block<NL, 2, 3>(p, stream);
     }
     return ENDO_E_BADARG;
@@ -1508,15 +1499,17 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
 
 extern "C" int endo_net_create(endo_net** out, int n, int h, int w) { return endo_net_create_grouped(out, n, h, w, 1); }
 
+static bool option_id_ok(int id) { return id >= 0 && id < ENDO_OPT_COUNT && id != 6; }          // 6: retired (include/endo_hip.h)
+
 extern "C" int endo_net_set_option(endo_net* net, int option_id, int value) {
-    if (!net || option_id < 0 || option_id >= ENDO_OPT_COUNT) return ENDO_E_BADARG;
+    if (!net || !option_id_ok(option_id)) return ENDO_E_BADARG;
     const int old = net->opt[option_id];
     net->opt[option_id] = value;
     return old;
 }
 
 extern "C" int endo_net_get_option(const endo_net* net, int option_id) {
-    if (!net || option_id < 0 || option_id >= ENDO_OPT_COUNT) return ENDO_E_BADARG;
+    if (!net || !option_id_ok(option_id)) return ENDO_E_BADARG;
     return net->opt[option_id];
 }
 

@@ -496,15 +496,14 @@ inline F34Plan wgrad_f34_plan(const WgradParams& p, int waves_per_xcd = kF34Wave
     return plan;
 }
 
-// blocks: 512 = two per CU (the default), 256 = one per CU (in-job A/B: leaves half of every CU's registers to the other stream's kernels)
 // batch: the launch leaves its partial sums in `scratch` and records what their reduction needs instead of reducing them
 // (launch_wgrad_f34_reduce_batch later, on the same stream; every launch of a batch needs its own scratch slice)
 template <int EXP = 0, bool RAW = false, bool PREP = false>
-inline int launch_wgrad_f34(const WgradParams& p, float* scratch, hipStream_t stream, int blocks = kF34Blocks, F34ReduceBatch* batch = nullptr) {
+inline int launch_wgrad_f34(const WgradParams& p, float* scratch, hipStream_t stream, F34ReduceBatch* batch = nullptr) {
     static_assert(!PREP || RAW, "the fused gradient preparation belongs to the first convolution's form");
-    const F34Plan plan = wgrad_f34_plan(p, blocks / 2, RAW);
+    const F34Plan plan = wgrad_f34_plan(p, kF34Blocks / 2, RAW);
     constexpr int lds = 4 * 2 * kF34Xs * 4;          // 67,584 bytes per block, two blocks per CU
-    ENDO_CHECK(launch_dyn(wgrad_f34_kernel<EXP, RAW, PREP>, blocks, kConvThreads, lds, stream, p, scratch, plan));
+    ENDO_CHECK(launch_dyn(wgrad_f34_kernel<EXP, RAW, PREP>, kF34Blocks, kConvThreads, lds, stream, p, scratch, plan));
     if (batch && !RAW && batch->count < 4) {
         const int k = batch->count++;
         batch->partial[k] = scratch; batch->dw[k] = p.dw; batch->plan[k] = plan; batch->cin[k] = p.cin;

@@ -36,8 +36,7 @@ constexpr int kNsUnits = 12 * kNsMap / 4;          // 360 float4
 
 // EXP: diagnostic bit mask for tools/conv_bench (0 in the library): 1 = no x loads, 2 = no dY DMA, 4 = no barrier,
 // 8 = fragment reads at consecutive (conflict-free, wrong) LDS addresses: what the 61 % bank conflicts of the real gathers cost
-// BF: 1 = bf16 MFMA operands (fp32 accumulation, fp32 memory): the 8 k-steps of a lane's two float4s become one v_mfma_f32_16x16x32_bf16;
-// 2 = fp32 operands as three bf16 terms each, six such MFMAs (fp32-accurate: common.h split_bf16x8)
+// BF: 1 = bf16 MFMA operands (fp32 accumulation, fp32 memory): the 8 k-steps of a lane's two float4s become one v_mfma_f32_16x16x32_bf16
 template <int NG, int EXP = 0, int BF = 0>
 __global__ void __launch_bounds__(kConvThreads) wgrad_nsplit_kernel(const WgradParams p, float* __restrict__ partial,
                                                                     int chunks_per_block) {
@@ -207,32 +206,7 @@ __global__ void __launch_bounds__(kConvThreads) wgrad_nsplit_kernel(const WgradP
         if (chunk + 2 < c_end) issue(buf == 0 ? 2 : buf - 1, slot_c);          // the buffer computed last iteration
 
         const float* s_dy = smem + buf * kNsBuf;
-        if constexpr (BF == 2) {
-            // fp32 products on the bf16 matrix cores (common.h, split_bf16x8): both operands split into three bf16 terms, six MFMAs per
-            // (row group, channel group) in place of the eight fp32 ones -- 96 instead of 256 matrix-pipe cycles, off the vector lanes
-            Bf16x8Split bq[NG];
-#pragma unroll
-            for (int g = 0; g < NG; ++g)
-                bq[g] = split_bf16x8(bv[g][0][0], bv[g][0][1], bv[g][0][2], bv[g][0][3], bv[g][1][0], bv[g][1][1], bv[g][1][2], bv[g][1][3]);
-#pragma unroll
-            for (int m = 0; m < kNsMG; ++m) {
-                const float* ap = s_dy + aoff[m];
-                const Bf16x8Split aq = split_bf16x8(ap[0], ap[1], ap[2], ap[3], ap[16], ap[17], ap[18], ap[19]);
-                // smallest products first; consecutive MFMAs go to different accumulators
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.lo, bq[g].hi, acc[g][m], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.hi, bq[g].lo, acc[g][m], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.mid, bq[g].mid, acc[g][m], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.mid, bq[g].hi, acc[g][m], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.hi, bq[g].mid, acc[g][m], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq.hi, bq[g].hi, acc[g][m], 0, 0, 0);
-            }
-        } else if constexpr (BF != 0) {
+        if constexpr (BF != 0) {
             // the lane's 8 pixels of the chunk (two float4s) are the k = 8 lk + i of ONE v_mfma_f32_16x16x32_bf16 per (row group, channel group)
             bf16x8_t bq[NG];
 #pragma unroll
@@ -242,8 +216,6 @@ __global__ void __launch_bounds__(kConvThreads) wgrad_nsplit_kernel(const WgradP
             for (int m = 0; m < kNsMG; ++m) {
                 const float* ap = s_dy + aoff[m];
                 const bf16x8_t aq = pack_bf16x8(ap[0], ap[1], ap[2], ap[3], ap[16], ap[17], ap[18], ap[19]);
-#pragma unroll
-                for (int rep = 0; rep < (BF == 3 ? 6 : 1); ++rep)          // BF = 3 (tools/x3_bench only): six MFMAs per pair on the ROUNDED operands -- what the matrix work of the x3 form costs without its splits
 #pragma unroll
                 for (int g = 0; g < NG; ++g)
                     if (g < ngw) acc[g][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, bq[g], acc[g][m], 0, 0, 0);
@@ -289,8 +261,7 @@ __global__ void __launch_bounds__(kConvThreads) wgrad_nsplit_kernel(const WgradP
 // grid (groups_total * 7, slices): the partial rows of row block (group, m) are one contiguous run of `blocks` x 256 floats; a
 // block of the grid adds its slice of them -- float4 per lane, four rows in flight per thread block pass, a fixed order per
 // (slice, element) -- and adds the slice's sum to the flat gradient (one atomic per element and slice).
-// ORDER: which (co, tap) a GEMM row m stands for -- 0: m = 9 co + tap (wgrad_nsplit_kernel), 1: m = 12 tap + co (wgrad_x3_kernel)
-template <int ORDER = 0>
+// GEMM row m stands for (co, tap) with m = 9 co + tap, as in wgrad_nsplit_kernel.
 __global__ void __launch_bounds__(256) wgrad_nsplit_reduce_kernel(const float* __restrict__ partial, int blocks, int groups_total, int cin,
                                                                   float* __restrict__ dw) {
     __shared__ f32x4 s_part[4][64];
@@ -318,15 +289,12 @@ __global__ void __launch_bounds__(256) wgrad_nsplit_reduce_kernel(const float* _
     const int m = 16 * m7 + 4 * (lane >> 4) + r;
     const int ci = 16 * group + (lane & 15);
     if (m < 108 && ci < cin) {
-        const int co = ORDER == 0 ? m / 9 : m % 12, tap = ORDER == 0 ? m - co * 9 : m / 12;
+        const int co = m / 9, tap = m - co * 9;
         atomicAdd(dw + (static_cast<int64_t>(co) * cin + ci) * 9 + tap, total);
     }
 }
 
 constexpr int kNsMinChunks = 2048;           // launches with fewer row chunks go to the tap-folded kernel
-#ifndef ENDO_NS_BLOCKS3
-#define ENDO_NS_BLOCKS3 512                  // blocks of an NG = 3 launch (in-job A/B: 512 = 2 per CU, 768 = 3 per CU)
-#endif
 constexpr int kNsMaxBlocks = 1024;
 constexpr int64_t kNsScratchFloats = static_cast<int64_t>(kNsMaxBlocks) * 12 * kNsMG * 256;   // blocks * groups <= 1024 * 12
 
@@ -341,35 +309,24 @@ inline bool wgrad_nsplit_ok(const WgradParams& p) {
 template <int NG, int EXP = 0, int BF = 0>
 inline int launch_wgrad_nsplit_ng(const WgradParams& p, float* scratch, int passes, hipStream_t stream) {
     const int chunks_total = ((p.w + kNsSeg - 1) / kNsSeg) * p.h * p.n;
-    int blocks = (NG == 3 ? ENDO_NS_BLOCKS3 : NG == 2 ? 768 : 1024) / passes;   // resident blocks per CU by register count: 2 / 3 / 4
+    int blocks = (NG == 3 ? 512 : NG == 2 ? 768 : 1024) / passes;   // resident blocks per CU by register count: 2 / 3 / 4 (NG = 3, in-job A/B: 512 = 2 per CU, 768 = 3 per CU)
     const int per = (chunks_total + blocks - 1) / blocks;
     blocks = (chunks_total + per - 1) / per;
     const int groups_total = (p.cin + 15) / 16;
     wgrad_nsplit_kernel<NG, EXP, BF><<<dim3(blocks, passes), kConvThreads, 0, stream>>>(p, scratch, per);
     ENDO_LAUNCH_CHECK();
-    wgrad_nsplit_reduce_kernel<0><<<dim3(groups_total * kNsMG, 16), 256, 0, stream>>>(scratch, blocks, groups_total, p.cin, p.dw);
+    wgrad_nsplit_reduce_kernel<<<dim3(groups_total * kNsMG, 16), 256, 0, stream>>>(scratch, blocks, groups_total, p.cin, p.dw);
     ENDO_LAUNCH_CHECK();
     return 0;
 }
 
-// scratch: kNsScratchFloats floats.  mfma_mode: 0 = fp32 matrix instructions, 1 = operands ROUNDED to bf16 (the mixed-precision mode of
-// DESIGN.md 4.10), 2 = fp32 operands split into three bf16 terms, six bf16 MFMAs (common.h: fp32-accurate products on the bf16 cores)
-inline int launch_wgrad_nsplit(const WgradParams& p, float* scratch, hipStream_t stream, int mfma_mode = 0) {
+// scratch: kNsScratchFloats floats.  bf16: operands ROUNDED to bf16 (the mixed-precision mode of DESIGN.md 4.10) instead of fp32 matrix instructions
+inline int launch_wgrad_nsplit(const WgradParams& p, float* scratch, hipStream_t stream, bool bf16 = false) {
     const int groups = (p.cin + 15) / 16;
     const int passes = (groups + 11) / 12;                       // at most 3 groups per wave
     const int per_pass = (groups + passes - 1) / passes;
     const int ng = (per_pass + 3) / 4;
-    if (mfma_mode == 2) {
-        if (ng <= 1) return launch_wgrad_nsplit_ng<1, 0, 2>(p, scratch, passes, stream);
-        if (ng == 2) return launch_wgrad_nsplit_ng<2, 0, 2>(p, scratch, passes, stream);
-        return launch_wgrad_nsplit_ng<3, 0, 2>(p, scratch, passes, stream);
-    }
-    if (mfma_mode == 3) {          // diagnostic (tools/x3_bench)
-        if (ng <= 1) return launch_wgrad_nsplit_ng<1, 0, 3>(p, scratch, passes, stream);
-        if (ng == 2) return launch_wgrad_nsplit_ng<2, 0, 3>(p, scratch, passes, stream);
-        return launch_wgrad_nsplit_ng<3, 0, 3>(p, scratch, passes, stream);
-    }
-    if (mfma_mode == 1) {
+    if (bf16) {
         if (ng <= 1) return launch_wgrad_nsplit_ng<1, 0, 1>(p, scratch, passes, stream);
         if (ng == 2) return launch_wgrad_nsplit_ng<2, 0, 1>(p, scratch, passes, stream);
         return launch_wgrad_nsplit_ng<3, 0, 1>(p, scratch, passes, stream);

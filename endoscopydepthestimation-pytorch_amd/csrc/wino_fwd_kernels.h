@@ -93,7 +93,12 @@ __global__ void __launch_bounds__(256) wino_fwd_weights_kernel(const WinoWeightT
     }
 }
 
-template <int R, int KC, int NS = 2>
+// LDS stages.  The Winograd form does 4/9 of the arithmetic on the same input bytes, so a K-chunk's MFMAs (~0.5 us) no
+// longer cover the latency of the next chunk's DMA (~1.5 us): with two stages the kernel ran at 42 % MFMA utilisation and
+// 2 TB/s, bound by neither.  NS stages keep NS - 1 chunks in flight (round 5, in-job A/B: 3 and 4 stages within +-0.2 % of 2).
+constexpr int kWinoFwdStages = 2;
+
+template <int R, int KC>
 struct WinoFwdGeom {
     static constexpr int kTileX = 32;
     static constexpr int kTileY = 8 * R;                      // 4 waves x R tile rows x 2 pixel rows
@@ -119,19 +124,18 @@ struct WinoFwdGeom {
     static_assert(kCS == 4 * kUnits, "a stage is one contiguous array of DMA units");
     static constexpr int kBuf = KC * kCS + KC * kWinoUStride;          // floats per stage
     static constexpr int kTail = 4 * 16 * 2;                  // statistics scratch: [4 waves][16][2]
-    static size_t bytes(int bn_cap) { return sizeof(float) * (NS * kBuf + 3 * bn_cap + kTail); }
+    static size_t bytes(int bn_cap) { return sizeof(float) * (kWinoFwdStages * kBuf + 3 * bn_cap + kTail); }
 };
 
 // p.wgt = this layer's U (kWinoUStride floats per input channel), p.cout <= 16, p.w % 4 == 0, 16-byte aligned planes.
-// NS: LDS stages.  The Winograd form does 4/9 of the arithmetic on the same input bytes, so a K-chunk's MFMAs (~0.5 us) no
-// longer cover the latency of the next chunk's DMA (~1.5 us): with two stages the kernel ran at 42 % MFMA utilisation and
-// 2 TB/s, bound by neither.  NS stages keep NS - 1 chunks in flight.
+// NS = kWinoFwdStages.
 // EXP: diagnostic bit mask (0 in the product; timing only, results are wrong): 1 = only the first NS - 1 chunks are DMA'd,
 // 2 = no BN + ReLU, 4 = no input transform, 8 = patch values are constants (no LDS reads), 16 = U values are constants,
 // 32 = no chunk barrier / DMA wait, 64 = no MFMAs
-template <int R, int KC, int MINW, int NS, int EXP = 0>
+template <int R, int KC, int MINW, int EXP = 0>
 __global__ void __launch_bounds__(kConvThreads, MINW) wino_fwd_kernel(const ConvParams p0) {
-    using G = WinoFwdGeom<R, KC, NS>;
+    using G = WinoFwdGeom<R, KC>;
+    constexpr int NS = kWinoFwdStages;
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_aux = smem + NS * G::kBuf;
@@ -370,13 +374,13 @@ inline bool wino_fwd_ok(const ConvParams& p) {
            p.cin % 4 == 0 && p.cin >= 8;          // whole K-chunks only (dense layers: cin = 48 + 12 j)
 }
 
-template <int R, int KC, int MINW, int NS, int EXP = 0>
+template <int R, int KC, int MINW, int EXP = 0>
 inline int launch_wino_fwd(ConvParams p, hipStream_t stream) {
-    using G = WinoFwdGeom<R, KC, NS>;
+    using G = WinoFwdGeom<R, KC>;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     p.bn_cap = ((p.cin + KC - 1) / KC * KC + 15) / 16 * 16;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
-    return launch_dyn(wino_fwd_kernel<R, KC, MINW, NS, EXP>, dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, G::bytes(p.bn_cap), stream, p);
+    return launch_dyn(wino_fwd_kernel<R, KC, MINW, EXP>, dim3(p.tiles_x * tiles_y, 1, p.n), kConvThreads, G::bytes(p.bn_cap), stream, p);
 }
 
 

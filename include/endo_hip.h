@@ -66,7 +66,8 @@ extern "C" {
  * record; then endo_evaluate and endo_evaluate_workspace_bytes; then endo_loss_head_planes, endo_display, endo_display_workspace_bytes,
  * endo_display_panel_shape and endo_validation_accumulate; then endo_depth_metrics, endo_evaluate_validation,
  * endo_evaluate_validation_workspace_bytes and endo_evaluate_validation_panel_shape -- entry points only, no existing signature
- * changes: additive, so the version stays 6. */
+ * changes: additive, so the version stays 6; then the option "MFMA X3" (id 6: fp32 products as three-term bf16 splits; retired and not reused) and the values
+ * ENDO_OPT_WINO_FWD = 3 / 4 and ENDO_OPT_WGRAD_F34 = 2 are removed -- no entry point and no signature changes. */
 #define ENDO_ABI_VERSION 6
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -247,11 +248,11 @@ int endo_net_groups(const endo_net* net);
 /* Kernel-form / precision options of ONE network handle (the reference's modules are independent objects, train.py:191,
  * 206-211: two models in one process, or a second thread configuring its own model, never change this one's arithmetic).
  * endo_net_create* sets the defaults below; nothing is read from the environment.  endo_net_set_option returns the previous
- * value, ENDO_E_BADARG for a null handle or an unknown option; it takes effect with the next endo_net_fwd / endo_net_bwd on
+ * value, ENDO_E_BADARG for a null handle or an unknown option (the retired id 6 included); it takes effect with the next endo_net_fwd / endo_net_bwd on
  * that handle (a forward and the backward that differentiates it must run under the same ENDO_OPT_MFMA_BF16 value).
  * Every setting but ENDO_OPT_MFMA_BF16 computes the same function up to fp32 summation order; tests use
  * ENDO_OPT_WINO_MIN_TILES = 1 to reach the Winograd kernels at small sizes.
- *   ENDO_OPT_WINO_FWD        dense-layer forward at the fine levels: 0 direct convolution, 1 Winograd F(2x2,3x3), 3 / 4 = with 3 / 4 LDS stages,
+ *   ENDO_OPT_WINO_FWD        dense-layer forward at the fine levels: 0 direct convolution, 1 (or any other non-zero value) Winograd F(2x2,3x3),
  *                            5 (default since round 5) = F(4x4,3x3) for the launches whose 64 x 16 blocks fill the chip (level 0 at 256 x 320; csrc/wino4_fwd_kernels.h)
  *                            and F(2x2,3x3) below: +3 % frame-pairs/s; the depth is 5e-6 of its maximum from fp64 instead of 1e-6, against the
  *                            1e-4 of the parity target
@@ -266,11 +267,6 @@ int endo_net_groups(const endo_net* net);
  *                            (v_mfma_f32_16x16x16_bf16; fp32 accumulation, fp32 tensors in memory) -- the mixed-precision mode of
  *                            BASELINE configs[2], with its own tolerance; default 0 = fp32 operands.
  *                            Development values 2 * mask (mask bit 0 weight gradients, 1 forward, 2 data gradients) select families
- *   ENDO_OPT_MFMA_X3         the SAME function as fp32 operands, on the bf16 matrix cores: a bit mask (1 weight gradients, 2 forward, 4 data
- *                            gradients) of the dense layers' kernel families that evaluate their fp32 products as three-term bf16 splits
- *                            (v = hi + mid + lo exactly; six exact bf16 products per fp32 product, fp32 accumulation; csrc/common.h
- *                            split_bf16x8) -- fp32 operands and fp32-level accuracy (held to the fp32 bounds by the parity tests) at
- *                            6 / 16 of the fp32 matrix instructions' issue time.  Ignored where ENDO_OPT_MFMA_BF16 selects rounded operands.
  *   ENDO_OPT_WGRAD_OVERLAP   endo_net_bwd runs the weight gradients on a side stream of its own, overlapped with the data-gradient
  *                            chain and joined before it returns: 1 (default) = forked behind every gradient preparation;
  *                            2 = in the fused dense blocks ONE fork per block, behind its last preparation (its four weight gradients
@@ -278,9 +274,8 @@ int endo_net_groups(const endo_net* net);
  *                            caller's stream (clean per-kernel timings)
  *   ENDO_OPT_WGRAD_F34       dense-layer weight gradient where the height is a multiple of 16 and the width of 4 (levels 0-4 at 256 x 320): 1 (default) = in the
  *                            Winograd domain, F(3x3, 4x4) -- 36 multiplications per 4 x 4 tile of the output gradient instead of 144,
- *                            fp32 throughout (csrc/wgrad_f34_kernels.h); 2 = the same with 256 instead of 512 blocks per dense-layer
- *                            launch (one instead of two per compute unit); 0 = the direct kernels.  Ignored where ENDO_OPT_MFMA_BF16 or
- *                            ENDO_OPT_MFMA_X3 select another operand form for the weight gradients.
+ *                            fp32 throughout (csrc/wgrad_f34_kernels.h); 0 = the direct kernels.  Ignored where ENDO_OPT_MFMA_BF16
+ *                            selects rounded operands for the weight gradients.
  *   ENDO_OPT_FINAL_VIRTUAL   1 (default) = the data gradient of the final 1x1 convolution (models.py:167, 186), g(pixel) * w[channel] with
  *                            g = grad_out * sign(pre), is not written to the 192 level-0 gradient planes: g goes to one plane and the last up
  *                            block's backward kernels form the product where they first touch a channel (two passes over 1 GB less per
@@ -299,7 +294,7 @@ int endo_net_groups(const endo_net* net);
 #define ENDO_OPT_WINO_MIN_TILES 3
 #define ENDO_OPT_MFMA_BF16 4
 #define ENDO_OPT_WGRAD_OVERLAP 5
-#define ENDO_OPT_MFMA_X3 6
+/* id 6 is retired and not reused */
 #define ENDO_OPT_WGRAD_F34 7
 #define ENDO_OPT_FINAL_VIRTUAL 8
 #define ENDO_OPT_TD_PERSIST 9

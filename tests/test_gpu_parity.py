@@ -386,7 +386,7 @@ def test_network_backward(shape):
     assert_close(model.flat_gradients(), 2.0 * first, 1e-5, "accumulated gradient")
 
 
-OPT_WINO_FWD, OPT_WINO_DGRAD, OPT_DGRAD_VEC, OPT_WINO_MIN_TILES, OPT_MFMA_BF16, OPT_WGRAD_OVERLAP, OPT_MFMA_X3, OPT_WGRAD_F34 = 0, 1, 2, 3, 4, 5, 6, 7
+OPT_WINO_FWD, OPT_WINO_DGRAD, OPT_DGRAD_VEC, OPT_WINO_MIN_TILES, OPT_MFMA_BF16, OPT_WGRAD_OVERLAP, OPT_WGRAD_F34 = 0, 1, 2, 3, 4, 5, 7          # (id 6 is retired)
 
 
 class kernel_options(object):
@@ -436,12 +436,21 @@ def test_kernel_options_are_per_model():
     assert lib.endo_net_set_option(None, OPT_MFMA_BF16, 1) == -1
     hnd = a._handle(n, h, w)[0]
     assert lib.endo_net_set_option(hnd, 99, 1) == -1 and lib.endo_net_get_option(hnd, OPT_WINO_MIN_TILES) == 1024
+    # the Python copy of the library's defaults (FCDenseNet._OPTION_DEFAULTS) against a fresh model's handle
+    _, fresh = make_model(81)
+    fresh_hnd = fresh._handle(n, h, w)[0]
+    for option_id, value in ea.models.FCDenseNet._OPTION_DEFAULTS.items():
+        assert lib.endo_net_get_option(fresh_hnd, option_id) == value, option_id
+    # id 6 (the removed three-term bf16 split option) is retired: unknown to the library and to the model
+    assert lib.endo_net_set_option(hnd, 6, 1) == -1 and lib.endo_net_get_option(hnd, 6) == -1
+    with pytest.raises(ValueError):
+        a.set_kernel_option(6, 1)
 
 
 @pytest.mark.parametrize("which,shape", [("winograd", (2, 64, 96)), ("winograd", (2, 128, 160)), ("winograd", (1, 64, 128)),
                                          ("direct", (2, 64, 96)), ("direct", (2, 128, 160)), ("direct", (1, 64, 128)),
                                          ("winograd4", (2, 64, 96)), ("winograd4", (2, 128, 160)), ("winograd4", (1, 64, 128)),
-                                         ("x3", (2, 128, 160))],          # x3: needs >= 2048 row chunks at level 0 to reach the n-split / x3 weight-gradient kernels
+                                         ("nsplit", (2, 128, 256))],          # nsplit: 8 * 128 * 2 = 2048 row chunks at level 0, the fewest that reach the n-split weight-gradient kernel
                          ids=lambda v: "x".join(str(i) for i in v) if isinstance(v, tuple) else v)
 def test_network_backward_kernel_forms(shape, which):
     """The Winograd kernels (dense-layer forward, fused base-channel data gradient, F(3x3, 4x4) weight gradient where the height is a multiple of 16
@@ -450,14 +459,15 @@ def test_network_backward_kernel_forms(shape, which):
     level and all 210 gradients are checked on the pass's own activation pattern as in test_network_backward -- so both forms
     of every such layer are held to the same 3e-5, at sizes the fp64 oracle finishes in seconds."""
     n, h, w = shape
-    # "x3": the dense weight gradient with its fp32 products as three-term bf16 splits on the bf16 matrix cores (ENDO_OPT_MFMA_X3 bit 0,
-    # csrc/wgrad_x3_kernels.h; DESIGN.md 4.15: not the default) -- the SAME function, held to the same fp32 bound
+    # "nsplit": everything default but ENDO_OPT_WGRAD_F34 = 0, at the smallest grid whose level 0 has the 2048 row chunks of 32 pixels that
+    # wgrad_nsplit_ok asks for: its eight dense layers take wgrad_nsplit_kernel<NG, 0, 0> (csrc/wgrad_nsplit_kernels.h; level 1, 512 chunks, stays
+    # on the tap-folded kernel) -- the bounds of "direct"
     # "winograd4": the dense-layer forward in F(4x4, 3x3) form (ENDO_OPT_WINO_FWD = 5, csrc/wino4_fwd_kernels.h; the default form of level 0 since
     # round 5) forced onto EVERY level whose height and width allow it.  With the interpolation points 0, +-5/8, +-3/2, inf of round 5 the depth
     # sits at 1.9e-6 .. 2.2e-6 of its maximum (round 4's textbook points: 4e-6 .. 6e-6; the other forms: 0.9e-6 .. 1.1e-6) and is held to the
     # same 1e-5 as every form; the gradients -- taken on the pass's own pattern, from activations that carry the forward's rounding --
     # measured 2.0e-5 .. 3.5e-5 (round 4: 5.8e-5 .. 1.1e-4; the other forms 0.7e-5 .. 2.2e-5) and are held to 5e-5 (round 4: 1.6e-4).
-    opts = {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 1} if which == "winograd" else {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 5} if which == "winograd4" else ({OPT_MFMA_X3: 1} if which == "x3" else {OPT_WINO_FWD: 0, OPT_WINO_DGRAD: 0, OPT_DGRAD_VEC: 0, OPT_WGRAD_F34: 0})
+    opts = {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 1} if which == "winograd" else {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 5} if which == "winograd4" else ({OPT_WGRAD_F34: 0} if which == "nsplit" else {OPT_WINO_FWD: 0, OPT_WINO_DGRAD: 0, OPT_DGRAD_VEC: 0, OPT_WGRAD_F34: 0})
     with kernel_options(opts):
         state, model = make_model(62)
         rng = np.random.default_rng(16)

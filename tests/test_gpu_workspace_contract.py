@@ -160,7 +160,7 @@ ORACLE_CASES = (
     [_case(tp, "test_fused_loss_head_matches_modules", shape=s) for s in ((3, 32, 64), (1, 256, 320))] +
     # fp32 network
     [_case(tp, "test_network_backward_kernel_forms", shape=s, which=wh) for wh in ("winograd", "winograd4", "direct") for s in ((2, 64, 96), (1, 64, 128))] +
-    [_case(tp, "test_network_backward_kernel_forms", shape=(2, 128, 160), which="x3"), _case(tp, "test_network_backward_eval_mode"),
+    [_case(tp, "test_network_backward_kernel_forms", shape=(2, 128, 256), which="nsplit"), _case(tp, "test_network_backward_eval_mode"),
      _case(tp, "test_forward_pair_is_two_calls", shape=(3, 32, 64))] +
     [_case(tp, "test_final_conv_fusions_are_transparent", forced=f, extra=e, ident=i) for f, e, i in FUSIONS] +
     [_case(tp, nm, shape=(3, 96, 160)) for nm in ("test_persistent_new_map_passes_match_the_per_tile_blocks", "test_persistent_base_pass_matches_the_per_tile_kernel",

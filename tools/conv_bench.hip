@@ -129,8 +129,8 @@ int main(int argc, char** argv) {
             static ConvParams fw, fwn;
             fw = f; fw.wgt = ubuf; fwn = fw; fwn.out_sums = nullptr;
             if (wino_fwd_ok(fw)) {
-                vs.push_back({"fwd Winograd F(2x2,3x3) 32x8 (level-1 form)", [&](hipStream_t s) { return launch_wino_fwd<1, 4, 3, 2>(fw, s); }});
-                vs.push_back({"fwd Winograd F(2x2,3x3) 32x8, no output statistics", [&](hipStream_t s) { return launch_wino_fwd<1, 4, 3, 2>(fwn, s); }});
+                vs.push_back({"fwd Winograd F(2x2,3x3) 32x8 (level-1 form)", [&](hipStream_t s) { return launch_wino_fwd<1, 4, 3>(fw, s); }});
+                vs.push_back({"fwd Winograd F(2x2,3x3) 32x8, no output statistics", [&](hipStream_t s) { return launch_wino_fwd<1, 4, 3>(fwn, s); }});
             }
         }
         bench(vs, f.out, (size_t)12 * plane, flops);      // compares sample 0's 12 planes
@@ -149,16 +149,14 @@ int main(int argc, char** argv) {
         }
         const double bflops = 2.0 * n * plane * c0 * 12 * 9 * 4;
         std::vector<Variant> vs;
-        vs.push_back({"dgrad_block<4> GP1 pipelined (library)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 0, 1>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP1 (library)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 0>(p, s); }});
         vs.push_back({"dgrad_block8<4> (512 threads, 2 halves)", [&](hipStream_t s) { return launch_dgrad_block8<4>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP1 unpipelined", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 0, 0>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP2 pipelined", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 2, 0, 1>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP2 unpipelined", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 2, 0, 0>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP1 pipelined no loads/stores", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 3, 1>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP1 trivial epilogue (32+8)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 40, 1>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP1 trivial epi, no ld/st (43)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 43, 1>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP1 + weights once (47)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 47, 1>(p, s); }});
-        vs.push_back({"dgrad_block<4> GP2 + weights once (47)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 2, 47, 0>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP2", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 2, 0>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP1 no loads/stores", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 3>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP1 trivial epilogue (32+8)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 40>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP1 trivial epi, no ld/st (43)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 43>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP1 + weights once (47)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 1, 47>(p, s); }});
+        vs.push_back({"dgrad_block<4> GP2 + weights once (47)", [&](hipStream_t s) { return launch_dgrad_block<4, 2, 3, 2, 47>(p, s); }});
         bench(vs, p.out, (size_t)c0 * plane, bflops);
     }
 
@@ -175,7 +173,7 @@ int main(int argc, char** argv) {
         auto zero = [&](hipStream_t s) { CK(hipMemsetAsync(dw, 0, (size_t)12 * cin * 9 * 4, s)); };
         vs.push_back({"wgrad taps-in-M dma 32x8", [&](hipStream_t s) { zero(s); return launch_wgrad_taps<12, IN_BNRELU>(g, s); }});
         vs.push_back({"wgrad nsplit (library)", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit(g, wscratch, s); }});
-        vs.push_back({"wgrad nsplit, bf16 MFMA operands", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit(g, wscratch, s, 1); }});
+        vs.push_back({"wgrad nsplit, bf16 MFMA operands", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit(g, wscratch, s, true); }});
         vs.push_back({"wgrad nsplit<3> no x loads", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit_ng<3, 1>(g, wscratch, passes, s); }});
         vs.push_back({"wgrad nsplit<3> no dY DMA", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit_ng<3, 2>(g, wscratch, passes, s); }});
         vs.push_back({"wgrad nsplit<3> no loads at all", [&](hipStream_t s) { zero(s); return launch_wgrad_nsplit_ng<3, 3>(g, wscratch, passes, s); }});

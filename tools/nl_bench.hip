@@ -67,7 +67,7 @@ static void bench(std::vector<Variant>& vs, float* out, size_t out_n, double flo
 
 
 template <int NL, int EXP, int VEC>
-static int run_nl(const DgradBlockParams& p, hipStream_t s) { return launch_dgrad_block<NL, 2, 3, 1, EXP, 1, VEC>(p, s); }
+static int run_nl(const DgradBlockParams& p, hipStream_t s) { return launch_dgrad_block<NL, 2, 3, 1, EXP, VEC>(p, s); }
 
 template <int NL>
 static void nl_section(DgradBlockParams p, int n, int64_t plane) {

@@ -127,7 +127,7 @@ int main(int argc, char** argv) {
     std::vector<Variant> vs;
     vs.push_back({"dgrad_block8<4> direct (reference values)", [&](hipStream_t s) { return launch_dgrad_block8<4>(p, s); }});
     vs.push_back({"dgrad_wino8<4> (round-2 library)", [&](hipStream_t s) { return launch_dgrad_wino8<4>(p, u, s); }});
-    vs.push_back({"dgrad_wino3<4> (library)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 0, 0>(p, u1, s); }});
+    vs.push_back({"dgrad_wino3<4> (library)", [&](hipStream_t s) { return launch_dgrad_wino3<4>(p, u1, s); }});
     // persistent blocks (dgrad_wino3p_kernels.h): one block per CU walking a run of tiles
     int cus = 256;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, 0) == hipSuccess) cus = prop.multiProcessorCount; }
@@ -169,7 +169,7 @@ int main(int argc, char** argv) {
         double* fwp; CK(hipMalloc(&fwp, (size_t)cus * c0 * sizeof(double))); CK(hipMemset(fwp, 0, (size_t)cus * c0 * sizeof(double)));
         int used = 0;
         std::vector<Variant> v3;
-        v3.push_back({"dgrad_wino3<4> (library), virtual old gradient", [&](hipStream_t s) { return launch_dgrad_wino3<4, 0, 0>(pv, u1, s); }});
+        v3.push_back({"dgrad_wino3<4> (library), virtual old gradient", [&](hipStream_t s) { return launch_dgrad_wino3<4>(pv, u1, s); }});
         v3.push_back({"dgrad_wino3p<4, FW> persistent, virtual old gradient", [&](hipStream_t s) { return launch_dgrad_wino3p<4, true, 0>(pv, u1, cus, fwp, &used, s); }});
         bench(v3, p.out, (size_t)n * c0 * plane, scratch, scratch_n, flops);
         std::vector<double> parts((size_t)used * c0);
@@ -187,15 +187,13 @@ int main(int argc, char** argv) {
         printf("final-conv weight gradient from %d block partials: max |diff| %.3e of max |ref| %.3e\n", used, worst, big);
         return 0;
     }
-    vs.push_back({"dgrad_wino3<4> OPT16 (weight DMA at V end)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 0, 16>(p, u1, s); }});
-    vs.push_back({"dgrad_wino3<4> OPT32 (setprio 1 in M phases)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 0, 32>(p, u1, s); }});
-    vs.push_back({"wino3 no dY tile load (8)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 8, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no atomics (4)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 4, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no tile load, no atomics (12)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 12, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no mem (7)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 7, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no mem, no V arithmetic (71)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 71, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no mem, no M phase (135)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 135, 0>(p, u1, s); }});
-    vs.push_back({"wino3 no mem, neither (199)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 199, 0>(p, u1, s); }});
+    vs.push_back({"wino3 no dY tile load (8)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 8>(p, u1, s); }});
+    vs.push_back({"wino3 no atomics (4)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 4>(p, u1, s); }});
+    vs.push_back({"wino3 no tile load, no atomics (12)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 12>(p, u1, s); }});
+    vs.push_back({"wino3 no mem (7)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 7>(p, u1, s); }});
+    vs.push_back({"wino3 no mem, no V arithmetic (71)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 71>(p, u1, s); }});
+    vs.push_back({"wino3 no mem, no M phase (135)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 135>(p, u1, s); }});
+    vs.push_back({"wino3 no mem, neither (199)", [&](hipStream_t s) { return launch_dgrad_wino3<4, 199>(p, u1, s); }});
     if (mode == 0) {
         vs.push_back({"wino8 no atomics (4)", [&](hipStream_t s) { return launch_dgrad_wino8<4, 4>(p, u, s); }});
         vs.push_back({"wino8 no stores (2)", [&](hipStream_t s) { return launch_dgrad_wino8<4, 2>(p, u, s); }});

@@ -1,7 +1,7 @@
-// fp32 products on the bf16 matrix cores ("bf16x3", csrc/common.h split_bf16x8): speed and ACCURACY of the dense-layer weight gradient in its
-// three operand modes -- fp32 MFMA, operands rounded to bf16 (the mixed-precision mode), three-term split with six bf16 MFMAs -- against an
-// fp64 evaluation of the same sums on the host (a sample of the weight-gradient entries) -- and, since round 4, of the Winograd F(3x3, 4x4)
-// form (csrc/wgrad_f34_kernels.h) with its diagnostic build without activation loads.  Development tool, not part of the product.
+// Speed and ACCURACY of the dense-layer weight gradient in its two operand modes -- fp32 MFMA, operands rounded to bf16 (the mixed-precision
+// mode) -- against an fp64 evaluation of the same sums on the host (a sample of the weight-gradient entries) -- and, since round 4, of the
+// Winograd F(3x3, 4x4) form (csrc/wgrad_f34_kernels.h) with its diagnostic build without activation loads.  (Named after the
+// three-term bf16 split of fp32 products it first measured: DESIGN_HISTORY.md 4.15, removed.)  Development tool, not part of the product.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics tools/x3_bench.hip -o tools/bin/x3_bench
 //   tools/bin/x3_bench [cin] [n] [h] [w]
 #include <cstdio>
@@ -13,7 +13,6 @@
 
 #include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad_taps_kernels.h"
 #include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad_nsplit_kernels.h"
-#include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad_x3_kernels.h"
 #include "../endoscopydepthestimation-pytorch_amd/csrc/wgrad_f34_kernels.h"
 
 using namespace endo;
@@ -93,12 +92,12 @@ int main(int argc, char** argv) {
     double maxref = 0; for (double v : ref) maxref = fmax(maxref, fabs(v));
 
     struct V { const char* name; int mode; };
-    const V vs[] = {{"fp32 MFMA (v_mfma_f32_16x16x4_f32)", 0}, {"operands rounded to bf16 (1 x bf16 MFMA)", 1}, {"three-term split per fragment, 6 x bf16 MFMA", 2}, {"three-term split, G pre-split in LDS (wgrad_x3_kernel)", 3}, {"diagnostic: 6 MFMAs on rounded operands, no split", 5}, {"diagnostic: fp32 MFMA, conflict-free (wrong) fragment addresses", 6}, {"Winograd F(3x3, 4x4), fp32 MFMA (wgrad_f34_kernel)", 7}, {"diagnostic: F(3x3, 4x4) without x loads", 9}};
+    const V vs[] = {{"fp32 MFMA (v_mfma_f32_16x16x4_f32)", 0}, {"operands rounded to bf16 (1 x bf16 MFMA)", 1}, {"diagnostic: fp32 MFMA, conflict-free (wrong) fragment addresses", 6}, {"Winograd F(3x3, 4x4), fp32 MFMA (wgrad_f34_kernel)", 7}, {"diagnostic: F(3x3, 4x4) without x loads", 9}};
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     std::vector<float> got((size_t)12 * cin * 9);
     for (const V& v : vs) {
         CK(hipMemset(dw, 0, got.size() * 4));
-        auto run = [&](int mode) { if (mode == 6) { const int groups = (g.cin + 15) / 16, passes = (groups + 11) / 12, ng = ((groups + passes - 1) / passes + 3) / 4; return ng <= 1 ? launch_wgrad_nsplit_ng<1, 8>(g, wscratch, passes, 0) : ng == 2 ? launch_wgrad_nsplit_ng<2, 8>(g, wscratch, passes, 0) : launch_wgrad_nsplit_ng<3, 8>(g, wscratch, passes, 0); } if (mode == 7) return wgrad_f34_ok(g, 16) ? launch_wgrad_f34(g, wscratch, 0) : -1; if (mode == 9) return launch_wgrad_f34<2>(g, wscratch, 0); return mode == 3 ? launch_wgrad_x3(g, wscratch, 0) : launch_wgrad_nsplit(g, wscratch, 0, mode == 5 ? 3 : mode); };
+        auto run = [&](int mode) { if (mode == 6) { const int groups = (g.cin + 15) / 16, passes = (groups + 11) / 12, ng = ((groups + passes - 1) / passes + 3) / 4; return ng <= 1 ? launch_wgrad_nsplit_ng<1, 8>(g, wscratch, passes, 0) : ng == 2 ? launch_wgrad_nsplit_ng<2, 8>(g, wscratch, passes, 0) : launch_wgrad_nsplit_ng<3, 8>(g, wscratch, passes, 0); } if (mode == 7) return wgrad_f34_ok(g, 16) ? launch_wgrad_f34(g, wscratch, 0) : -1; if (mode == 9) return launch_wgrad_f34<2>(g, wscratch, 0); return launch_wgrad_nsplit(g, wscratch, 0, mode == 1); };
         int rc = run(v.mode);
         if (rc) { printf("%s: launch failed %d\n", v.name, rc); continue; }
         CK(hipDeviceSynchronize());
