@@ -82,6 +82,9 @@ SIGNATURES = {
     "endo_net_level_channels": (_I, [_I]),
     "endo_net_act_offset": (_L, [_P, _I]),
     "endo_net_tape_offset": (_L, [_P, _I, _I]),
+    "endo_net_last_plan": (_I, [_P, _I, _P, _I]),
+    "endo_net_plan_query": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "endo_net_plan_name": (ctypes.c_char_p, [_I, _I]),
     "endo_net_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "endo_net_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "endo_sgd_clip_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P, _P]),

@@ -385,15 +385,16 @@ inline bool dgrad_newmap_ok(const DgradBlockParams& p) {
     return p.count <= 16 && p.acc_from == 0 && 36ll * p.g_cs * 4 < (1ll << 31) && (16ll * p.cs + static_cast<int64_t>(p.h) * p.w) * 4 < (1ll << 32);
 }
 
+// cus: compute units the launch is sized for (the device's, or fewer: ENDO_OPT_CHIP_DIVISOR)
 template <int NL>
-inline int launch_dgrad_newmap(DgradBlockParams p, hipStream_t stream) {
+inline int launch_dgrad_newmap(DgradBlockParams p, int cus, hipStream_t stream) {
     using NG = NewMapGeom<NL>;
     using G = typename NG::G;
     p.tiles_x = (p.w + G::kTileX - 1) / G::kTileX;
     const int tiles_y = (p.h + G::kTileY - 1) / G::kTileY;
     const int groups = p.group_n > 0 ? p.n / p.group_n : 1;
     const int tiles_per_group = p.tiles_x * tiles_y * (p.group_n > 0 ? p.group_n : p.n);
-    const int resident = device_cu_count() * NG::kBlocksPerCu / groups;          // blocks per group that are on the chip at once
+    const int resident = std::max(1, cus * NG::kBlocksPerCu / groups);          // blocks per group that are on the chip at once
     const int tiles_per_block = (tiles_per_group + resident - 1) / resident;
     int blocks_per_group = (tiles_per_group + tiles_per_block - 1) / tiles_per_block;
     blocks_per_group = (blocks_per_group + 7) / 8 * 8;          // (empty blocks leave at once) a multiple of 8 for the XCD map

@@ -146,6 +146,8 @@ static const Table& table() {
 
 using namespace endo;
 
+namespace endo { struct FwdPlan; struct BwdPlan; }
+
 struct endo_net {
     int n, h, w;           // n = samples per group
     int groups;            // independent forward / backward passes batched into every launch (each with its own BN statistics)
@@ -181,6 +183,9 @@ struct endo_net {
     // kernel-form / precision options of THIS network (endo_net_set_option): two networks in one process never change each
     // other's arithmetic, and a thread stepping one model is not affected by another thread configuring a second one
     int opt[ENDO_OPT_COUNT];
+    // copies of the plans the last endo_net_fwd / endo_net_bwd on this handle followed (endo_net_last_plan); null until that pass has run
+    FwdPlan* last_fwd;
+    BwdPlan* last_bwd;
 };
 
 namespace endo {
@@ -723,7 +728,12 @@ static void default_options(int (&opt)[ENDO_OPT_COUNT]) {
     opt[ENDO_OPT_WGRAD_F34] = 1;
     opt[ENDO_OPT_FINAL_VIRTUAL] = 1;
     opt[ENDO_OPT_TD_PERSIST] = 3;
+    opt[ENDO_OPT_CHIP_DIVISOR] = 1;
 }
+// ENDO_OPT_CHIP_DIVISOR d: every does-it-fill-the-chip comparison of the plan sees its tile / chunk count times d, and the persistent launches
+// get 1 / d of the compute units -- a small grid then takes the forms, and its blocks walk the runs of tiles, of a grid d times its size
+static long chip_divisor(const endo_net* net) { const int d = net->opt[ENDO_OPT_CHIP_DIVISOR]; return d < 1 ? 1 : d; }
+static int persistent_cus(const endo_net* net) { const int cus = static_cast<int>(device_cu_count() / chip_divisor(net)); return cus < 1 ? 1 : cus; }
 // ENDO_OPT_MFMA_BF16 as a mask of kernel families -- bit 0: weight gradients, bit 1: forward, bit 2: data gradients of the dense layers (1 = all three)
 static int bf16_mask(const int* opt) { const int v = opt[ENDO_OPT_MFMA_BF16]; return v == 1 ? 7 : (v >> 1); }
 
@@ -739,7 +749,7 @@ static DenseBlock dense_block(int b) {
 }
 static long tile_count(const Ctx& c, int level, int tx, int ty) {          // tx x ty pixel tiles of a launch over the level, partial ones included
     const auto& lv = c.net->lv[level];
-    return static_cast<long>((lv.w + tx - 1) / tx) * ((lv.h + ty - 1) / ty) * c.nt();
+    return static_cast<long>((lv.w + tx - 1) / tx) * ((lv.h + ty - 1) / ty) * c.nt() * chip_divisor(c.net);
 }
 
 // dense layer forward: BN -> ReLU -> conv3x3 -> +12 channels (reference models.py:19-28, 44-52), with the weights where `form` reads them
@@ -891,7 +901,7 @@ static int td_fwd(const Ctx& c, int level) {
     const ConvParams p = td_fwd_params(c, level);
     ProfScope prof(kProfConv1x1Pool, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1),
                    4.0 * c.nt() * c.net->lv[level].plane * (cv.cin + cv.cout / 4.0));
-    if (c.fwd->td_persistent[level]) return launch_td_fwd(p, device_cu_count(), c.stream);
+    if (c.fwd->td_persistent[level]) return launch_td_fwd(p, persistent_cus(c.net), c.stream);
     if (c.fwd->bf16) return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4, 2, 1, 1>(p, c.stream);
     return launch_conv_dma_auto<1, 8, 3, IN_BNRELU, EPI_FWD_POOL, 4>(p, c.stream);    // 32x8 tiles: -6 % in the in-job A/B (Q = 6 was 10 % slower; round 5: K-chunks of 16 channels +-0, of 32 +40 % on the family, Q = 6 with 16 +14 %)
 }
@@ -1114,7 +1124,8 @@ static BwdPlan plan_bwd(const Ctx& c) {
     pl.bf16_dgrad = (bf16_mask(opt) & 4) != 0;
     // operands of a dense-layer weight gradient: rounded to bf16, else fp32 MFMA -- and only the latter has a Winograd-domain form
     const bool f34 = opt[ENDO_OPT_WGRAD_F34] && !pl.bf16_wgrad;
-    const long f34_min_tiles = min_tiles / 4;          // from 256 tiles of 4 x 4 pixels: levels 0-4 of configs[1] (level 5 is 8 x 10)
+    const long fill = chip_divisor(c.net);
+    const long f34_min_tiles = (min_tiles / 4 + fill - 1) / fill;          // from 256 tiles of 4 x 4 pixels: levels 0-4 of configs[1] (level 5 is 8 x 10)
     // the data-gradient weights are transformed whenever a Winograd form is selected, whether or not a block takes one this pass (at small sizes none does)
     pl.dgrad_weights = wino_dgrad != 0 && !pl.bf16_dgrad;
     for (int b = 0; b < kBlocks; ++b) {
@@ -1129,7 +1140,7 @@ static BwdPlan plan_bwd(const Ctx& c) {
         bl.fused = dgrad_block_ok(base);
         // base pass at the fine levels: Winograd F(2x2, 3x3), 48 instead of 108 MFMAs per 64 pixels and step (dgrad_wino_kernels.h) -- the phase-skewed
         // kernel (ENDO_OPT_WINO_DGRAD 1 / 3, at most DgradWino3Geom::kMaxCount base channels), as persistent blocks where that form applies (3), else the round-2 kernel
-        const long wtiles = static_cast<long>(lv.w / 32) * (lv.h / 8) * c.nt();
+        const long wtiles = static_cast<long>(lv.w / 32) * (lv.h / 8) * c.nt() * fill;
         if (pl.bf16_dgrad) bl.base = BasePass::Block8Bf16;
         else if (wino_dgrad != 0 && dgrad_wino_ok(base) && wtiles >= min_tiles)
             bl.base = !((wino_dgrad == 1 || wino_dgrad == 3) && dgrad_wino3_ok(base)) ? BasePass::Wino8
@@ -1144,7 +1155,7 @@ static BwdPlan plan_bwd(const Ctx& c) {
         }
         for (int j = 0; j < kLayers; ++j) {
             const WgradParams p = dense_wgrad_params(c, k, j);
-            pl.wgrad[b * kLayers + j] = (f34 && wgrad_f34_ok(p, f34_min_tiles)) ? DenseWgrad::F34 : wgrad_nsplit_ok(p) ? DenseWgrad::NSplit
+            pl.wgrad[b * kLayers + j] = (f34 && wgrad_f34_ok(p, f34_min_tiles)) ? DenseWgrad::F34 : wgrad_nsplit_ok(p, fill) ? DenseWgrad::NSplit
                                       : wgrad_taps_ok(p) ? DenseWgrad::Taps : DenseWgrad::Direct;
         }
     }
@@ -1238,10 +1249,10 @@ static int dense_bwd(const Ctx& c, int b, int j, int acc_from) {
 }
 
 template <int NL>
-static int launch_newmap(NewMap form, const DgradBlockParams& p, hipStream_t stream) {
+static int launch_newmap(NewMap form, const DgradBlockParams& p, int cus, hipStream_t stream) {
     switch (form) {
         case NewMap::Bf16: return launch_dgrad_block<NL, 2, 3, 1, 0, 4, 1>(p, stream);
-        case NewMap::Persistent: return launch_dgrad_newmap<NL>(p, stream);          // dgrad_newmap_kernels.h
+        case NewMap::Persistent: return launch_dgrad_newmap<NL>(p, cus, stream);          // dgrad_newmap_kernels.h
         case NewMap::Vec16: return launch_dgrad_block<NL, 2, 3, 1, 0, 4>(p, stream);
         case NewMap::Dword: return launch_dgrad_block<NL, 2, 3>(p, stream);
     }
@@ -1301,7 +1312,8 @@ static int dense_block_bwd(const Ctx& c, int b, const FinalVirt* fv = nullptr) {
             if (fv) { p.vg = fv->vg; p.vw = fv->vw + ic0 + p.w_ci_off; }
             ProfScope prof(kProfDgradDense, c.stream, 2.0 * c.nt() * lv.plane * kGrowth * kGrowth * 9 * nl,
                            4.0 * c.nt() * lv.plane * (3.0 * kGrowth + kGrowth * nl));
-            rc = nl == 1 ? launch_newmap<1>(bl.newmap[j], p, c.stream) : nl == 2 ? launch_newmap<2>(bl.newmap[j], p, c.stream) : launch_newmap<3>(bl.newmap[j], p, c.stream);
+            const int cus = bl.newmap[j] == NewMap::Persistent ? persistent_cus(c.net) : 0;
+            rc = nl == 1 ? launch_newmap<1>(bl.newmap[j], p, cus, c.stream) : nl == 2 ? launch_newmap<2>(bl.newmap[j], p, cus, c.stream) : launch_newmap<3>(bl.newmap[j], p, cus, c.stream);
             if (rc) return rc;
             pending = a;          // consumed by the prep_dy of these 12 maps at the top of the next iteration
             pending_nl = nl;
@@ -1326,7 +1338,7 @@ static int dense_block_bwd(const Ctx& c, int b, const FinalVirt* fv = nullptr) {
                 // persistent blocks, one per CU; with virt_base_w they leave per-block partials of dW_final[ic0 .. ic0 + c0), added up here
                 double* fwp = (virt && c.bwd->virt_base_w) ? reinterpret_cast<double*>(c.gradws + c.net->fw_parts_off) : nullptr;
                 int used = 0;
-                rc = run_dgrad_wino3p_nl4(p, u, std::min(device_cu_count(), kFwPartBlocks), fwp, &used, c.stream);
+                rc = run_dgrad_wino3p_nl4(p, u, std::min(persistent_cus(c.net), kFwPartBlocks), fwp, &used, c.stream);
                 if (rc == 0 && fwp) {
                     final_w_reduce_kernel<<<c0, 64, 0, c.stream>>>(fwp, used, c0, fv->gw + ic0);
                     ENDO_LAUNCH_CHECK();
@@ -1371,7 +1383,7 @@ static int td_bwd(const Ctx& c, int level) {
         const ConvParams p = td_dgrad_params(c, level);
         ProfScope prof(kProfDgradOther, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1), 4.0 * c.nt() * lv.plane * 3.0 * cv.cin);
         switch (c.bwd->td_dgrad[level]) {
-            case TdDgrad::Persistent: rc = launch_td_dgrad(p, device_cu_count(), c.stream); break;
+            case TdDgrad::Persistent: rc = launch_td_dgrad(p, persistent_cus(c.net), c.stream); break;
             case TdDgrad::Runs128: rc = launch_td_dgrad_small(p, c.stream); break;
             case TdDgrad::Dma: rc = c.bwd->bf16_dgrad ? launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4, 2, 1, 1>(p, c.stream)
                                                       : launch_conv_dma_auto<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN, 4>(p, c.stream); break;
@@ -1439,6 +1451,7 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     if (!net) return ENDO_E_BADARG;
     net->n = n; net->h = h; net->w = w; net->groups = groups;
     net->wstream = nullptr; net->ev_fork = nullptr; net->ev_join = nullptr;
+    net->last_fwd = nullptr; net->last_bwd = nullptr;
     default_options(net->opt);
     int64_t off = 0, sums = 0, pq = 0;
     for (int l = 0; l <= kLevels; ++l) {
@@ -1518,6 +1531,8 @@ extern "C" void endo_net_destroy(endo_net* net) {
     if (net->ev_fork) (void)hipEventDestroy(net->ev_fork);
     if (net->ev_join) (void)hipEventDestroy(net->ev_join);
     if (net->wstream) (void)hipStreamDestroy(net->wstream);
+    delete net->last_fwd;
+    delete net->last_bwd;
     delete net;
 }
 extern "C" int64_t endo_net_param_floats(void) { return table().param_floats; }
@@ -1561,6 +1576,8 @@ extern "C" int endo_net_fwd(endo_net* net, const float* params, float* bn_runnin
     Ctx c{net, params, bn_running, tape, nullptr, nullptr, training, static_cast<hipStream_t>(stream_)};
     const FwdPlan plan = plan_fwd(c);
     c.fwd = &plan;
+    if (!net->last_fwd) net->last_fwd = new (std::nothrow) FwdPlan;
+    if (net->last_fwd) *net->last_fwd = plan;
     for (int g = 0; g < net->groups; ++g)
         ENDO_CHECK(hipMemsetAsync(reinterpret_cast<char*>(tape + g * net->gs) + net->sums_off, 0, net->sums_bytes, c.stream));
     if (!plan.bf16) {          // dense-layer weights in Winograd form or in the direct kernel's chunk order, as each layer's planned form reads them: all 44 layers in one launch
@@ -1622,6 +1639,8 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
     c.x = x;
     const BwdPlan plan = plan_bwd(c);
     c.bwd = &plan;
+    if (!net->last_bwd) net->last_bwd = new (std::nothrow) BwdPlan;
+    if (net->last_bwd) *net->last_bwd = plan;
     BiasParts bias_parts{};
     c.bias_parts = &bias_parts;
     if (!net->wstream) {          // side stream of the weight gradients (see endo_net), created on first use on the caller's device
@@ -1719,4 +1738,128 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         ENDO_CHECK(hipStreamWaitEvent(c.stream, net->ev_join, 0));
     }
     return 0;
+}
+
+// ---- the plan, readable (include/endo_hip.h: endo_net_last_plan / endo_net_plan_query / endo_net_plan_name) ----
+namespace endo {
+
+// One name table per ENDO_PLAN_* kind whose value is a choice of kernel form (enumerators in the order of the enum classes above; two-way choices
+// are the plans' bools, false first); kinds with a null table carry a plain number.
+struct PlanKind { const char* name; const char* const* values; int count; };
+static const char* const kDenseFwdNames[] = {"Wino4", "Wino2_32x16", "Wino2_32x8", "SplitK", "Direct32x8", "Direct16x8", "DirectAuto"};
+static const char* const kNewMapNames[] = {"Bf16", "Persistent", "Vec16", "Dword"};
+static const char* const kBasePassNames[] = {"Block8", "Block8Bf16", "Wino3", "Wino3Persistent", "Wino8"};
+static const char* const kDenseWgradNames[] = {"F34", "NSplit", "Taps", "Direct"};
+static const char* const kTdDgradNames[] = {"Persistent", "Runs128", "Dma", "Staged"};
+static const char* const kTuWgradNames[] = {"Subpix", "Taps", "Direct"};
+static const char* const kTuDgradNames[] = {"Subpix32x8", "Subpix16x8", "Subpix16x4", "Plain"};
+static const char* const kFirstWgradNames[] = {"F34Prep", "F34", "Taps", "Direct"};
+static const char* const kTdFwdNames[] = {"PerTile", "Persistent"};
+static const char* const kTuFwdNames[] = {"Upsample", "Subpix"};
+static const char* const kBlockBwdNames[] = {"PerLayer", "Fused"};
+static const char* const kTdWgradNames[] = {"Plain", "Dma"};
+static_assert(static_cast<int>(DenseFwd::DirectAuto) == 6 && static_cast<int>(NewMap::Dword) == 3 && static_cast<int>(BasePass::Wino8) == 4 &&
+              static_cast<int>(DenseWgrad::Direct) == 3 && static_cast<int>(TdDgrad::Staged) == 3 && static_cast<int>(TuWgrad::Direct) == 2 &&
+              static_cast<int>(TuDgrad::Plain) == 3 && static_cast<int>(FirstWgrad::Direct) == 3, "the name tables follow the enums");
+static const PlanKind kPlanKinds[ENDO_PLAN_KIND_COUNT] = {
+    {"dense_fwd", kDenseFwdNames, 7}, {"dense_fwd_ksplit", nullptr, 0}, {"dense_fwd_chunk_weights", nullptr, 0}, {"fwd_bf16", nullptr, 0},
+    {"wino4_weights", nullptr, 0}, {"fuse_final", nullptr, 0}, {"td_fwd", kTdFwdNames, 2}, {"tu_fwd", kTuFwdNames, 2},
+    {"block_bwd", kBlockBwdNames, 2}, {"newmap", kNewMapNames, 4}, {"base_pass", kBasePassNames, 5}, {"wino3_layout", nullptr, 0},
+    {"dense_wgrad", kDenseWgradNames, 4}, {"td_wgrad", kTdWgradNames, 2}, {"td_dgrad", kTdDgradNames, 4}, {"tu_wgrad", kTuWgradNames, 3},
+    {"tu_dgrad", kTuDgradNames, 4}, {"wgrad_overlap", nullptr, 0}, {"bf16_wgrad", nullptr, 0}, {"bf16_dgrad", nullptr, 0},
+    {"dgrad_weights", nullptr, 0}, {"use_virt", nullptr, 0}, {"virt_base", nullptr, 0}, {"virt_base_w", nullptr, 0},
+    {"materialise", nullptr, 0}, {"c_first", nullptr, 0}, {"first_wgrad", kFirstWgradNames, 4},
+};
+
+// (kind, index, level, value) per field; writes only while the entries fit, always counts
+struct PlanWriter {
+    int32_t* out; int capacity; int count = 0;
+    void put(int kind, int index, int level, int value) {
+        if (count + 4 <= capacity) { out[count] = kind; out[count + 1] = index; out[count + 2] = level; out[count + 3] = value; }
+        count += 4;
+    }
+};
+
+static void write_plan(const FwdPlan& pl, PlanWriter& w) {
+    for (int i = 0; i < kDense; ++i) {
+        const int level = dense_block(i / kLayers).level;
+        w.put(ENDO_PLAN_DENSE_FWD, i, level, static_cast<int>(pl.dense[i].form));
+        w.put(ENDO_PLAN_DENSE_FWD_KSPLIT, i, level, pl.dense[i].ksplit);
+        w.put(ENDO_PLAN_DENSE_FWD_CHUNK_WEIGHTS, i, level, pl.dense[i].chunk_weights);
+    }
+    w.put(ENDO_PLAN_FWD_BF16, 0, -1, pl.bf16);
+    w.put(ENDO_PLAN_WINO4_WEIGHTS, 0, -1, pl.wino4_weights);
+    w.put(ENDO_PLAN_FUSE_FINAL, 0, -1, pl.fuse_final);
+    for (int l = 0; l < kLevels; ++l) {
+        w.put(ENDO_PLAN_TD_FWD, l, l, pl.td_persistent[l]);
+        w.put(ENDO_PLAN_TU_FWD, l, l, pl.tu_subpix[l]);
+    }
+}
+
+static void write_plan(const BwdPlan& pl, PlanWriter& w) {
+    for (int b = 0; b < kBlocks; ++b) {
+        const int level = dense_block(b).level;
+        const BwdPlan::Block& bl = pl.block[b];
+        w.put(ENDO_PLAN_BLOCK_BWD, b, level, bl.fused);
+        for (int j = 1; j < kLayers; ++j) w.put(ENDO_PLAN_NEWMAP, b * kLayers + j, level, static_cast<int>(bl.newmap[j]));
+        w.put(ENDO_PLAN_BASE_PASS, b, level, static_cast<int>(bl.base));
+        w.put(ENDO_PLAN_WINO3_LAYOUT, b, level, bl.wino3_layout);
+    }
+    for (int i = 0; i < kDense; ++i) w.put(ENDO_PLAN_DENSE_WGRAD, i, dense_block(i / kLayers).level, static_cast<int>(pl.wgrad[i]));
+    for (int l = 0; l < kLevels; ++l) {
+        w.put(ENDO_PLAN_TD_WGRAD, l, l, pl.td_wgrad_dma[l]);
+        w.put(ENDO_PLAN_TD_DGRAD, l, l, static_cast<int>(pl.td_dgrad[l]));
+        w.put(ENDO_PLAN_TU_WGRAD, l, l, static_cast<int>(pl.tu_wgrad[l]));
+        w.put(ENDO_PLAN_TU_DGRAD, l, l, static_cast<int>(pl.tu_dgrad[l]));
+    }
+    w.put(ENDO_PLAN_WGRAD_OVERLAP, 0, -1, pl.overlap);
+    w.put(ENDO_PLAN_BF16_WGRAD, 0, -1, pl.bf16_wgrad);
+    w.put(ENDO_PLAN_BF16_DGRAD, 0, -1, pl.bf16_dgrad);
+    w.put(ENDO_PLAN_DGRAD_WEIGHTS, 0, -1, pl.dgrad_weights);
+    w.put(ENDO_PLAN_USE_VIRT, 0, -1, pl.use_virt);
+    w.put(ENDO_PLAN_VIRT_BASE, 0, -1, pl.virt_base);
+    w.put(ENDO_PLAN_VIRT_BASE_W, 0, -1, pl.virt_base_w);
+    w.put(ENDO_PLAN_MATERIALISE, 0, -1, pl.materialise);
+    w.put(ENDO_PLAN_C_FIRST, 0, -1, pl.c_first);
+    w.put(ENDO_PLAN_FIRST_WGRAD, 0, 0, static_cast<int>(pl.first));
+}
+
+template <typename Plan>
+static int serialise_plan(const Plan& pl, int32_t* out, int capacity) {
+    PlanWriter w{out, capacity};
+    write_plan(pl, w);
+    return w.count <= capacity ? w.count : ENDO_E_BADARG;          // (a short buffer: part of the plan is in it, which the error says not to read)
+}
+
+}  // namespace endo
+
+extern "C" int endo_net_last_plan(const endo_net* net, int pass, int32_t* out, int capacity) {
+    if (!net || !out || capacity < 0) return ENDO_E_BADARG;
+    if (pass == ENDO_PASS_FWD) return net->last_fwd ? serialise_plan(*net->last_fwd, out, capacity) : ENDO_E_BADARG;
+    if (pass == ENDO_PASS_BWD) return net->last_bwd ? serialise_plan(*net->last_bwd, out, capacity) : ENDO_E_BADARG;
+    return ENDO_E_BADARG;
+}
+
+extern "C" int endo_net_plan_query(const endo_net* net, int pass, int training, const float* params, float* bn_running, const float* x,
+                                   float* tape, float* grads, float* gradws, int32_t* out, int capacity) {
+    if (!net || !out || capacity < 0 || !params || !tape) return ENDO_E_BADARG;
+    if (pass == ENDO_PASS_FWD) {          // the Ctx of endo_net_fwd
+        if (!bn_running) return ENDO_E_BADARG;
+        const Ctx c{net, params, bn_running, tape, nullptr, nullptr, training, nullptr};
+        return serialise_plan(plan_fwd(c), out, capacity);
+    }
+    if (pass == ENDO_PASS_BWD) {          // the Ctx of endo_net_bwd
+        if (!x || !grads || !gradws) return ENDO_E_BADARG;
+        Ctx c{net, params, nullptr, tape, grads, gradws, training, nullptr};
+        c.x = x;
+        return serialise_plan(plan_bwd(c), out, capacity);
+    }
+    return ENDO_E_BADARG;
+}
+
+extern "C" const char* endo_net_plan_name(int kind, int value) {
+    if (kind < 0 || kind >= ENDO_PLAN_KIND_COUNT) return nullptr;
+    const PlanKind& k = kPlanKinds[kind];
+    if (value == -1) return k.name;
+    return (k.values && value >= 0 && value < k.count) ? k.values[value] : nullptr;
 }

@@ -292,7 +292,7 @@ class FCDenseNet(nn.Module):
 
     # kernel-form / precision options (include/endo_hip.h ENDO_OPT_*) belong to THIS module object -- like everything else about a
     # reference module (train.py:191): they apply to every native handle it owns, present and future, and to no other model
-    _OPTION_DEFAULTS = {0: 5, 1: 3, 2: 2, 3: 1024, 4: 0, 5: 1, 7: 1, 8: 1, 9: 3}          # default_options() of csrc/net.hip (id 6 is retired)
+    _OPTION_DEFAULTS = {0: 5, 1: 3, 2: 2, 3: 1024, 4: 0, 5: 1, 7: 1, 8: 1, 9: 3, 10: 1}          # default_options() of csrc/net.hip (id 6 is retired)
 
     def set_kernel_option(self, option_id, value):
         """Returns the previous value."""
@@ -313,6 +313,22 @@ class FCDenseNet(nn.Module):
 
     def kernel_option(self, option_id):
         return self.__dict__.get("_kernel_options", {}).get(int(option_id), self._OPTION_DEFAULTS[int(option_id)])
+
+    def last_plan(self, n, h, w, groups=1, entries=False):
+        """Kernel forms the last forward and (where one ran) backward pass over an ``n x 3 x h x w`` batch in ``groups`` groups took:
+        ``{(kind, layer / block / level): name}`` (plan_entries' fields with ``entries=True``; include/endo_hip.h, endo_net_last_plan)."""
+        key = (n // groups, h, w, groups)
+        if key not in self._handles:
+            raise RuntimeError("no pass has run at %d x %d x %d in %d group(s)" % (n, h, w, groups))
+        lib = _lib.load()
+        out = []
+        for which in (PLAN_FWD, PLAN_BWD):
+            raw = (ctypes.c_int32 * PLAN_MAX_INTS)()
+            count = lib.endo_net_last_plan(self._handles[key][0], which, raw, PLAN_MAX_INTS)
+            if count < 0 and which == PLAN_FWD:
+                raise RuntimeError("no forward pass has run on this handle yet")
+            out += plan_entries(raw, max(count, 0))
+        return out if entries else {(kind, index): value for kind, index, _, value in out}
 
     def __del__(self):
         try:
@@ -520,6 +536,48 @@ class FCDenseNet(nn.Module):
             hh, ww = h >> lvl, w >> lvl
             levels.append(tape[off:off + n * ch * hh * ww].view(n, ch, hh, ww))
         return out, levels
+
+
+# ---------------------------------------------------------------------------------------------
+# the plan of a pass, readable (include/endo_hip.h: endo_net_last_plan / endo_net_plan_query / endo_net_plan_name)
+# ---------------------------------------------------------------------------------------------
+PLAN_FWD, PLAN_BWD = 0, 1          # ENDO_PASS_*
+PLAN_MAX_INTS = 1024               # ENDO_PLAN_MAX_INTS
+
+
+def plan_entries(raw, count):
+    """The library's (kind, index, level, value) quadruples as ``[(kind name, index, level, form name or number)]``."""
+    lib = _lib.load()
+    out = []
+    for i in range(0, count, 4):
+        kind, index, level, value = raw[i:i + 4]
+        name = lib.endo_net_plan_name(kind, value) if value >= 0 else None
+        out.append((lib.endo_net_plan_name(kind, -1).decode(), index, level, name.decode() if name else value))
+    return out
+
+
+def plan_query(n, h, w, groups=1, options=None, training=True, entries=False, x_offset=0):
+    """The kernel forms a forward + backward pass over an ``n x 3 x h x w`` batch in ``groups`` groups WOULD take under ``options``
+    ({ENDO_OPT_* id: value}), in last_plan's form.  Nothing is launched and no memory is touched (the buffers are made-up 256-byte-aligned
+    addresses, as torch's allocations are -- the image tensor's moved by ``x_offset`` bytes), so this runs on a machine without a GPU."""
+    lib = _lib.load()
+    hnd = ctypes.c_void_p()
+    _lib.check(lib.endo_net_create_grouped(ctypes.byref(hnd), n // groups, h, w, groups), "endo_net_create_grouped")
+    try:
+        for option_id, value in (options or {}).items():
+            if lib.endo_net_set_option(hnd, int(option_id), int(value)) == -1 and int(option_id) not in FCDenseNet._OPTION_DEFAULTS:
+                raise ValueError("unknown kernel option %d" % option_id)
+        params, bn, x, tape, grads, gradws = (ctypes.c_void_p(((i + 1) << 40) + (x_offset if i == 2 else 0)) for i in range(6))
+        out = []
+        for which in (PLAN_FWD, PLAN_BWD):
+            raw = (ctypes.c_int32 * PLAN_MAX_INTS)()
+            count = lib.endo_net_plan_query(hnd, which, 1 if training else 0, params, bn, x, tape, grads, gradws, raw, PLAN_MAX_INTS)
+            if count < 0:
+                raise RuntimeError("endo_net_plan_query failed: %d" % count)
+            out += plan_entries(raw, count)
+    finally:
+        lib.endo_net_destroy(hnd)
+    return out if entries else {(kind, index): value for kind, index, _, value in out}
 
 
 def FCDenseNet57(n_classes):

@@ -67,8 +67,10 @@ extern "C" {
  * endo_display_panel_shape and endo_validation_accumulate; then endo_depth_metrics, endo_evaluate_validation,
  * endo_evaluate_validation_workspace_bytes and endo_evaluate_validation_panel_shape -- entry points only, no existing signature
  * changes: additive, so the version stays 6; then the option "MFMA X3" (id 6: fp32 products as three-term bf16 splits; retired and not reused) and the values
- * ENDO_OPT_WINO_FWD = 3 / 4 and ENDO_OPT_WGRAD_F34 = 2 are removed -- no entry point and no signature changes. */
-#define ENDO_ABI_VERSION 6
+ * ENDO_OPT_WINO_FWD = 3 / 4 and ENDO_OPT_WGRAD_F34 = 2 are removed -- no entry point and no signature changes.
+ * 7: the plan of a pass can be read: adds endo_net_last_plan, endo_net_plan_query, endo_net_plan_name and the option
+ * ENDO_OPT_CHIP_DIVISOR; no existing signature changes. */
+#define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
 const char* endo_error_string(int code);
@@ -287,7 +289,14 @@ int endo_net_groups(const endo_net* net);
  *   ENDO_OPT_TD_PERSIST      transition-down layers (models.py:56-67) with 96 / 144 channels on whole 32 x 8 tiles (levels 0 / 1 of configs[1]) as
  *                            persistent blocks that keep the 1x1 weights in LDS: bit 0 (1) = the data gradient (csrc/td_dgrad_kernels.h; also the
  *                            128-pixel-run kernel where the pooled rows have no whole code dwords), bit 1 (2) = the training-mode forward
- *                            (csrc/td_fwd_kernels.h).  Default 3; 0 = the per-tile kernels (conv_dma_kernel).  Same function up to summation order. */
+ *                            (csrc/td_fwd_kernels.h).  Default 3; 0 = the per-tile kernels (conv_dma_kernel).  Same function up to summation order.
+ *   ENDO_OPT_CHIP_DIVISOR    d >= 1 (default 1; smaller values count as 1): plan as if the chip had 1 / d of its compute units.  Every comparison of
+ *                            the plan that asks whether a launch fills the chip sees its tile or chunk count times d (the tile counts of the forward
+ *                            and transition-up forms and the split-K slice arithmetic, the Winograd data gradient's tiles, the F(3x3,4x4) and
+ *                            n-split minimums of the weight gradients), and the persistent launches are sized for 1 / d of the device's compute
+ *                            units (at least one), rounded as each launch rounds.  Shape and alignment conditions are untouched.  For tests: a
+ *                            grid of 1 / d of the benchmark's pixels takes the benchmark grid's kernel forms, and its persistent blocks walk as
+ *                            many tiles each.  Same function up to summation order. */
 #define ENDO_OPT_WINO_FWD 0
 #define ENDO_OPT_WINO_DGRAD 1
 #define ENDO_OPT_DGRAD_VEC 2
@@ -298,7 +307,8 @@ int endo_net_groups(const endo_net* net);
 #define ENDO_OPT_WGRAD_F34 7
 #define ENDO_OPT_FINAL_VIRTUAL 8
 #define ENDO_OPT_TD_PERSIST 9
-#define ENDO_OPT_COUNT 10
+#define ENDO_OPT_CHIP_DIVISOR 10
+#define ENDO_OPT_COUNT 11
 int endo_net_set_option(endo_net* net, int option_id, int value);
 int endo_net_get_option(const endo_net* net, int option_id);
 int64_t endo_net_group_stride(const endo_net* net);
@@ -338,6 +348,62 @@ int64_t endo_net_act_offset(const endo_net* net, int level);
 #define ENDO_TAPE_BN_SAVED 1
 #define ENDO_TAPE_POOL 2
 int64_t endo_net_tape_offset(const endo_net* net, int what, int index);
+
+/* The plan of a pass: which kernel form every launch takes (csrc/net.hip: FwdPlan / BwdPlan), decided once at the top of endo_net_fwd /
+ * endo_net_bwd from the grid, the handle's options, the training flag and the alignment of the pass's pointers.
+ *   endo_net_last_plan   the plan the last endo_net_fwd (pass = ENDO_PASS_FWD) / endo_net_bwd (ENDO_PASS_BWD) on this handle followed
+ *   endo_net_plan_query  the plan such a call WOULD follow with these pointers: the same two functions decide it, nothing is launched and
+ *                        no pointer is dereferenced (any addresses of the right alignment do, on a machine without a GPU too).  The forward
+ *                        query reads params, bn_running and tape; the backward query params, x, tape, grads and gradws.
+ * Both write the plan as entries of four int32: (kind, index, level, value), every field of the plan's struct once, and return the
+ * number of int32 written (ENDO_PLAN_MAX_INTS is enough for either pass).  ENDO_E_BADARG: a null handle or `out`, an unknown pass, a
+ * pointer the pass reads is null, a buffer too short for the whole plan (its contents are then unspecified) -- and, from
+ * endo_net_last_plan, a pass that has not run on this handle yet.
+ *   index  dense layer 0..43 (= 4 * block + layer; blocks 0-4 the down path, 5 the bottleneck, 6-10 the up path, coarsest first) for
+ *          DENSE_FWD*, DENSE_WGRAD and NEWMAP (the pass into layer j - 1's maps, j = 1..3); dense block 0..10 for BLOCK_BWD, BASE_PASS and
+ *          WINO3_LAYOUT; level 0..4 for the transitions (TD_*: the level the transition-down reads, TU_*: the level the transition-up
+ *          writes); 0 for the plan-wide fields
+ *   level  the resolution level 0..5 the launch works at, -1 for plan-wide fields
+ *   value  an enumerator of the kind (endo_net_plan_name gives its name) or, for the kinds marked [n], a number (0 / 1 for flags).
+ *          NEWMAP, BASE_PASS and WINO3_LAYOUT of a block whose BLOCK_BWD is PerLayer are decided but not followed.
+ * endo_net_plan_name(kind, value): the enumerator's name, the kind's own name for value = -1, NULL for anything else (static strings). */
+#define ENDO_PASS_FWD 0
+#define ENDO_PASS_BWD 1
+#define ENDO_PLAN_MAX_INTS 1024
+/* forward plan */
+#define ENDO_PLAN_DENSE_FWD 0                 /* Wino4 Wino2_32x16 Wino2_32x8 SplitK Direct32x8 Direct16x8 DirectAuto */
+#define ENDO_PLAN_DENSE_FWD_KSPLIT 1          /* [n] K slices of SplitK, else 0 */
+#define ENDO_PLAN_DENSE_FWD_CHUNK_WEIGHTS 2   /* [n] the layer's prepared weights are in the direct kernel's K-chunk order */
+#define ENDO_PLAN_FWD_BF16 3                  /* [n] */
+#define ENDO_PLAN_WINO4_WEIGHTS 4             /* [n] */
+#define ENDO_PLAN_FUSE_FINAL 5                /* [n] */
+#define ENDO_PLAN_TD_FWD 6                    /* PerTile Persistent */
+#define ENDO_PLAN_TU_FWD 7                    /* Upsample Subpix */
+/* backward plan */
+#define ENDO_PLAN_BLOCK_BWD 8                 /* PerLayer Fused */
+#define ENDO_PLAN_NEWMAP 9                    /* Bf16 Persistent Vec16 Dword */
+#define ENDO_PLAN_BASE_PASS 10                /* Block8 Block8Bf16 Wino3 Wino3Persistent Wino8 */
+#define ENDO_PLAN_WINO3_LAYOUT 11             /* [n] */
+#define ENDO_PLAN_DENSE_WGRAD 12              /* F34 NSplit Taps Direct */
+#define ENDO_PLAN_TD_WGRAD 13                 /* Plain Dma */
+#define ENDO_PLAN_TD_DGRAD 14                 /* Persistent Runs128 Dma Staged */
+#define ENDO_PLAN_TU_WGRAD 15                 /* Subpix Taps Direct */
+#define ENDO_PLAN_TU_DGRAD 16                 /* Subpix32x8 Subpix16x8 Subpix16x4 Plain */
+#define ENDO_PLAN_WGRAD_OVERLAP 17            /* [n] ENDO_OPT_WGRAD_OVERLAP as set */
+#define ENDO_PLAN_BF16_WGRAD 18               /* [n] */
+#define ENDO_PLAN_BF16_DGRAD 19               /* [n] */
+#define ENDO_PLAN_DGRAD_WEIGHTS 20            /* [n] */
+#define ENDO_PLAN_USE_VIRT 21                 /* [n] */
+#define ENDO_PLAN_VIRT_BASE 22                /* [n] */
+#define ENDO_PLAN_VIRT_BASE_W 23              /* [n] */
+#define ENDO_PLAN_MATERIALISE 24              /* [n] channels written out by the final convolution's data-gradient kernel */
+#define ENDO_PLAN_C_FIRST 25                  /* [n] first channel of the final convolution's weight-gradient kernel */
+#define ENDO_PLAN_FIRST_WGRAD 26              /* F34Prep F34 Taps Direct */
+#define ENDO_PLAN_KIND_COUNT 27
+int endo_net_last_plan(const endo_net* net, int pass, int32_t* out, int capacity);
+int endo_net_plan_query(const endo_net* net, int pass, int training, const float* params, float* bn_running, const float* x,
+                        float* tape, float* grads, float* gradws, int32_t* out, int capacity);
+const char* endo_net_plan_name(int kind, int value);
 
 /* ---------------------------------------------------------------------------------------------
  * clip_grad_norm_(params, max_norm) + SGD(momentum) -- reference train.py:327-328, 202

@@ -58,7 +58,7 @@ def test_library_exports_the_validation_entries():
     for name in names:
         assert hasattr(raw, name) and name in ea._lib.SIGNATURES, name
     lib = ea._lib.load()
-    assert lib.endo_abi_version() == 6          # additive: the version stays
+    assert lib.endo_abi_version() == 7          # (additive: these entries left it at 6; 7 since the plan entry points)
     # argument validation happens before any device work
     assert lib.endo_depth_metrics(None, None, None, 1, 2, 2, 1e-8, None, None) == -1
     assert lib.endo_evaluate_validation_workspace_bytes(0, 8, 8) == -1 and lib.endo_evaluate_validation_workspace_bytes(65536, 1, 1) == -1

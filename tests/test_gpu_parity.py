@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import test_plan_coverage as cov          # FP64_CASES: the (shape, groups, options) of every test here that compares with the fp64 oracle
 from oracle import geometry as ogeo, losses as olos, network as onet, schedule as osch, train_step as ostep
 from device_pattern import pattern_of
 
@@ -259,6 +260,17 @@ def make_model(seed, positive_depth=False):
     return state, model.to(dev())
 
 
+def assert_plan(model, n, h, w, groups, takes, lacks=(), what=""):
+    """The passes `model` last ran over n x 3 x h x w samples in `groups` groups took every (kind, form, level) of `takes` and none of `lacks`
+    (FCDenseNet57.last_plan; a level of None in `lacks`: at no level).  What a docstring says runs is asserted with this, not assumed."""
+    entries = model.last_plan(n, h, w, groups, entries=True)
+    cov.assert_takes(entries, takes, what or "%d x %d x %d" % (n, h, w))
+    got = cov.forms_of(entries)
+    present = [t for t in lacks if any(g[:2] == tuple(t[:2]) and (t[2] is None or g[2] == t[2]) for g in got)]
+    assert not present, "%s: the plan takes %s" % (what, present)
+    return got
+
+
 def level_reference(trace, level):
     """Assemble the oracle's view of level buffer `level` (layout: DESIGN.md / net.hip header)."""
     if level == 5:
@@ -266,7 +278,7 @@ def level_reference(trace, level):
     return torch.cat([trace["tu_%d" % level], trace["skip_%d" % level], trace["upnew_%d" % level]], dim=1)
 
 
-@pytest.mark.parametrize("shape", [(2, 32, 32), (2, 64, 96), (1, 128, 160)])
+@pytest.mark.parametrize("shape", cov.shapes("test_gpu_parity.test_network_forward_levels"))
 def test_network_forward_levels(shape):
     n, h, w = shape
     state, model = make_model(51)
@@ -344,7 +356,7 @@ GRAD_TOL = 3e-5          # every parameter gradient: max abs error / the tensor'
                          # oracle's own distance from fp64 on the same pattern; BASELINE.json's bar is 1e-4.
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 96)])          # (2, 128, 160): test_network_backward_kernel_forms runs it in three kernel forms
+@pytest.mark.parametrize("shape", cov.shapes("test_gpu_parity.test_network_backward"))          # (2, 128, 160): test_network_backward_kernel_forms runs it in three kernel forms
 def test_network_backward(shape):
     """All 210 parameter gradients against the fp64 oracle at 1e-4 -- evaluated on the activation pattern the HIP forward
     pass itself took (device_pattern.py).  Without that, the comparison is a lottery: any two finite-precision runs of a
@@ -447,10 +459,19 @@ def test_kernel_options_are_per_model():
         a.set_kernel_option(6, 1)
 
 
-@pytest.mark.parametrize("which,shape", [("winograd", (2, 64, 96)), ("winograd", (2, 128, 160)), ("winograd", (1, 64, 128)),
-                                         ("direct", (2, 64, 96)), ("direct", (2, 128, 160)), ("direct", (1, 64, 128)),
-                                         ("winograd4", (2, 64, 96)), ("winograd4", (2, 128, 160)), ("winograd4", (1, 64, 128)),
-                                         ("nsplit", (2, 128, 256))],          # nsplit: 8 * 128 * 2 = 2048 row chunks at level 0, the fewest that reach the n-split weight-gradient kernel
+KERNEL_FORMS = {          # what each variant of test_network_backward_kernel_forms must run, and must not, at every one of its shapes (assert_plan)
+    "winograd": ([("dense_fwd", "Wino2_32x16", l) for l in (0, 1, 2, 3)] + [("base_pass", "Wino3Persistent", 0), ("dense_wgrad", "F34", 0), ("dense_wgrad", "F34", 2),
+                 ("newmap", "Persistent", 0)], [("dense_fwd", "Wino4", None)]),
+    "winograd4": ([("dense_fwd", "Wino4", l) for l in (0, 1, 2, 3)] + [("base_pass", "Wino3Persistent", 0), ("dense_wgrad", "F34", 0), ("fuse_final", 1, -1), ("virt_base_w", 1, -1)],
+                  [("dense_fwd", "Wino2_32x16", l) for l in (0, 1, 2, 3)]),          # (1 x 64 x 128 forces a Winograd form on levels 4 and 5 too: F(2x2, 3x3) where the height is no multiple of 4)
+    "direct": ([("dense_fwd", "SplitK", 1), ("base_pass", "Block8", 0), ("newmap", "Dword", 0), ("dense_wgrad", "Taps", 0), ("first_wgrad", "Taps", 0)],
+               [("dense_fwd", f, None) for f in ("Wino4", "Wino2_32x16", "Wino2_32x8")] + [("dense_wgrad", "F34", None), ("newmap", "Persistent", None),
+                ("base_pass", "Wino3", None), ("base_pass", "Wino3Persistent", None), ("base_pass", "Wino8", None)]),
+    "nsplit": ([("dense_wgrad", "NSplit", 0), ("dense_wgrad", "Taps", 1)], [("dense_wgrad", "F34", None), ("dense_wgrad", "NSplit", 1)]),
+}
+
+
+@pytest.mark.parametrize("which,shape", [(c.tag, c.shape) for c in cov.cases("test_gpu_parity.test_network_backward_kernel_forms")],          # nsplit: 8 * 128 * 2 = 2048 row chunks at level 0, the fewest that reach the n-split weight-gradient kernel
                          ids=lambda v: "x".join(str(i) for i in v) if isinstance(v, tuple) else v)
 def test_network_backward_kernel_forms(shape, which):
     """The Winograd kernels (dense-layer forward, fused base-channel data gradient, F(3x3, 4x4) weight gradient where the height is a multiple of 16
@@ -467,7 +488,10 @@ def test_network_backward_kernel_forms(shape, which):
     # sits at 1.9e-6 .. 2.2e-6 of its maximum (round 4's textbook points: 4e-6 .. 6e-6; the other forms: 0.9e-6 .. 1.1e-6) and is held to the
     # same 1e-5 as every form; the gradients -- taken on the pass's own pattern, from activations that carry the forward's rounding --
     # measured 2.0e-5 .. 3.5e-5 (round 4: 5.8e-5 .. 1.1e-4; the other forms 0.7e-5 .. 2.2e-5) and are held to 5e-5 (round 4: 1.6e-4).
-    opts = {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 1} if which == "winograd" else {OPT_WINO_MIN_TILES: 1, OPT_WINO_FWD: 5} if which == "winograd4" else ({OPT_WGRAD_F34: 0} if which == "nsplit" else {OPT_WINO_FWD: 0, OPT_WINO_DGRAD: 0, OPT_DGRAD_VEC: 0, OPT_WGRAD_F34: 0})
+    # What runs is asserted from the pass's plan (KERNEL_FORMS): "winograd" the F(2x2, 3x3) forward on 32 x 16 tiles at levels 0-3, the persistent
+    # phase-skewed base pass at level 0 (the other levels' widths are no multiple of 32 but at 1 x 64 x 128: Block8 there), F(3x3, 4x4) weight gradients
+    # at levels 0-2; "direct" none of the Winograd forms -- split-K and the auto-tiled direct forward, Block8, dword new-map passes, tap-folded weight gradients.
+    opts = cov.case("test_gpu_parity.test_network_backward_kernel_forms", which, shape).options
     with kernel_options(opts):
         state, model = make_model(62)
         rng = np.random.default_rng(16)
@@ -478,6 +502,7 @@ def test_network_backward_kernel_forms(shape, which):
         (pattern,) = pattern_of(y, model, n, h, w)
         (y * cot.to(dev())).sum().backward()
         torch.cuda.synchronize()
+    assert_plan(model, n, h, w, 1, *KERNEL_FORMS[which], what="%s %s" % (which, shape))
     params = dict(model.named_parameters())
     g64p = reference_grads(state, x, cot, torch.float64, pattern)
     y64 = onet.forward(state_as(state, torch.float64), x.double(), training=True, pattern=pattern)
@@ -491,7 +516,7 @@ def test_network_backward_eval_mode():
     """Backward through the network in eval mode (running statistics, no batch-statistic terms in the BN backward; what a caller
     fine-tuning with frozen BN would run -- endo_net_bwd(training = 0)): all 210 gradients against the fp64 oracle on the pass's
     own activation pattern, the bound of the training-mode test."""
-    n, h, w = 2, 64, 96
+    n, h, w = cov.case("test_gpu_parity.test_network_backward_eval_mode", "").shape
     state, model = make_model(68)
     rng = np.random.default_rng(19)
     # running statistics that are not the initial (0, 1): take them from one training-mode pass of the oracle
@@ -526,14 +551,15 @@ BF16_GRAD_TOL = 1e-1      # ... and every parameter gradient, max error / the te
                           # bottleneck and first up block, whose BN normalises over 2 x (2 x 3) ... 2 x (16 x 20) values)
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 96), (2, 128, 160)])          # (a development mode, bench.py --config 5; the second shape has the >= 2048 row chunks at level 0 that select the n-split weight-gradient kernel's bf16 branch, which bench.py --config 5 runs)
+@pytest.mark.parametrize("shape", cov.shapes("test_gpu_parity.test_bf16_operand_mode_on_pattern"))          # (a development mode, bench.py --config 5; neither shape has the 2048 row chunks at level 0 that select the n-split weight-gradient kernel's bf16 branch -- 2 x 128 x 160 has 1280 -- which bench.py --config 5 runs: test_gpu_plan_forms.py's model-256x320-bf16 case takes it)
 def test_bf16_operand_mode_on_pattern(shape):
     """ENDO_OPT_MFMA_BF16 = 1 (the mixed-precision mode behind bench.py --config 5): the dense layers' forward, data-gradient and
     weight-gradient kernels round their MFMA operands to bf16 and accumulate in fp32; tensors in memory, BN statistics, the
     BN / ReLU / pooling arithmetic, reductions and the optimizer stay fp32.  It is a different function from the fp32 path, so it
     has its own stated tolerance: depth and all 210 gradients against the fp64 oracle evaluated on the activation pattern this
-    very pass took (the comparison that is meaningful for a piecewise-linear network, see test_network_backward).  The second
-    shape is large enough for the n-split weight gradient and the fused data-gradient kernels of the benchmark."""
+    very pass took (the comparison that is meaningful for a piecewise-linear network, see test_network_backward).  Both shapes take
+    the bf16 forms of the fused data-gradient kernels (Block8Bf16, new-map Bf16) at levels 0-3 and the tap-folded weight gradient; the n-split
+    weight gradient of the benchmark needs 2048 row chunks and is not reached here (asserted below)."""
     n, h, w = shape
     with kernel_options({OPT_MFMA_BF16: 1}):
         state, model = make_model(65)
@@ -545,6 +571,7 @@ def test_bf16_operand_mode_on_pattern(shape):
         (pattern,) = pattern_of(y, model, n, h, w)
         (y * cot.to(dev())).sum().backward()
         torch.cuda.synchronize()
+    assert_plan(model, n, h, w, 1, [("fwd_bf16", 1, -1), ("base_pass", "Block8Bf16", 0), ("newmap", "Bf16", 0), ("dense_wgrad", "Taps", 0)], [("dense_wgrad", "NSplit", None)])
     params = dict(model.named_parameters())
     g64p = reference_grads(state, x, cot, torch.float64, pattern)
     y64 = onet.forward(state_as(state, torch.float64), x.double(), training=True, pattern=pattern)
@@ -596,7 +623,7 @@ def reference_pattern(state64, x64):
     return own
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 96), (3, 32, 64)])          # (an odd group size on the smallest grid the five poolings allow; (3, 64, 64) until round 5, 12 s more for the same launches; (2, 128, 160) went in round 4: the grouped pass at that size is covered on the pattern by test_network_backward_kernel_forms, at 2 x 8 x 256 x 320 by test_full_size_pair_backward_on_pattern)
+@pytest.mark.parametrize("shape", cov.shapes("test_gpu_parity.test_forward_pair_is_two_calls"))          # (an odd group size on the smallest grid the five poolings allow; (3, 64, 64) until round 5, 12 s more for the same launches; (2, 128, 160) went in round 4: the grouped pass at that size is covered on the pattern by test_network_backward_kernel_forms, at 2 x 8 x 256 x 320 by test_full_size_pair_backward_on_pattern)
 def test_forward_pair_is_two_calls(shape):
     """forward_pair(x1, x2) -- both frames of a training pair as one grouped batch, every launch covering both, each
     frame with its own BatchNorm batch statistics -- against the oracle's two sequential calls (reference
@@ -653,7 +680,7 @@ def test_forward_pair_is_two_calls(shape):
         assert_close(e2, model(x2.to(dev())), 1e-6, "eval pair 2")
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64), (2, 128, 160)])
+@pytest.mark.parametrize("shape", cov.shapes("test_gpu_parity.test_network_backward_last_block_exact"))
 def test_network_backward_last_block_exact(shape):
     """The layers that are differentiated FIRST (final conv, last up block, its transition-up) see no
     accumulated mask-flip noise, so the kernels behind them -- dgrad with fused BN/ReLU backward,
@@ -1013,6 +1040,16 @@ def test_final_conv_fusions_are_transparent(forced, extra):
         y1, y2 = model.forward_pair(xs[0].to(dev()), xs[1].to(dev()))
         ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
         torch.cuda.synchronize()
+        # what the docstring says runs, from the plan: with bf16 operands nothing is forced (no Winograd form there, and the first convolution
+        # keeps prep_dy + the tap-folded kernel); the forward fusion and the virtual base channels only under "winograd-forms"
+        bf16 = bool(extra.get(OPT_MFMA_BF16))
+        wino = forced and not bf16
+        assert_plan(model, 2 * n, h, w, 2, [("use_virt", virtual, -1), ("fuse_final", int(bool(virtual and wino)), -1), ("virt_base", int(bool(virtual and wino)), -1),
+                                            ("virt_base_w", int(bool(virtual and wino)), -1), ("materialise", 192 if not virtual else 0 if wino else 144, -1),
+                                            ("c_first", 144 if virtual and wino else 0, -1), ("first_wgrad", "Taps" if bf16 else "F34Prep" if virtual else "F34", 0),
+                                            ("dense_fwd", "Wino4", 0) if wino else ("dense_fwd", "SplitK", 0),
+                                            ("newmap", "Bf16" if bf16 else {0: "Dword", 1: "Vec16"}.get(extra.get(OPT_DGRAD_VEC), "Persistent"), 0)],
+                    what="final-conv fusions %s, virtual = %d, %s" % ("forced" if forced else "default", virtual, extra))
         results.append((y1.detach().clone(), y2.detach().clone(), {nm: p.grad.detach().clone() for nm, p in model.named_parameters()}))
     (a1, a2, ga), (b1, b2, gb) = results
     assert_close(a1, b1, 2e-6, "depth of frame 1, fused vs separate final convolution")
@@ -1049,6 +1086,9 @@ def test_persistent_new_map_passes_match_the_per_tile_blocks(shape):
         y1, y2 = model.forward_pair(xs[0].to(dev()), xs[1].to(dev()))
         ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
         torch.cuda.synchronize()
+        # levels 0-3 take the fused block path at these sizes (4 and 5 the per-layer path, which has no new-map passes): all 24 passes in the form under test
+        assert_plan(model, 2 * n, h, w, 2, [("newmap", "Persistent" if form == 2 else "Vec16", l) for l in (0, 1, 2, 3)] + [("use_virt", 1, -1)],
+                    [("newmap", "Vec16" if form == 2 else "Persistent", None)], what="new-map passes, ENDO_OPT_DGRAD_VEC = %d" % form)
         results.append({nm: p.grad.detach().clone() for nm, p in model.named_parameters()})
     ga, gb = results
     gmax = max(float(v.abs().max()) for v in gb.values())
@@ -1071,9 +1111,11 @@ def test_persistent_base_pass_matches_the_per_tile_kernel(shape):
     it also forms the final convolution's weight gradient of the 144 base channels (final_bwd_weight_kernel reads the other 48).  Same
     arithmetic per pixel; sums are added up in another order.  Bounds as for the persistent new-map passes: 5e-5 of each tensor's maximum
     with a floor of 1e-2 of the largest gradient for the tensors whose true gradient is zero.  The Winograd forms are forced on
-    (ENDO_OPT_WINO_MIN_TILES = 1) so that the kernel runs at these sizes: blocks with 48, 96 and 144 base channels take it (odd and even
-    group counts), the 192-channel block keeps the per-tile kernel in both runs.  3 x 96 x 160: runs that cross the samples of a group;
-    8 x 128 x 160: several tiles per block (320 tiles per group on 128 blocks)."""
+    (ENDO_OPT_WINO_MIN_TILES = 1) so that the kernel runs at these sizes: the two level-0 blocks, with 48 and 144 base channels (odd group
+    counts: 3 and 9), take it -- asserted from the plan below.  Level 1 is 48 or 80 pixels wide at these shapes, no multiple of the 32-pixel tile,
+    so its blocks (96 and 192 base channels) run Block8 in both runs; the 96-channel block in the persistent form is
+    test_network_backward_kernel_forms' at 1 x 64 x 128 (against fp64) and the benchmark-grid tests'.  3 x 96 x 160: runs that cross the samples of a
+    group; 8 x 128 x 160: several tiles per block (320 tiles per group on 128 blocks)."""
     n, h, w = shape
     rng = np.random.default_rng(31)
     xs = [torch.from_numpy(rng.uniform(-1, 1, (n, 3, h, w)).astype(np.float32)) for _ in range(2)]
@@ -1087,6 +1129,10 @@ def test_persistent_base_pass_matches_the_per_tile_kernel(shape):
         y1, y2 = model.forward_pair(xs[0].to(dev()), xs[1].to(dev()))
         ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
         torch.cuda.synchronize()
+        got = assert_plan(model, 2 * n, h, w, 2, [("base_pass", "Wino3Persistent" if form == 3 else "Wino3", 0), ("base_pass", "Block8", 1), ("virt_base", 1, -1),
+                                                  ("virt_base_w", int(form == 3), -1), ("c_first", 144 if form == 3 else 0, -1)],
+                          [("base_pass", "Wino3" if form == 3 else "Wino3Persistent", None), ("base_pass", "Wino8", None)], what="base pass, ENDO_OPT_WINO_DGRAD = %d" % form)
+        assert ("base_pass", "Block8", 0) not in got          # both level-0 blocks
         results.append({nm: p.grad.detach().clone() for nm, p in model.named_parameters()})
     ga, gb = results
     gmax = max(float(v.abs().max()) for v in gb.values())
@@ -1109,9 +1155,9 @@ def test_persistent_transition_down_dgrad_matches_the_per_tile_kernel(shape):
     as persistent blocks (csrc/td_dgrad_kernels.h: weights LDS-resident, pooled gradient + argmax codes by 16-byte DMA through a swizzled
     source, x / old gradient requested ahead of a pass's MFMAs) where the level has whole 32 x 8 tiles, instead of one block per
     (tile, 32 output channels) (= 2, conv_dma_kernel<1, 16, 2, IN_UNPOOL, EPI_DGRAD_BN>).  Same products per pixel in the same k order;
-    BN-backward sums in another order.  Bounds as for the other persistent forms.  64 x 96: level 0 only (level 1 is 32 x 48: a partial
-    tile, per-tile kernel in both runs); 96 x 160 and 128 x 160: level 0 (96 channels, two tile buffers) and, at 128 x 160, level 1
-    (144 channels, one buffer: 64 x 80 has partial tiles -- per-tile kernel)."""
+    BN-backward sums in another order.  Bounds as for the other persistent forms.  At all three shapes the form runs at level 0 only (96 channels,
+    two tile buffers): level 1 is 48 or 80 pixels wide, a partial tile, and keeps the per-tile kernel in both runs -- asserted from the plan below.  The
+    144-channel (level 1, one buffer) instantiation runs at the benchmark grids and in test_gpu_plan_forms.py's model cases."""
     n, h, w = shape
     rng = np.random.default_rng(37)
     xs = [torch.from_numpy(rng.uniform(-1, 1, (n, 3, h, w)).astype(np.float32)) for _ in range(2)]
@@ -1124,6 +1170,11 @@ def test_persistent_transition_down_dgrad_matches_the_per_tile_kernel(shape):
         y1, y2 = model.forward_pair(xs[0].to(dev()), xs[1].to(dev()))
         ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
         torch.cuda.synchronize()
+        # level 0 in the form under test; level 1 has a partial tile at every shape here (per-tile LDS-DMA kernel in both runs); with bit 0 set level 3's
+        # pooled rows (no whole code dwords) also go to the 128-pixel-run kernel instead of the register-staged one
+        assert_plan(model, 2 * n, h, w, 2, [("td_dgrad", "Persistent" if form == 3 else "Dma", 0), ("td_dgrad", "Dma", 1), ("td_dgrad", "Runs128" if form == 3 else "Staged", 3),
+                                            ("td_fwd", "Persistent", 0)],
+                    [("td_dgrad", "Persistent", l) for l in ((1, 2, 3, 4) if form == 3 else (None,))], what="transition-down data gradient, ENDO_OPT_TD_PERSIST = %d" % form)
         results.append({nm: p.grad.detach().clone() for nm, p in model.named_parameters()})
     ga, gb = results
     gmax = max(float(v.abs().max()) for v in gb.values())
@@ -1156,6 +1207,8 @@ def test_persistent_transition_down_forward_matches_the_per_tile_kernel(shape):
         model.train()
         y1, y2 = model.forward_pair(xs[0].to(dev()), xs[1].to(dev()))
         torch.cuda.synchronize()
+        assert_plan(model, 2 * n, h, w, 2, [("td_fwd", "Persistent" if form == 3 else "PerTile", 0), ("td_fwd", "PerTile", 1)],          # (level 1: a partial tile at every shape here)
+                    [("td_fwd", "Persistent", l) for l in ((1, 2, 3, 4) if form == 3 else (None,))], what="transition-down forward, ENDO_OPT_TD_PERSIST = %d" % form)
         outs.append((y1.detach().clone(), y2.detach().clone(), {k: v.detach().clone() for k, v in model.state_dict().items() if "running" in k}))
     (a1, a2, ra), (b1, b2, rb) = outs
     assert_close(a1, b1, 1e-6, "depth of frame 1, persistent vs per-tile transition-down forward")
@@ -1185,6 +1238,7 @@ def test_wgrad_overlap_is_transparent(shape):
             loss, _, _, _ = step.losses(batch)
             loss.backward()
             torch.cuda.synchronize()
+            assert_plan(model, 2 * n, h, w, 2, [("wgrad_overlap", overlap, -1), ("dense_wgrad", "F34", 0)], what="overlap %d" % overlap)          # (the step's grouped pair pass)
             grads = model.flat_gradients().clone()
             for _ in range(3):
                 step(batch, lr=1.0e-3)
@@ -1306,7 +1360,9 @@ def test_pair_backward_on_pattern_512x640():
     """configs[3] AT ITS OWN GRID: forward_pair at 2 x (4 x 512 x 640) -- 8 samples per launch, exactly the launches
     ``bench.py --config 3`` times (other grids select other kernel variants and workspace sizes: round 3's partial-buffer overrun
     was such a case) -- all 210 parameter gradients against the fp32 CPU oracle on the pass's own activation pattern (as
-    test_full_size_pair_backward_on_pattern), 1e-4."""
+    test_full_size_pair_backward_on_pattern), 1e-4.  The plan here (asserted equal to the CPU query's): F(4x4, 3x3) forward at levels 0 and 1,
+    Direct16x8 at level 2, split-K in 3 / 5-6 / 9-11 slices at levels 3 / 4 / 5; phase-skewed base passes at levels 0 and 1 (persistent but for the
+    192-channel block), Block8 below; F(3x3, 4x4) weight gradients at all six levels; the fused block path down to the bottleneck."""
     n, h, w = 4, 512, 640
     state, model = make_model(59)
     rng = np.random.default_rng(15)
@@ -1317,6 +1373,7 @@ def test_pair_backward_on_pattern_512x640():
     patterns = pattern_of(y1, model, n, h, w, groups=2)
     ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
     torch.cuda.synchronize()
+    assert model.last_plan(2 * n, h, w, 2, entries=True) == cov.bench_plans()[3][1], "this pass did not follow the plan test_plan_coverage.py reasons about"
     params = dict(model.named_parameters())
     names = onet.trainable_names()
     total = None
@@ -1347,8 +1404,9 @@ def test_train_step_full_size_golden(golden, forward_form):
     7.1e-7, 1 of 185, 6.1e-5 / 8.2e-4.)
 
     One training iteration at the size and through the code path bench.py times -- TrainingStep(pair_forward=True):
-    16 samples per launch, the 32x16 / split-K / n-split / 8-wave fused-dgrad variants that only these grids select --
-    against tests/golden/train_step_8x256x320.npz, which make_golden.py wrote by running the reference's own modules,
+    16 samples per launch, in the forms the plan takes at this grid (asserted below: "default" the plan pinned as
+    tests/test_plan_coverage.py DEFAULT_PLAN; "f23" the same but F(2x2, 3x3) on 32 x 16 tiles at level 0, and no fusion of the final
+    convolution into the last layer's launch) -- against tests/golden/train_step_8x256x320.npz, which make_golden.py wrote by running the reference's own modules,
     torch.optim.SGD and clip_grad_norm_ on the same seeded batch (reference train.py:272-328).
 
     Forward (loss terms, depth, scaled depth, warped depth, BN running statistics): 1e-4 relative, BASELINE.json's bar
@@ -1379,6 +1437,11 @@ def test_train_step_full_size_golden(golden, forward_form):
     assert step.pair_forward
     batch = to_dev(synthetic.make_batch(n, h, w, seed=seed + 10, sparse_points=500))
     loss, dcl, sfl, ex = step.losses(batch)
+    if forward_form == "default":
+        assert model.last_plan(2 * n, h, w, 2, entries=True)[:cov.FWD_ENTRIES] == cov.bench_plans()[1][1][:cov.FWD_ENTRIES]          # (the forward pass; the backward plan: test_full_size_pair_backward_on_pattern)
+    else:
+        assert_plan(model, 2 * n, h, w, 2, [("dense_fwd", "Wino2_32x16", 0), ("dense_fwd", "Wino2_32x8", 1), ("dense_fwd", "DirectAuto", 2), ("fuse_final", 0, -1)],
+                    [("dense_fwd", "Wino4", None)], what="f23")
     problems = []
 
     def check(ok, msg):
@@ -1634,8 +1697,10 @@ def test_warp_consistency_call():
 
 
 def test_full_size_pair_backward_on_pattern():
-    """The grouped 2 x 8 x 256 x 320 pass bench.py times (forward_pair: 16 samples per launch -- the 32x16 forward tiles,
-    split-K coarse levels, n-split weight gradients and 8-wave fused data gradients that only these grids select), all 210
+    """The grouped 2 x 8 x 256 x 320 pass bench.py times (forward_pair: 16 samples per launch; its plan is pinned as text in
+    tests/test_plan_coverage.py DEFAULT_PLAN and must be the plan this pass follows: F(4x4, 3x3) forward at level 0, F(2x2, 3x3) on 32 x 8 tiles at
+    level 1, the auto-tiled direct kernel at level 2, split-K in 3 ... 21 slices below; persistent phase-skewed base passes at levels 0 / 1,
+    persistent new-map passes, F(3x3, 4x4) weight gradients at levels 0-4, sub-pixel transition-up gradients on 32 x 8 / 16 x 8 / 16 x 4 tiles), all 210
     parameter gradients against the CPU oracle evaluated on the activation pattern the pass itself took
     (device_pattern.py), frame by frame with each frame's own BatchNorm statistics.  The oracle runs in fp32 here (fp64 at
     this size costs minutes and 40 GB): both sides then carry fp32 rounding, ~1e-5 each at the smaller sizes, and the bound
@@ -1650,6 +1715,7 @@ def test_full_size_pair_backward_on_pattern():
     patterns = pattern_of(y1, model, n, h, w, groups=2)
     ((y1 * cots[0].to(dev())).sum() + (y2 * cots[1].to(dev())).sum()).backward()
     torch.cuda.synchronize()
+    assert model.last_plan(2 * n, h, w, 2, entries=True) == cov.bench_plans()[1][1], "this pass did not follow the plan test_plan_coverage.py reasons about"
     params = dict(model.named_parameters())
     names = onet.trainable_names()
     total = None
@@ -1685,6 +1751,10 @@ def test_wgrad_f34_against_the_direct_kernels_at_benchmark_size():
         y1, y2 = model.forward_pair(xs[0], xs[1])
         ((y1 * cots[0]).sum() + (y2 * cots[1]).sum()).backward()
         torch.cuda.synchronize()
+        # form 1: F(3x3, 4x4) at levels 0-4, the bottleneck (8 x 10) on the direct kernel; form 0: the n-split kernel at levels 0-2, the tap-folded one at 3 and 4
+        assert_plan(model, 2 * n, h, w, 2, [("dense_wgrad", "F34", l) for l in range(5)] + [("dense_wgrad", "Direct", 5), ("first_wgrad", "F34Prep", 0)] if form else
+                    [("dense_wgrad", "NSplit", l) for l in (0, 1, 2)] + [("dense_wgrad", "Taps", 3), ("dense_wgrad", "Taps", 4), ("dense_wgrad", "Direct", 5), ("first_wgrad", "Taps", 0)],
+                    [] if form else [("dense_wgrad", "F34", None)], what="ENDO_OPT_WGRAD_F34 = %d" % form)
         grads[form] = {nm: p.grad.detach().clone() for nm, p in model.named_parameters()}
     model.set_kernel_option(OPT_WGRAD_F34, 1)
     worst_dense, worst_other = (0.0, ""), (0.0, "")

@@ -27,6 +27,7 @@ import test_gpu_augment as t_aug
 import test_gpu_bf16 as t_16
 import test_gpu_evaluate as t_eval
 import test_gpu_parity as tp
+import test_plan_coverage as cov
 import test_gpu_scatter as t_scat
 import test_gpu_validation as t_val
 import test_reader as t_read
@@ -332,13 +333,27 @@ def test_twin_run_at_portrait_grids(shape, form, storage):
     twin_run(shape, form, storage)
 
 
-@pytest.mark.parametrize("form", ["default", "winograd", "winograd4", "direct"])
+PORTRAIT_FORMS = {          # what each form of test_portrait_network_backward_on_pattern runs at 2 x 160 x 96 (tp.assert_plan: takes, lacks)
+    "default": ([("dense_fwd", "SplitK", 1), ("dense_wgrad", "F34", 0), ("dense_wgrad", "F34", 1), ("dense_wgrad", "Taps", 2), ("base_pass", "Block8", 0), ("newmap", "Persistent", 0),
+                 ("td_dgrad", "Persistent", 0), ("td_fwd", "Persistent", 0), ("tu_dgrad", "Subpix16x4", 0), ("first_wgrad", "F34Prep", 0)], [("dense_fwd", "Wino4", None)]),
+    "winograd": ([("dense_fwd", "Wino2_32x16", l) for l in (0, 1, 2, 3)] + [("base_pass", "Wino3Persistent", 0), ("base_pass", "Block8", 1), ("dense_wgrad", "F34", 1)], [("dense_fwd", "Wino4", None)]),
+    "winograd4": ([("dense_fwd", "Wino4", l) for l in (0, 1, 2, 3)] + [("base_pass", "Wino3Persistent", 0), ("fuse_final", 1, -1)], [("dense_fwd", "Wino2_32x16", None)]),
+    "direct": ([("dense_fwd", "SplitK", 1), ("dense_wgrad", "Taps", 0), ("base_pass", "Block8", 0), ("newmap", "Dword", 0), ("td_dgrad", "Dma", 0), ("td_fwd", "PerTile", 0),
+                ("use_virt", 0, -1), ("materialise", 192, -1), ("first_wgrad", "Taps", 0)],
+               [("dense_wgrad", "F34", None), ("newmap", "Persistent", None), ("td_dgrad", "Persistent", None), ("td_dgrad", "Runs128", None), ("td_fwd", "Persistent", None)]),
+}
+
+
+@pytest.mark.parametrize("form", [c.tag for c in cov.cases("test_gpu_workspace_contract.test_portrait_network_backward_on_pattern")])
 def test_portrait_network_backward_on_pattern(form):
     """2 x 160 x 96 -- a portrait grid -- through the fp64 oracle on the pass's own activation pattern, with the bounds of
-    test_network_backward_kernel_forms (depth 1e-5; gradients GRAD_TOL, 5e-5 for the F(4x4, 3x3) forward, as there), on poisoned buffers."""
-    n, h, w = 2, 160, 96
+    test_network_backward_kernel_forms (depth 1e-5; gradients GRAD_TOL, 5e-5 for the F(4x4, 3x3) forward, as there), on poisoned buffers.
+    What each form runs here is asserted from the pass's plan (PORTRAIT_FORMS)."""
+    case = cov.case("test_gpu_workspace_contract.test_portrait_network_backward_on_pattern", form)
+    assert case.options == FORMS[form]
+    n, h, w = case.shape
     with contract():
-        with tp.kernel_options(FORMS[form]):
+        with tp.kernel_options(case.options):
             state, model = tp.make_model(62)
         rng = np.random.default_rng(16)
         x = torch.from_numpy(rng.uniform(-1, 1, (n, 3, h, w)).astype(np.float32))
@@ -348,6 +363,7 @@ def test_portrait_network_backward_on_pattern(form):
         (pattern,) = tp.pattern_of(y, model, n, h, w)
         (y * cot.to(tp.dev())).sum().backward()
         torch.cuda.synchronize()
+        tp.assert_plan(model, n, h, w, 1, *PORTRAIT_FORMS[form], what="portrait %s" % form)
     g64p = tp.reference_grads(state, x, cot, torch.float64, pattern)
     y64 = onet.forward(tp.state_as(state, torch.float64), x.double(), training=True, pattern=pattern)
     print("portrait %s: depth max err / max |depth| = %.2e" % (form, tp.rel_err(y, y64)))
@@ -357,29 +373,29 @@ def test_portrait_network_backward_on_pattern(form):
 
 
 # One shape per fixed scratch bound of endo_net_create_grouped that a SMALL input reaches better than the benchmark grids do (poison and guard
-# runs: a forward and a backward pass, everything finite, every guard intact).  (shape, kernel forms, bound, use):
+# runs: a forward and a backward pass, everything finite, every guard intact).  (shape, kernel forms, the plan entries the use rests on -- asserted --, bound, use):
 BOUND_CASES = [
     # kGrowth * 163840 floats of split-K partials (dense_fwd): ksplit * n * plane floats per output channel.  The split form is taken with
     # tiles_small = ceil(w / 16) * ceil(h / 8) * n < 512 and ksplit = ceil(768 / tiles_small) from 256 tiles on: 3 slices up to 383 tiles, 2 from 384.
     # 383 x 32 x 64: level 2 is 8 x 16 = one whole tile per sample, 383 tiles, cin 144 ... 276 (9 ... 18 K-chunks) -> ksplit = 3:
     # 3 * 383 * 128 = 147 072 of 163 840 floats per channel = 89.8 %.  No input comes closer: 511 tiles x 2 slices is 130 816 (79.8 %).
-    pytest.param((383, 32, 64), "default", id="split-k-partials-383x32x64-89.8pct"),
+    pytest.param((383, 32, 64), "default", [("dense_fwd_ksplit", 3, 2), ("dense_fwd", "SplitK", 2)], id="split-k-partials-383x32x64-89.8pct"),
     # kNsScratchFloats (n-split weight gradient, 1024 * 12 block-groups): a launch uses blocks * groups with (blocks, groups) <= (1024, 4), (768, 8),
     # (512, 12) or (256, 24): 6 144 of 12 288 = 50 % at most, whatever the input.  8 x 128 x 160 with the F(3x3, 4x4) form off: level 0 has
     # 5 120 row chunks (>= 2 048: the n-split kernel), denseBlocksUp.4's last layer cin = 180 -> 12 groups x 512 blocks = 50 %.
-    pytest.param((8, 128, 160), "direct", id="nsplit-partials-8x128x160-50pct"),
+    pytest.param((8, 128, 160), "direct", [("dense_wgrad", "NSplit", 0), ("dense_wgrad", "Taps", 1)], id="nsplit-partials-8x128x160-50pct"),
     # kSpScratchFloats (sub-pixel transition-up weight gradient, 384 blocks): 6 x 128 x 160 -> the 64 x 80 low-resolution grid of the last transition
     # up has 3 * 64 * 6 = 1 152 = 3 * 384 chunks -> 384 blocks = 100 % of kSpScratchFloats.  (The region holds max(kNs, kSp, 4 * kF34) = kNs floats:
     # 64 % of the region; nothing reaches its end, the n-split form that sized it stops at 50 %.)
     # kFwPartBlocks * 192 doubles (final-conv weight partials of the persistent base pass at level 0): blocks x count doubles with
     # min(CU count, 512) = 256 blocks on an MI355X and count = the up block's 144 base channels = 37.5 %, whatever the input; every default-form
     # run at a size that takes the persistent base pass uses them (with ONE sample group they are the last thing in the workspace).
-    pytest.param((6, 128, 160), "default", id="subpixel-partials-6x128x160-100pct"),
+    pytest.param((6, 128, 160), "default", [("tu_wgrad", "Subpix", 0), ("base_pass", "Block8", 0)], id="subpixel-partials-6x128x160-100pct"),
 ]
 
 
-@pytest.mark.parametrize("shape,form", BOUND_CASES)
-def test_shapes_closest_to_the_fixed_scratch_bounds(shape, form):
+@pytest.mark.parametrize("shape,form,takes", BOUND_CASES)
+def test_shapes_closest_to_the_fixed_scratch_bounds(shape, form, takes):
     n, h, w = shape
     with contract() as g:
         with tp.kernel_options(FORMS[form]):
@@ -392,6 +408,7 @@ def test_shapes_closest_to_the_fixed_scratch_bounds(shape, form):
         (y * cot).sum().backward()
         torch.cuda.synchronize()
         g.check()
+        tp.assert_plan(model, n, h, w, 1, takes, what="%s %s" % (shape, form))
         _finite("depth", y.detach().cpu())
         first = model.flat_gradients().cpu()
         _finite("gradients", first)
@@ -403,7 +420,7 @@ def test_shapes_closest_to_the_fixed_scratch_bounds(shape, form):
         tp.assert_close(model.flat_gradients(), 2.0 * first, 1e-5, "accumulated gradient of two passes")
 
 
-@pytest.mark.parametrize("groups", [3, 4])
+@pytest.mark.parametrize("groups", [c.groups for c in cov.cases("test_gpu_workspace_contract.test_three_and_four_sample_groups")])
 def test_three_and_four_sample_groups(groups):
     """endo_net_create_grouped allows up to 4 sample groups and the kernels size LDS by kMaxGroups; no other test goes past 2.  With the bounds of
     test_forward_pair_is_two_calls: each group's depth equals a separate single-group call on that group's input to 2e-5 of the maximum, and the
@@ -412,7 +429,7 @@ def test_three_and_four_sample_groups(groups):
     only (noise_aware): the grouped pass and a separate call sum their BatchNorm statistics in another order and so take different ReLU branches at
     a handful of borderline elements (measured: 13 of 5.7e7 bits with 3 groups, 19 of 7.5e7 with 4; the flat gradients then differ by 1.9e-3 / 7e-4 of their maximum), each an O(1) change of that pixel's gradient
     (device_pattern.py) -- the number of such bits is held to the 1e-5 of all bits that test_network_backward allows two evaluations."""
-    n, h, w = 2, 64, 96
+    n, h, w = cov.case("test_gpu_workspace_contract.test_three_and_four_sample_groups", str(groups)).shape
     rng = np.random.default_rng(31)
     x = torch.from_numpy(rng.uniform(-1, 1, (groups * n, 3, h, w)).astype(np.float32))
     cot = torch.from_numpy(rng.standard_normal((groups * n, 1, h, w)).astype(np.float32))

@@ -79,7 +79,7 @@ static void nl_section(DgradBlockParams p, int n, int64_t plane) {
     DgradBlockParams one = p;
     one.slot_stride = 0;
     vs.push_back({"BN sums in ONE copy (same-address atomics)", [&](hipStream_t s) { return run_nl<NL, 0, 4>(one, s); }});
-    vs.push_back({"persistent blocks (dgrad_newmap_kernel)", [&](hipStream_t s) { return launch_dgrad_newmap<NL>(p, s); }});
+    vs.push_back({"persistent blocks (dgrad_newmap_kernel)", [&](hipStream_t s) { return launch_dgrad_newmap<NL>(p, device_cu_count(), s); }});
     vs.push_back({"dword dY DMA", [&](hipStream_t s) { return run_nl<NL, 0, 1>(p, s); }});
     vs.push_back({"no x / dbuf loads (1)", [&](hipStream_t s) { return run_nl<NL, 1, 4>(p, s); }});
     vs.push_back({"no stores (2)", [&](hipStream_t s) { return run_nl<NL, 2, 4>(p, s); }});
