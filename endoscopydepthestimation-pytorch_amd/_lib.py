@@ -36,6 +36,16 @@ SIGNATURES = {
     "endo_norm_dist_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "endo_scale_inv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "endo_scale_inv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_norm_l2_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_norm_l2_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_norm_l1_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_norm_l1_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_weighted_l2_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_weighted_l2_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_masked_scale_inv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_masked_scale_inv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "endo_sparse_l1_display_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "endo_sparse_l1_display_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "endo_loss_head_workspace_floats": (_L, [_I, _I, _I]),
     "endo_loss_head": (_I, [_P] * 16 + [_F, _F, _F] + [_P] * 4 + [_I, _I, _I, _P]),
     "endo_warp_consistency_workspace_floats": (_L, [_I, _I, _I]),

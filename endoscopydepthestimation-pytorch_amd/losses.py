@@ -4,6 +4,8 @@ kernels.  ``forward(x)`` takes ONE list argument, as in the reference (losses.py
 122-123).  Per-sample sums are reduced with wave shuffles + one fp64 atomic per block; the batch
 mean happens in a one-wave finalize kernel.  AbsRelError and Threshold (losses.py:189-227, the error measures against the sparse
 reconstruction that evaluate.validation_outputs reports) are forward only: one launch of endo_depth_metrics, no atomics.
+The reference's other six classes (NormalizedWeightedMaskedL2Loss, SparseMaskedL1LossDisplay, MaskedL1Loss, NormalizedL2Loss,
+NormalizedL1Loss, MaskedScaleInvariantLoss -- losses.py:35-54, 69-109, 149-186) follow the same pattern, forward and backward.
 """
 
 import torch
@@ -139,6 +141,202 @@ class ScaleInvariantLoss(nn.Module):
     def forward(self, x):
         predicted_depths, goal_depths, boundaries = x
         return _ScaleInvFn.apply(predicted_depths, goal_depths, boundaries, self.epsilon)
+
+
+def _no_grad_inputs(owner, **tensors):
+    """Masks, sparse depths and translations are never differentiated by the reference; asking for such a gradient is an error here,
+    not a silent None."""
+    for name, t in tensors.items():
+        if t.requires_grad:
+            raise RuntimeError("%s: %s get no gradient (the reference does not differentiate them); detach them" % (owner, name))
+
+
+class _RatioFn(torch.autograd.Function):
+    """NormalizedL2Loss / NormalizedL1Loss / NormalizedWeightedMaskedL2Loss: ``name`` picks the endo_<name>_fwd / _bwd pair;
+    ``translations`` is None except for the weighted form."""
+
+    @staticmethod
+    def forward(ctx, depth, warped, masks, translations, eps, name):
+        lib = _lib.load()
+        depth = _lib.dev_f32(depth, "depth maps")
+        warped = _lib.dev_f32(warped, "warped depth maps")
+        masks = _lib.dev_f32(masks, "masks")
+        if depth.dim() != 4 or warped.shape != depth.shape or masks.shape != depth.shape:
+            raise ValueError("%s needs three (N, C, H, W) tensors of one shape" % name)
+        n, hw = depth.shape[0], depth.shape[1] * depth.shape[2] * depth.shape[3]
+        loss = torch.empty((), dtype=torch.float32, device=depth.device)
+        stats = torch.empty((n, 4), dtype=torch.float64, device=depth.device)
+        args = [_lib.ptr(depth), _lib.ptr(warped), _lib.ptr(masks)]
+        if translations is not None:
+            translations = _lib.dev_f32(translations, "translations").reshape(-1)
+            if translations.numel() != 3 * n:
+                raise ValueError("%s needs (N, 3) translations" % name)
+            args.append(_lib.ptr(translations))
+        _lib.check(getattr(lib, "endo_%s_fwd" % name)(*args, _lib.ptr(loss), _lib.ptr(stats), n, hw, eps, _lib.stream()),
+                   "endo_%s_fwd" % name)
+        ctx.save_for_backward(depth, warped, masks, stats)
+        ctx.eps, ctx.name = eps, name
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        lib = _lib.load()
+        depth, warped, masks, stats = ctx.saved_tensors
+        n, hw = depth.shape[0], depth.shape[1] * depth.shape[2] * depth.shape[3]
+        grad_loss = _lib.dev_f32(grad_loss, "grad")
+        g_d = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty_like(warped) if ctx.needs_input_grad[1] else None
+        _lib.check(getattr(lib, "endo_%s_bwd" % ctx.name)(_lib.ptr(grad_loss), _lib.ptr(depth), _lib.ptr(warped), _lib.ptr(masks),
+                                                          _lib.ptr(stats), _lib.ptr(g_d), _lib.ptr(g_w), n, hw, ctx.eps, _lib.stream()),
+                   "endo_%s_bwd" % ctx.name)
+        return g_d, g_w, None, None, None, None
+
+
+class NormalizedWeightedMaskedL2Loss(nn.Module):
+    """reference losses.py:35-54.  The per-sample weights 1 / (1e-8 + |translation|) couple the batch; they are formed on the device."""
+
+    def __init__(self, epsilon=1.0):
+        super().__init__()
+        self.epsilon = float(epsilon)
+
+    def forward(self, x):
+        depth_maps, warped_depth_maps, intersect_masks, translations = x
+        _no_grad_inputs("NormalizedWeightedMaskedL2Loss", masks=intersect_masks, translations=translations)
+        return _RatioFn.apply(depth_maps, warped_depth_maps, intersect_masks, translations, self.epsilon, "weighted_l2")
+
+
+class NormalizedL2Loss(nn.Module):
+    """reference losses.py:94-109.  The mean depth in the denominator is a constant in the backward (the reference's no_grad)."""
+
+    def __init__(self, eps=1.0e-3):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        depth_maps, warped_depth_maps, intersect_masks = x
+        _no_grad_inputs("NormalizedL2Loss", masks=intersect_masks)
+        return _RatioFn.apply(depth_maps, warped_depth_maps, intersect_masks, None, float(self.eps), "norm_l2")
+
+
+class NormalizedL1Loss(nn.Module):
+    """reference losses.py:149-164.  Here the mean depth is differentiated, as the reference's autograd does."""
+
+    def __init__(self, eps=1.0e-3):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        depth_maps, warped_depth_maps, masks = x
+        _no_grad_inputs("NormalizedL1Loss", masks=masks)
+        return _RatioFn.apply(depth_maps, warped_depth_maps, masks, None, float(self.eps), "norm_l1")
+
+
+class _MaskedScaleInvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, sparse, masks, eps):
+        lib = _lib.load()
+        est = _lib.dev_f32(est, "absolute depth estimations")
+        sparse = _lib.dev_f32(sparse, "input sparse depths")
+        masks = _lib.dev_f32(masks, "input sparse masks")
+        if est.dim() != 4 or sparse.shape != est.shape or masks.shape != est.shape:
+            raise ValueError("MaskedScaleInvariantLoss needs three (N, C, H, W) tensors of one shape")
+        n, hw = est.shape[0], est.shape[1] * est.shape[2] * est.shape[3]
+        loss = torch.empty((), dtype=torch.float32, device=est.device)
+        stats = torch.empty((n, 3), dtype=torch.float64, device=est.device)
+        _lib.check(lib.endo_masked_scale_inv_fwd(_lib.ptr(est), _lib.ptr(sparse), _lib.ptr(masks), _lib.ptr(loss), _lib.ptr(stats), n,
+                                                 hw, eps, _lib.stream()), "endo_masked_scale_inv_fwd")
+        ctx.save_for_backward(est, sparse, masks, stats)
+        ctx.eps = eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        lib = _lib.load()
+        est, sparse, masks, stats = ctx.saved_tensors
+        n, hw = est.shape[0], est.shape[1] * est.shape[2] * est.shape[3]
+        grad_loss = _lib.dev_f32(grad_loss, "grad")
+        g_e = torch.empty_like(est) if ctx.needs_input_grad[0] else None
+        _lib.check(lib.endo_masked_scale_inv_bwd(_lib.ptr(grad_loss), _lib.ptr(est), _lib.ptr(sparse), _lib.ptr(masks), _lib.ptr(stats),
+                                                 _lib.ptr(g_e), n, hw, ctx.eps, _lib.stream()), "endo_masked_scale_inv_bwd")
+        return g_e, None, None, None
+
+
+class MaskedScaleInvariantLoss(nn.Module):
+    """reference losses.py:167-186: ScaleInvariantLoss against sparse depths.  The log ratio is selected where the sparse depth is at
+    least 0.5 (0 elsewhere, mask or no mask); an empty mask gives NaN, as the reference's 0 / 0 does."""
+
+    def __init__(self, epsilon=1.0e-8):
+        super().__init__()
+        self.epsilon = float(epsilon)
+
+    def forward(self, x):
+        absolute_depth_estimations, input_sparse_depths, input_sparse_masks = x
+        _no_grad_inputs("MaskedScaleInvariantLoss", sparse_depths=input_sparse_depths, masks=input_sparse_masks)
+        return _MaskedScaleInvFn.apply(absolute_depth_estimations, input_sparse_depths, input_sparse_masks, self.epsilon)
+
+
+class MaskedL1Loss(nn.Module):
+    """reference losses.py:82-91: the photometric term.  Arithmetically SparseMaskedL1Loss with C image channels under the
+    (N, 1, H, W) mask, so it runs on the same kernels (endo_sparse_l1_fwd / _bwd)."""
+
+    def __init__(self, epsilon=1.0):
+        super().__init__()
+        self.epsilon = float(epsilon)
+
+    def forward(self, x):
+        images, twice_warped_images, intersect_masks = x
+        _no_grad_inputs("MaskedL1Loss", masks=intersect_masks)
+        _one_channel_mask("MaskedL1Loss", images, twice_warped_images, intersect_masks)
+        return _SparseL1Fn.apply(images, twice_warped_images, intersect_masks, self.epsilon)
+
+
+def _one_channel_mask(owner, maps, maps_hat, masks):
+    if maps.dim() != 4 or maps_hat.shape != maps.shape or tuple(masks.shape) != (maps.shape[0], 1, maps.shape[2], maps.shape[3]):
+        raise ValueError("%s needs two (N, C, H, W) tensors and an (N, 1, H, W) mask" % owner)
+
+
+class _SparseL1DisplayFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, flows_hat, masks, eps):
+        lib = _lib.load()
+        flows = _lib.dev_f32(flows, "flows")
+        flows_hat = _lib.dev_f32(flows_hat, "flows from depth")
+        masks = _lib.dev_f32(masks, "sparse masks")
+        n, c, h, w = flows.shape
+        out = torch.empty((n,), dtype=torch.float32, device=flows.device)
+        stats = torch.empty((n, 2), dtype=torch.float64, device=flows.device)
+        _lib.check(lib.endo_sparse_l1_display_fwd(_lib.ptr(flows), _lib.ptr(flows_hat), _lib.ptr(masks), _lib.ptr(out), _lib.ptr(stats),
+                                                  n, c, h * w, eps, _lib.stream()), "endo_sparse_l1_display_fwd")
+        ctx.save_for_backward(flows, flows_hat, masks, stats)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        flows, flows_hat, masks, stats = ctx.saved_tensors
+        n, c, h, w = flows.shape
+        grad_out = _lib.dev_f32(grad_out, "grad")
+        g_f = torch.empty_like(flows) if ctx.needs_input_grad[0] else None
+        g_h = torch.empty_like(flows_hat) if ctx.needs_input_grad[1] else None
+        _lib.check(lib.endo_sparse_l1_display_bwd(_lib.ptr(grad_out), _lib.ptr(flows), _lib.ptr(flows_hat), _lib.ptr(masks),
+                                                  _lib.ptr(stats), _lib.ptr(g_f), _lib.ptr(g_h), n, c, h * w, ctx.eps, _lib.stream()),
+                   "endo_sparse_l1_display_bwd")
+        return g_f, g_h, None, None
+
+
+class SparseMaskedL1LossDisplay(nn.Module):
+    """reference losses.py:69-79: SparseMaskedL1Loss per sample, the (N,) vector the reference's outlier detection reads."""
+
+    def __init__(self, epsilon=1.0):
+        super().__init__()
+        self.epsilon = float(epsilon)
+
+    def forward(self, x):
+        flows, flows_from_depth, sparse_masks = x
+        _no_grad_inputs("SparseMaskedL1LossDisplay", masks=sparse_masks)
+        _one_channel_mask("SparseMaskedL1LossDisplay", flows, flows_from_depth, sparse_masks)
+        return _SparseL1DisplayFn.apply(flows, flows_from_depth, sparse_masks, self.epsilon)
 
 
 _consistency_ws = {}

@@ -69,7 +69,8 @@ extern "C" {
  * changes: additive, so the version stays 6; then the option "MFMA X3" (id 6: fp32 products as three-term bf16 splits; retired and not reused) and the values
  * ENDO_OPT_WINO_FWD = 3 / 4 and ENDO_OPT_WGRAD_F34 = 2 are removed -- no entry point and no signature changes.
  * 7: the plan of a pass can be read: adds endo_net_last_plan, endo_net_plan_query, endo_net_plan_name and the option
- * ENDO_OPT_CHIP_DIVISOR; no existing signature changes. */
+ * ENDO_OPT_CHIP_DIVISOR; no existing signature changes; since then (unchanged by additions) endo_norm_l2_*, endo_norm_l1_*,
+ * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each). */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -163,6 +164,48 @@ int endo_scale_inv_fwd(const float* pred, const float* goal, const float* bounda
 int endo_scale_inv_bwd(const float* grad_loss, const float* pred, const float* goal,
                        const float* boundary, const double* stats,
                        float* grad_pred, float* grad_goal, int n, int hw, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The rest of the reference's losses.py.  As above: asynchronous on `stream`, ENDO_E_BADARG before any device work, `stats` is
+ * zeroed by the forward and read by the backward, a NULL gradient pointer means that gradient is not requested.  All maps
+ * n x hw fp32 (hw = C * H * W of one sample); masks, sparse depths and translations get no gradient.  Additive: the version stays 7.
+ * MaskedL1Loss (losses.py:87-91) is endo_sparse_l1_* with c image channels and its n x 1 x H x W mask.
+ *
+ * NormalizedL2Loss.forward -- reference losses.py:99-109
+ * stats: n x 4 fp64 [sum m*d, sum m, sum m(d-dw)^2, sum m(d^2+dw^2)]; the mean depth is a constant in the backward (no_grad)
+ * ------------------------------------------------------------------------------------------- */
+int endo_norm_l2_fwd(const float* depth, const float* warped, const float* mask,
+                     float* loss, double* stats, int n, int hw, float eps, void* stream);
+int endo_norm_l2_bwd(const float* grad_loss, const float* depth, const float* warped, const float* mask,
+                     const double* stats, float* grad_depth, float* grad_warped,
+                     int n, int hw, float eps, void* stream);
+/* NormalizedL1Loss.forward -- reference losses.py:154-164
+ * stats: n x 4 fp64 [sum m*d, sum m, sum m|d-dw|, sum m(|d|+|dw|)]; the mean depth IS differentiated (d 1e-5 mu / d depth) */
+int endo_norm_l1_fwd(const float* depth, const float* warped, const float* mask,
+                     float* loss, double* stats, int n, int hw, float eps, void* stream);
+int endo_norm_l1_bwd(const float* grad_loss, const float* depth, const float* warped, const float* mask,
+                     const double* stats, float* grad_depth, float* grad_warped,
+                     int n, int hw, float eps, void* stream);
+/* NormalizedWeightedMaskedL2Loss.forward -- reference losses.py:40-54.  translations: n x 3; the weights 1 / (1e-8 + |t_n|) are
+ * formed on the device.  stats: n x 4 fp64 [sum m(d-dw)^2, sum m(d^2+dw^2), w_n, sum_n w_n] */
+int endo_weighted_l2_fwd(const float* depth, const float* warped, const float* mask, const float* translations,
+                         float* loss, double* stats, int n, int hw, float eps, void* stream);
+int endo_weighted_l2_bwd(const float* grad_loss, const float* depth, const float* warped, const float* mask,
+                         const double* stats, float* grad_depth, float* grad_warped,
+                         int n, int hw, float eps, void* stream);
+/* MaskedScaleInvariantLoss.forward -- reference losses.py:173-186.  r = 0 where sparse < 0.5 (selected, not multiplied), else
+ * log(est + eps) - log(sparse).  stats: n x 3 fp64 [sum m r^2, sum m r, sum m].  The gradient goes to the estimations only. */
+int endo_masked_scale_inv_fwd(const float* est, const float* sparse, const float* mask,
+                              float* loss, double* stats, int n, int hw, float eps, void* stream);
+int endo_masked_scale_inv_bwd(const float* grad_loss, const float* est, const float* sparse, const float* mask,
+                              const double* stats, float* grad_est, int n, int hw, float eps, void* stream);
+/* SparseMaskedL1LossDisplay.forward -- reference losses.py:74-79: endo_sparse_l1_fwd's sums, out: the (n,) per-sample vector and
+ * no batch mean; grad_out: (n,) */
+int endo_sparse_l1_display_fwd(const float* flows, const float* flows_hat, const float* mask,
+                               float* out, double* stats, int n, int c, int hw, float eps, void* stream);
+int endo_sparse_l1_display_bwd(const float* grad_out, const float* flows, const float* flows_hat,
+                               const float* mask, const double* stats, float* grad_flows, float* grad_hat,
+                               int n, int c, int hw, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The loss head of a training iteration in one call -- reference train.py:279-315 (depth scaling, flow from depth, boundary
