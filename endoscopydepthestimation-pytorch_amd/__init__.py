@@ -12,6 +12,7 @@ The directory name carries a hyphen, so import it with
 
 from . import _lib, augment, dataset, display, distributed, evaluate, losses, models, optim, reader, scatter, scheduler, synthetic, train_step, utils  # noqa: F401
 from .models import FCDenseNet57, DepthScalingLayer, DepthWarpingLayer, FlowfromDepthLayer  # noqa: F401
+from .models import images_warping, _bilinear_interpolate, _warp_coordinate_generate  # noqa: F401
 from .losses import SparseMaskedL1Loss, NormalizedDistanceLoss, ScaleInvariantLoss, AbsRelError, Threshold  # noqa: F401
 from .losses import (NormalizedWeightedMaskedL2Loss, SparseMaskedL1LossDisplay, MaskedL1Loss, NormalizedL2Loss, NormalizedL1Loss,  # noqa: F401
                      MaskedScaleInvariantLoss)

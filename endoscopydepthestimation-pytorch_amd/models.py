@@ -8,6 +8,8 @@ API kept from the reference:
   * ``DepthScalingLayer(epsilon)``, ``FlowfromDepthLayer()``, ``DepthWarpingLayer(epsilon)``:
     ``forward(x)`` takes ONE list argument and returns a tensor or a pair (models.py:346-347,
     370-371, 460-461).
+  * ``images_warping``, ``_bilinear_interpolate``, ``_warp_coordinate_generate``: the reference's functions of the same
+    names (models.py:317-336, 377-429) with their arguments and shapes, differentiable.
 Tensors are contiguous NCHW fp32 on the current HIP device; there is no CPU path.
 
 Design notes (DESIGN.md has the full story): parameters are views into one flat fp32 buffer and
@@ -738,3 +740,109 @@ class DepthWarpingLayer(nn.Module):
         warped, intersect = _WarpFn.apply(depth_maps_1, depth_maps_2, img_masks, translation_vectors, rotation_matrices,
                                           intrinsic_matrices, self.epsilon, self.tile)
         return warped, intersect
+
+
+# ---------------------------------------------------------------------------------------------
+# image warping: the functional part of reference models.py (317-336, 377-429)
+# ---------------------------------------------------------------------------------------------
+PADDING_MODES = {"zeros": 0, "border": 1, "reflection": 2}
+
+
+class _ImageWarpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, images, u, v, mode):
+        lib = _lib.load()
+        n, c, h, w = images.shape
+        warped = torch.empty_like(images)
+        _lib.check(lib.endo_image_warp_fwd(_lib.ptr(images), _lib.ptr(u), _lib.ptr(v), _lib.ptr(warped), n, c, h, w, mode,
+                                           _lib.stream()), "endo_image_warp_fwd")
+        ctx.save_for_backward(images, u, v)
+        ctx.mode = mode
+        return warped
+
+    @staticmethod
+    def backward(ctx, grad_warped):
+        lib = _lib.load()
+        images, u, v = ctx.saved_tensors
+        n, c, h, w = images.shape
+        grad_warped = _lib.dev_f32(grad_warped, "grad")
+        want = ctx.needs_input_grad
+        g_images = torch.empty_like(images) if want[0] else None
+        g_u = torch.empty_like(u) if want[1] else None
+        g_v = torch.empty_like(v) if want[2] else None
+        _lib.check(lib.endo_image_warp_bwd(_lib.ptr(grad_warped), _lib.ptr(images), _lib.ptr(u), _lib.ptr(v), _lib.ptr(g_images),
+                                           _lib.ptr(g_u), _lib.ptr(g_v), n, c, h, w, ctx.mode, _lib.stream()), "endo_image_warp_bwd")
+        return g_images, g_u, g_v, None
+
+
+def images_warping(images, source_coord_w_flat, source_coord_h_flat, padding_mode="zeros"):
+    """reference models.py:317-322: ``images`` (N, C, H, W) sampled bilinearly at the pixel coordinates (u, v) =
+    (``source_coord_w_flat``, ``source_coord_h_flat``), any shape with N * H * W elements -- ``F.grid_sample`` (bilinear,
+    ``align_corners=False``) on the grid (2u/W - 1, 2v/H - 1).  Returns (N, C, H, W); gradients reach the images and both coordinates.
+    A pixel whose coordinate is not finite gives 0 and gets zero gradients (the reference's result there is undefined)."""
+    if padding_mode not in PADDING_MODES:
+        raise ValueError("images_warping: padding_mode is one of %s, not %r" % (sorted(PADDING_MODES), padding_mode))
+    if images.dim() != 4:
+        raise ValueError("images_warping: images are (N, C, H, W), not %s" % (tuple(images.shape),))
+    n, _, h, w = images.shape
+    for name, coord in (("source_coord_w_flat", source_coord_w_flat), ("source_coord_h_flat", source_coord_h_flat)):
+        if coord.numel() != n * h * w:
+            raise ValueError("images_warping: %s has %d elements, the images have N * H * W = %d" % (name, coord.numel(), n * h * w))
+    images = _lib.dev_f32(images, "images")
+    u = _lib.dev_f32(source_coord_w_flat, "source coordinates").reshape(n, h, w)
+    v = _lib.dev_f32(source_coord_h_flat, "source coordinates").reshape(n, h, w)
+    return _ImageWarpFn.apply(images, u, v, PADDING_MODES[padding_mode])
+
+
+def _bilinear_interpolate(im, x, y, padding_mode="zeros"):
+    """reference models.py:325-336, the NHWC form of ``images_warping``: ``im`` (N, H, W, C) -> (N, H, W, C)."""
+    if im.dim() != 4:
+        raise ValueError("_bilinear_interpolate: im is (N, H, W, C), not %s" % (tuple(im.shape),))
+    return images_warping(im.permute(0, 3, 1, 2), x, y, padding_mode).permute(0, 2, 3, 1)
+
+
+class _WarpCoordFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, mask, t, r, k):
+        lib = _lib.load()
+        n, h, w, _ = depth.shape
+        u = torch.empty_like(depth)
+        v = torch.empty_like(depth)
+        _lib.check(lib.endo_warp_coordinates_fwd(_lib.ptr(depth), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(r), _lib.ptr(k), _lib.ptr(u),
+                                                 _lib.ptr(v), n, h, w, _lib.stream()), "endo_warp_coordinates_fwd")
+        ctx.save_for_backward(depth, mask, t, r, k)
+        ctx.set_materialize_grads(False)
+        return u, v
+
+    @staticmethod
+    def backward(ctx, grad_u, grad_v):
+        if grad_u is None and grad_v is None:
+            return None, None, None, None, None
+        lib = _lib.load()
+        depth, mask, t, r, k = ctx.saved_tensors
+        n, h, w, _ = depth.shape
+        gu = None if grad_u is None else _lib.dev_f32(grad_u, "grad")
+        gv = None if grad_v is None else _lib.dev_f32(grad_v, "grad")
+        grad_depth = torch.empty_like(depth)
+        _lib.check(lib.endo_warp_coordinates_bwd(_lib.ptr(gu), _lib.ptr(gv), _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(r),
+                                                 _lib.ptr(k), _lib.ptr(grad_depth), n, h, w, _lib.stream()), "endo_warp_coordinates_bwd")
+        return grad_depth, None, None, None, None
+
+
+def _warp_coordinate_generate(depth_maps_1, img_masks, translation_vectors, rotation_matrices, intrinsic_matrices):
+    """reference models.py:377-429: ``[u_2, v_2]``, each (N, H, W, 1) -- the frame-2 pixel coordinates of the frame-1 pixels under depth
+    and mask (N, H, W, 1) and the pose of frame 1 with respect to frame 2.  The gradient reaches the depth; the mask and the pose get
+    none.  A masked-out pixel lands at (0, 0), as in the reference."""
+    if depth_maps_1.dim() != 4 or depth_maps_1.shape[3] != 1 or img_masks.shape != depth_maps_1.shape:
+        raise ValueError("_warp_coordinate_generate: depth and mask are (N, H, W, 1), not %s and %s" % (
+            tuple(depth_maps_1.shape), tuple(img_masks.shape)))
+    for name, t in (("masks", img_masks), ("translations", translation_vectors), ("rotations", rotation_matrices),
+                    ("intrinsics", intrinsic_matrices)):
+        if t.requires_grad:
+            raise RuntimeError("_warp_coordinate_generate: %s get no gradient (the reference does not differentiate them); detach them" % name)
+    n = depth_maps_1.shape[0]
+    depth = _lib.dev_f32(depth_maps_1, "depth maps")
+    mask = _lib.dev_f32(img_masks, "image masks")
+    t, r, k = _pose(translation_vectors, rotation_matrices, intrinsic_matrices, n)
+    u, v = _WarpCoordFn.apply(depth, mask, t, r, k)
+    return [u, v]

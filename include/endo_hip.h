@@ -70,7 +70,8 @@ extern "C" {
  * ENDO_OPT_WINO_FWD = 3 / 4 and ENDO_OPT_WGRAD_F34 = 2 are removed -- no entry point and no signature changes.
  * 7: the plan of a pass can be read: adds endo_net_last_plan, endo_net_plan_query, endo_net_plan_name and the option
  * ENDO_OPT_CHIP_DIVISOR; no existing signature changes; since then (unchanged by additions) endo_norm_l2_*, endo_norm_l1_*,
- * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each). */
+ * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each); then endo_warp_coordinates_* and
+ * endo_image_warp_* (_fwd / _bwd each). */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -130,6 +131,39 @@ int endo_depth_warp_bwd_tiled(const float* grad_warped, const float* depth_1, co
  * the gather path instead (large / divergent motion, e.g. the gap-scaled poses of BASELINE configs[4]); per process and device.
  * Copies two counters from the device (synchronises); either pointer may be null. */
 int endo_warp_fallback_blocks(long long* forward, long long* backward, int reset);
+
+/* ---------------------------------------------------------------------------------------------
+ * _warp_coordinate_generate -- reference models.py:377-429: where the frame-1 pixels land in frame 2.
+ * depth, mask, u, v: n x H x W (the reference's n x H x W x 1); t, R, K as above.  The arithmetic is endo_flow_from_depth_fwd's
+ * before its ((u - x) / W, (v - y) / H): camera maps in fp64, zt = 1e30 (1 - m) + m z2, u = (w_x + d q_x) / zt.  A masked-out
+ * pixel therefore lands at u ~ 0, v ~ 0, as in the reference.
+ * Backward: grad_depth written in full; grad_u or grad_v may be NULL (= zero).
+ * ------------------------------------------------------------------------------------------- */
+int endo_warp_coordinates_fwd(const float* depth, const float* mask, const float* t, const float* R,
+                              const float* K, float* u, float* v, int n, int h, int w, void* stream);
+int endo_warp_coordinates_bwd(const float* grad_u, const float* grad_v, const float* depth, const float* mask,
+                              const float* t, const float* R, const float* K, float* grad_depth,
+                              int n, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * images_warping / _bilinear_interpolate -- reference models.py:317-336: F.grid_sample (bilinear, align_corners=False) of `images` on
+ * the grid (2u/W - 1, 2v/H - 1), i.e. at the source location (u - 0.5, v - 0.5).
+ * images, warped: n x C x H x W (any C >= 1); u, v: n x H x W pixel coordinates.
+ * padding_mode: 0 zeros, 1 border (source location clipped to [0, W - 1]), 2 reflection (reflected over [-0.5, W - 0.5], then
+ * clipped) -- ATen's transforms for align_corners=False; anything else is ENDO_E_BADARG.
+ * A pixel whose source location is not finite (NaN or infinite u, v, or a u so large that the location overflows) gives 0 and gets
+ * zero gradients in every mode; ATen's result there is undefined (it converts the location to an integer).
+ * Backward: each of grad_images, grad_u, grad_v may be NULL, and its work is then skipped.  grad_images is zeroed by the call and
+ * then scatter-added (fp32 atomics: the order of a pixel's additions is not fixed; zero terms are skipped, which spares the atomics of
+ * the masked-out pixels of endo_warp_coordinates_fwd -- they all sample at pixel (0, 0) -- under a mask-weighted loss);
+ * grad_u, grad_v are written in full and carry
+ * the padding mode's factor 0 / +1 / -1 (grid_sample's W / 2 times the grid's 2 / W is 1).  No workspace.
+ * ------------------------------------------------------------------------------------------- */
+int endo_image_warp_fwd(const float* images, const float* u, const float* v, float* warped,
+                        int n, int c, int h, int w, int padding_mode, void* stream);
+int endo_image_warp_bwd(const float* grad_warped, const float* images, const float* u, const float* v,
+                        float* grad_images, float* grad_u, float* grad_v,
+                        int n, int c, int h, int w, int padding_mode, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------
