@@ -15,4 +15,4 @@ from .models import FCDenseNet57, DepthScalingLayer, DepthWarpingLayer, Flowfrom
 from .models import images_warping, _bilinear_interpolate, _warp_coordinate_generate  # noqa: F401
 from .losses import SparseMaskedL1Loss, NormalizedDistanceLoss, ScaleInvariantLoss, AbsRelError, Threshold  # noqa: F401
 from .losses import (NormalizedWeightedMaskedL2Loss, SparseMaskedL1LossDisplay, MaskedL1Loss, NormalizedL2Loss, NormalizedL1Loss,  # noqa: F401
-                     MaskedScaleInvariantLoss)
+                     MaskedScaleInvariantLoss, PhotometricLoss)

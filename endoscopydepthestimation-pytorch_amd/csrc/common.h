@@ -196,6 +196,17 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
                            const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics, float dcl_weight,
                            float eps, float* loss, float* grad_depth_1, float* grad_depth_2, float* workspace, int n, int h, int w,
                            int zero_grads, hipStream_t stream);
+// geometry.hip: where phase 1 leaves the two intersect masks (n x h x w floats each) in endo_consistency_phase's workspace
+void endo_consistency_intersect_planes(float* workspace, int n, int h, int w, float** inter_1, float** inter_2);
+
+// image_warp.hip, used by head.hip: the photometric term's forward kernel (phase 1; the caller has zeroed stats, [dirs][n][2] doubles)
+// and backward kernel (phase 2) for dirs = 1 or 2 directions in one launch.  Each pointer argument holds one entry per direction; phase
+// 1 reads colors_1 .. R and writes stats and plane, phase 2 reads stats, plane and upstream (one device float per direction) and writes
+// (accumulate = 0) or adds to (1) grad.  Not part of the C ABI.
+int endo_photometric_phase(int phase, int dirs, const float* const* colors_1, const float* const* colors_2, const float* const* depth,
+                           const float* mask, const float* const* inter, const float* const* t, const float* const* R, const float* K,
+                           double* stats, float* const* plane, const float* const* upstream, float* const* grad, int accumulate, int n,
+                           int c, int h, int w, float eps, int padding_mode, hipStream_t stream);
 
 namespace endo {
 

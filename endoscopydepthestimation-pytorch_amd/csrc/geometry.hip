@@ -1051,6 +1051,13 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
     return 0;
 }
 
+// the third and fourth piece of the carving above
+void endo_consistency_intersect_planes(float* workspace, int n, int h, int w, float** inter_1, float** inter_2) {
+    const int64_t piece = (static_cast<int64_t>(n) * h * w + 3) / 4 * 4;
+    *inter_1 = workspace + 2 * piece;
+    *inter_2 = workspace + 3 * piece;
+}
+
 extern "C" int endo_warp_consistency(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
                                      const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
                                      float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,

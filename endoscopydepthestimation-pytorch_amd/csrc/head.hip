@@ -5,6 +5,7 @@
 // the modules'; what it removes is ~60 autograd nodes and as many host round trips between ~45 small launches: in the traced
 // step the GPU sat idle for 0.35 ms there.  The backward half runs unconditionally (it is cheap); the caller still decides on
 // the non-finite guard from the loss value before it differentiates the network.
+// endo_loss_head_photo is the same body with the photometric term (image_warp.hip) in both directions: three launches more.
 #include "common.h"
 
 namespace endo {
@@ -67,6 +68,34 @@ __global__ void head_combine_kernel(const float* __restrict__ parts, float c_sfl
     }
 }
 
+// head_combine_kernel with the photometric term: the two directions' terms from their reduction tables ([2][n][2] doubles:
+// photometric_fwd_kernel's sums, image_warp.hip) as photometric_finalize_kernel forms them, losses[4] = c_photo * (term_1 + term_2)
+// added to the total before the non-finite test; up[2] = d total / d (each photometric term)
+__global__ void head_combine_photo_kernel(const float* __restrict__ parts, float c_sfl, const float* __restrict__ dcl_weighted,
+                                          const double* __restrict__ photo_stats, int n, float photo_eps, float c_photo,
+                                          float* __restrict__ losses, float* __restrict__ up) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const float sfl = c_sfl * (parts[0] + parts[1]);
+        const float dcl = dcl_weighted[0];
+        float term[2];
+        for (int z = 0; z < 2; ++z) {
+            float acc = 0.f;
+            for (int i = 0; i < n; ++i)
+                acc += static_cast<float>(photo_stats[2 * (z * n + i)]) / (photo_eps + static_cast<float>(photo_stats[2 * (z * n + i) + 1]));
+            term[z] = acc / static_cast<float>(n);
+        }
+        const float photo = c_photo * (term[0] + term[1]);
+        const float total = dcl + sfl + photo;
+        losses[0] = total;
+        losses[1] = dcl;
+        losses[2] = sfl;
+        losses[3] = (isnan(total) || isinf(total)) ? 1.f : 0.f;
+        losses[4] = photo;
+        up[0] = c_sfl;
+        up[2] = c_photo;
+    }
+}
+
 }  // namespace endo
 
 using namespace endo;
@@ -87,10 +116,12 @@ struct HeadLayout {
     int64_t g_flow_1, g_flow_2;          // d / d masked flow, then masked in place = d / d raw flow
     int64_t g_s1, g_s2;                  // d loss / d scaled depth: the flow terms, then += the consistency terms
     int64_t dstats;                      // fp64 reduction tables (depth scaling, sparse-flow loss, distance loss)
-    int64_t parts, up, ratio, end;
+    int64_t parts, up, ratio;
+    int64_t photo_1, photo_2;            // endo_loss_head_photo only: the photometric term's derivative planes, behind everything else
+    int64_t end;
 };
 
-static HeadLayout head_layout(int n, int h, int w) {
+static HeadLayout head_layout(int n, int h, int w, bool photo = false) {
     const int64_t p = static_cast<int64_t>(n) * h * w;
     int64_t at = 0;
     auto take = [&](int64_t count) { const int64_t q = at; at += (count + 3) / 4 * 4; return q; };
@@ -106,6 +137,8 @@ static HeadLayout head_layout(int n, int h, int w) {
     l.parts = take(8);           // sfl_1, sfl_2, dcl_1, dcl_2
     l.up = take(4);              // upstream gradients of the four terms
     l.ratio = take(4);           // depth-scaling's second output (unused by the loss)
+    l.photo_1 = l.photo_2 = at;
+    if (photo) { l.photo_1 = take(p); l.photo_2 = take(p); }
     l.end = at;
     return l;
 }
@@ -116,7 +149,16 @@ extern "C" int64_t endo_loss_head_workspace_floats(int n, int h, int w) {
     return 34 * p + 128 * n + 256;
 }
 
-extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
+extern "C" int64_t endo_loss_head_photo_workspace_floats(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return -1;
+    const int64_t p = static_cast<int64_t>(n) * h * w;
+    return 36 * p + 128 * n + 264;
+}
+
+// The body of endo_loss_head and endo_loss_head_photo.  photo = false: colors_*, photo_weight and padding_mode are unused, losses has
+// four floats, and the launches, values and workspace layout are endo_loss_head's.
+static int loss_head_impl(bool photo, const float* colors_1, const float* colors_2, float photo_weight, int padding_mode,
+                          const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
                               const float* sparse_depths_2, const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
                               const float* sparse_flows_1, const float* sparse_flows_2, const float* sparse_flow_masks_1,
                               const float* sparse_flow_masks_2, const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1,
@@ -130,7 +172,7 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int hw = h * w;
     // ---- workspace carving (floats): head_layout ----
-    const HeadLayout l = head_layout(n, h, w);
+    const HeadLayout l = head_layout(n, h, w, photo);
     float* scaled_1 = workspace + l.scaled_1;  float* scaled_2 = workspace + l.scaled_2;
     float* flow_1 = workspace + l.flow_1;      float* flow_2 = workspace + l.flow_2;
     float* msf_1 = workspace + l.msf_1;        float* msf_2 = workspace + l.msf_2;
@@ -150,7 +192,9 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
 #define HEAD(call) do { rc = (call); if (rc) return rc; } while (0)
     // ---- forward (train.py:279-315) ----
     // one memset for the reduction tables of both frames' depth scaling (forward sums, backward work) and sparse-flow losses: 22 n doubles
-    ENDO_CHECK(hipMemsetAsync(dstats, 0, sizeof(double) * (2 * 8 * n + 2 * n + 2 * 2 * n), stream));
+    // (with the photometric term: + its 2 x 2 n sums, which take the first half of the unused table behind them)
+    double* photo_stats = nd_stats_1;
+    ENDO_CHECK(hipMemsetAsync(dstats, 0, sizeof(double) * (2 * 8 * n + 2 * n + 2 * 2 * n + (photo ? 2 * 2 * n : 0)), stream));
     HEAD(endo_depth_scale_fwd_impl(pred_1, sparse_depths_1, sparse_depth_masks_1, scaled_1, ratio, ds_stats_1, n, hw, eps, 0, stream));
     HEAD(endo_depth_scale_fwd_impl(pred_2, sparse_depths_2, sparse_depth_masks_2, scaled_2, ratio + 1, ds_stats_2, n, hw, eps, 0, stream));
     HEAD(endo_flow_from_depth_fwd(scaled_1, boundaries, t_1_wrt_2, r_1_wrt_2, intrinsics, flow_1, n, h, w, stream_));
@@ -169,7 +213,26 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
     // leaves dcl_weight * 0.5 * (term_1 + term_2) in parts[4] and the backward coefficients in its workspace
     HEAD(endo_consistency_phase(1, scaled_1, scaled_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps,
                                 parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, stream));
-    head_combine_kernel<<<1, 64, 0, stream>>>(parts, static_cast<float>(static_cast<double>(sfl_weight) * 0.5), parts + 4, losses, up);
+    // the photometric term, both directions in one kernel: each frame's masked colours against the other's sampled at its own scaled
+    // depth, under the intersect mask the consistency kernel has just written
+    const float* ph_c1[2] = {colors_1, colors_2};
+    const float* ph_c2[2] = {colors_2, colors_1};
+    const float* ph_depth[2] = {scaled_1, scaled_2};
+    const float* ph_t[2] = {t_1_wrt_2, t_2_wrt_1};
+    const float* ph_r[2] = {r_1_wrt_2, r_2_wrt_1};
+    float* ph_plane[2] = {workspace + l.photo_1, workspace + l.photo_2};
+    if (photo) {
+        float* inter_1 = nullptr;
+        float* inter_2 = nullptr;
+        endo_consistency_intersect_planes(cons_ws, n, h, w, &inter_1, &inter_2);
+        const float* ph_inter[2] = {inter_1, inter_2};
+        HEAD(endo_photometric_phase(1, 2, ph_c1, ph_c2, ph_depth, boundaries, ph_inter, ph_t, ph_r, intrinsics, photo_stats, ph_plane, nullptr,
+                                    nullptr, 0, n, 3, h, w, 1.0f, padding_mode, stream));
+        head_combine_photo_kernel<<<1, 64, 0, stream>>>(parts, static_cast<float>(static_cast<double>(sfl_weight) * 0.5), parts + 4, photo_stats,
+                                                        n, 1.0f, static_cast<float>(static_cast<double>(photo_weight) * 0.5), losses, up);
+    } else {
+        head_combine_kernel<<<1, 64, 0, stream>>>(parts, static_cast<float>(static_cast<double>(sfl_weight) * 0.5), parts + 4, losses, up);
+    }
     ENDO_LAUNCH_CHECK();
     // ---- backward ----
     HEAD(endo_sparse_l1_bwd(up + 0, msf_1, flow_1, msm_1, l1_stats_1, nullptr, g_flow_1, n, 2, hw, 1.0f, stream_));
@@ -186,10 +249,42 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
     HEAD(endo_flow_from_depth_bwd(g_flow_2, scaled_2, boundaries, t_2_wrt_1, r_2_wrt_1, intrinsics, g_s2, n, h, w, stream_));
     HEAD(endo_consistency_phase(2, scaled_1, scaled_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps,
                                 parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, stream));
+    if (photo) {          // += the photometric terms: stream order, one writer per element
+        const float* ph_up[2] = {up + 2, up + 2};
+        float* ph_grad[2] = {g_s1, g_s2};
+        HEAD(endo_photometric_phase(2, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, photo_stats, ph_plane, ph_up,
+                                    ph_grad, 1, n, 3, h, w, 1.0f, 0, stream));
+    }
     HEAD(endo_depth_scale_bwd_impl(g_s1, nullptr, pred_1, sparse_depths_1, ds_stats_1, grad_pred_1, ds_work_1, n, hw, eps, 0, stream));
     HEAD(endo_depth_scale_bwd_impl(g_s2, nullptr, pred_2, sparse_depths_2, ds_stats_2, grad_pred_2, ds_work_2, n, hw, eps, 0, stream));
 #undef HEAD
     return 0;
+}
+
+extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
+                              const float* sparse_depths_2, const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
+                              const float* sparse_flows_1, const float* sparse_flows_2, const float* sparse_flow_masks_1,
+                              const float* sparse_flow_masks_2, const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1,
+                              const float* r_2_wrt_1, const float* intrinsics, float sfl_weight, float dcl_weight, float eps,
+                              float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace, int n, int h, int w, void* stream_) {
+    return loss_head_impl(false, nullptr, nullptr, 0.0f, 0, pred_1, pred_2, boundaries, sparse_depths_1, sparse_depths_2, sparse_depth_masks_1,
+                          sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1, sparse_flow_masks_2, t_1_wrt_2, r_1_wrt_2,
+                          t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses, grad_pred_1, grad_pred_2, workspace, n, h, w,
+                          stream_);
+}
+
+extern "C" int endo_loss_head_photo(const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
+                                    const float* sparse_depths_2, const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
+                                    const float* sparse_flows_1, const float* sparse_flows_2, const float* sparse_flow_masks_1,
+                                    const float* sparse_flow_masks_2, const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1,
+                                    const float* r_2_wrt_1, const float* intrinsics, const float* colors_1, const float* colors_2,
+                                    float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode, float* losses,
+                                    float* grad_pred_1, float* grad_pred_2, float* workspace, int n, int h, int w, void* stream_) {
+    if (!colors_1 || !colors_2 || padding_mode < 0 || padding_mode > 2 || !(photo_weight >= 0.0f)) return ENDO_E_BADARG;
+    return loss_head_impl(true, colors_1, colors_2, photo_weight, padding_mode, pred_1, pred_2, boundaries, sparse_depths_1, sparse_depths_2,
+                          sparse_depth_masks_1, sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1, sparse_flow_masks_2,
+                          t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses, grad_pred_1,
+                          grad_pred_2, workspace, n, h, w, stream_);
 }
 
 extern "C" int endo_loss_head_planes(int n, int h, int w, int64_t* offsets) {

@@ -6,6 +6,8 @@ mean happens in a one-wave finalize kernel.  AbsRelError and Threshold (losses.p
 reconstruction that evaluate.validation_outputs reports) are forward only: one launch of endo_depth_metrics, no atomics.
 The reference's other six classes (NormalizedWeightedMaskedL2Loss, SparseMaskedL1LossDisplay, MaskedL1Loss, NormalizedL2Loss,
 NormalizedL1Loss, MaskedScaleInvariantLoss -- losses.py:35-54, 69-109, 149-186) follow the same pattern, forward and backward.
+PhotometricLoss (not a reference class) is the chain _warp_coordinate_generate -> images_warping -> MaskedL1Loss as one forward and one
+backward kernel.
 """
 
 import torch
@@ -293,6 +295,78 @@ class MaskedL1Loss(nn.Module):
 def _one_channel_mask(owner, maps, maps_hat, masks):
     if maps.dim() != 4 or maps_hat.shape != maps.shape or tuple(masks.shape) != (maps.shape[0], 1, maps.shape[2], maps.shape[3]):
         raise ValueError("%s needs two (N, C, H, W) tensors and an (N, 1, H, W) mask" % owner)
+
+
+class _PhotometricFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, colors_1, colors_2, mask, intersect, t, r, k, eps, mode):
+        lib = _lib.load()
+        n, c, h, w = colors_1.shape
+        loss = torch.empty((), dtype=torch.float32, device=depth.device)
+        stats = torch.empty((n, 2), dtype=torch.float64, device=depth.device)
+        plane = torch.empty(int(lib.endo_photometric_workspace_floats(n, h, w)), dtype=torch.float32, device=depth.device)
+        _lib.check(lib.endo_photometric_fwd(_lib.ptr(colors_1), _lib.ptr(colors_2), _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(intersect),
+                                            _lib.ptr(t), _lib.ptr(r), _lib.ptr(k), _lib.ptr(loss), _lib.ptr(stats), _lib.ptr(plane),
+                                            n, c, h, w, eps, mode, _lib.stream()), "endo_photometric_fwd")
+        ctx.save_for_backward(stats, plane)
+        ctx.eps, ctx.shape = eps, (n, 1, h, w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        lib = _lib.load()
+        stats, plane = ctx.saved_tensors
+        n, _, h, w = ctx.shape
+        grad_loss = _lib.dev_f32(grad_loss, "grad")
+        g_d = torch.empty(ctx.shape, dtype=torch.float32, device=plane.device)
+        _lib.check(lib.endo_photometric_bwd(_lib.ptr(grad_loss), _lib.ptr(stats), _lib.ptr(plane), _lib.ptr(g_d), 0, n, h, w, ctx.eps,
+                                            _lib.stream()), "endo_photometric_bwd")
+        return (g_d,) + (None,) * 9
+
+
+class PhotometricLoss(nn.Module):
+    """The photometric term: frame 2's colours sampled where the frame-1 pixels land under depth and pose, against frame 1's colours,
+    under the intersect mask -- the scalar of the chain
+
+        [u, v] = _warp_coordinate_generate(depth.permute(0, 2, 3, 1), mask.permute(0, 2, 3, 1), t, R, K)
+        warped = images_warping(colors_2, u, v, padding_mode)
+        MaskedL1Loss(epsilon)([colors_1, warped, intersect_masks])
+
+    as one forward and one backward kernel (endo_photometric_fwd / _bwd), without the planes u, v and warped.  ``forward`` takes ONE
+    list ``[colors_1, colors_2, depth_maps_1, img_masks, intersect_masks, translation_vectors, rotation_matrices, intrinsic_matrices]``:
+    colours (N, C, H, W), depth and both masks (N, 1, H, W), as for ``DepthWarpingLayer``.  The gradient reaches the depth only; colours,
+    masks or poses that ask for one raise.  A pixel whose coordinate is not finite samples nothing and gets zero gradient."""
+
+    def __init__(self, epsilon=1.0, padding_mode="zeros"):
+        super().__init__()
+        from .models import PADDING_MODES
+        if padding_mode not in PADDING_MODES:
+            raise ValueError("PhotometricLoss: padding_mode is one of %s, not %r" % (sorted(PADDING_MODES), padding_mode))
+        self.epsilon = float(epsilon)
+        self.padding_mode = padding_mode
+        self._mode = PADDING_MODES[padding_mode]
+
+    def forward(self, x):
+        colors_1, colors_2, depth_maps_1, img_masks, intersect_masks, translation_vectors, rotation_matrices, intrinsic_matrices = x
+        _no_grad_inputs("PhotometricLoss", colors_1=colors_1, colors_2=colors_2, masks=img_masks, intersect_masks=intersect_masks,
+                        translations=translation_vectors, rotations=rotation_matrices, intrinsics=intrinsic_matrices)
+        if colors_1.dim() != 4 or colors_2.shape != colors_1.shape:
+            raise ValueError("PhotometricLoss needs two (N, C, H, W) colour tensors of one shape, not %s and %s" % (
+                tuple(colors_1.shape), tuple(colors_2.shape)))
+        n, _, h, w = (int(v) for v in colors_1.shape)
+        for name, t in (("depth maps", depth_maps_1), ("image masks", img_masks), ("intersect masks", intersect_masks)):
+            if tuple(t.shape) != (n, 1, h, w):
+                raise ValueError("PhotometricLoss: %s are (N, 1, H, W) = %s, not %s" % (name, (n, 1, h, w), tuple(t.shape)))
+        for name, t, count in (("translation vectors", translation_vectors, 3), ("rotation matrices", rotation_matrices, 9),
+                               ("intrinsic matrices", intrinsic_matrices, 9)):
+            if t.numel() != n * count:
+                raise ValueError("PhotometricLoss: %s hold N x %d numbers, not %d" % (name, count, t.numel()))
+        pose = lambda t, cols, what: _lib.dev_f32(t, what).reshape(n, cols)
+        return _PhotometricFn.apply(_lib.dev_f32(depth_maps_1, "depth maps"), _lib.dev_f32(colors_1, "colors 1"),
+                                    _lib.dev_f32(colors_2, "colors 2"), _lib.dev_f32(img_masks, "image masks"),
+                                    _lib.dev_f32(intersect_masks, "intersect masks"), pose(translation_vectors, 3, "translation vectors"),
+                                    pose(rotation_matrices, 9, "rotation matrices"), pose(intrinsic_matrices, 9, "intrinsic matrices"),
+                                    self.epsilon, self._mode)
 
 
 class _SparseL1DisplayFn(torch.autograd.Function):

@@ -3,7 +3,8 @@ train.py:272-328, built from the drop-in modules of ``models`` / ``losses`` and 
 
   colours * boundary -> two network forwards (BN statistics per call, train.py:276-277) -> depth
   scaling -> flow-from-depth both ways -> boundary masking -> sparse-flow loss -> depth warping
-  both ways -> depth-consistency loss -> weighted sum (+ the non-finite flag, on the device) -> backward
+  both ways -> depth-consistency loss (-> with photometric_weight > 0 the photometric term both ways) -> weighted sum (+ the
+  non-finite flag, on the device) -> backward
   -> ONE all-reduce of gradients + flag -> fused clip_grad_norm_(10) + SGD(0.9), skipped by the kernel when
   any rank's loss was NaN / Inf.
 """
@@ -47,8 +48,18 @@ def mask_mul(a, mask):
 
 class TrainingStep(object):
     def __init__(self, model, optimizer, height, width, sfl_weight=20.0, dcl_weight=0.1, epsilon=1.0e-8, pair_forward=True,
-                 fused_head=True, bf16_storage=False, fp16_storage=False):
+                 fused_head=True, bf16_storage=False, fp16_storage=False, photometric_weight=0.0, photometric_padding="zeros"):
         self.model = model
+        # photometric_weight > 0 adds  w * 0.5 * (P(frame 1 against frame 2) + P(frame 2 against frame 1))  of losses.PhotometricLoss on
+        # the masked colours, each frame's scaled depth and the depth warp's intersect masks to the total (not in the reference's train.py);
+        # 0 is the step without it: the same calls as before the term existed
+        self.photometric_weight = float(photometric_weight)
+        if not self.photometric_weight >= 0.0:
+            raise ValueError("photometric_weight must be >= 0 (got %r)" % (photometric_weight,))
+        if photometric_padding not in models.PADDING_MODES:
+            raise ValueError("photometric_padding is one of %s, not %r" % (sorted(models.PADDING_MODES), photometric_padding))
+        self.photometric_padding = photometric_padding
+        self.photometric_loss_function = losses.PhotometricLoss(padding_mode=photometric_padding)
         # the network over bf16 level buffers (FCDenseNet.forward_bf16_storage: activations and inter-layer gradients stored as
         # bf16, bf16 matrix cores, fp32 accumulation / statistics / parameter gradients; BASELINE configs[2]); the two frames are two
         # sample groups of one call (each with its own BatchNorm statistics, as the reference's two calls, train.py:276-277); losses,
@@ -114,13 +125,22 @@ class TrainingStep(object):
         extras = {"pred_1": pred_1, "pred_2": pred_2, "scaled_1": scaled_1, "scaled_2": scaled_2,
                   "warped_21": warped_21, "warped_12": warped_12, "inter_1": inter_1, "inter_2": inter_2,
                   "std_1": std_1, "std_2": std_2}
+        if self.photometric_weight > 0.0:
+            photo = self.photometric_weight * 0.5 * (
+                self.photometric_loss_function([colors_1, colors_2, scaled_1, b, inter_1, batch["translations_1_wrt_2"],
+                                                batch["rotations_1_wrt_2"], batch["intrinsics"]]) +
+                self.photometric_loss_function([colors_2, colors_1, scaled_2, b, inter_2, batch["translations_2_wrt_1"],
+                                                batch["rotations_2_wrt_1"], batch["intrinsics"]]))
+            extras["photo"] = photo
+            return dcl + sfl + photo, dcl, sfl, extras
         return dcl + sfl, dcl, sfl, extras
 
     def _fused_iteration(self, batch):
         """Network forward -> endo_loss_head (loss values and d loss / d prediction).  Everything is issued straight through the
         C ABI, without autograd nodes: the caller differentiates the network with ``_fused_backward`` after its guard, which
         saves the autograd engine's start-up latency (~0.1 ms of idle GPU after the loss synchronisation).
-        Returns (losses tensor [total, dcl, sfl], network input, forward tape, d loss / d prediction)."""
+        Returns (losses tensor [total, dcl, sfl, flag] -- with photometric_weight > 0 endo_loss_head_photo's [total, dcl, sfl, flag, photo]
+        --, network input, forward tape, predictions, d loss / d prediction)."""
         lib = _lib.load()
         self._display_source = None          # the previous call's masked input goes back to the allocator before this call's is taken
         b = _lib.dev_f32(batch["boundaries"], "boundaries")
@@ -135,20 +155,26 @@ class TrainingStep(object):
                 pred, tape = self.model._run_forward16(x, 2, self.half_storage)       # both frames as two sample groups of one call
             else:
                 pred, tape = self.model._run_forward(x, 2)          # (2N, 1, H, W): frame 1's predictions first
-            need = int(lib.endo_loss_head_workspace_floats(n, h, w))
+            photo = self.photometric_weight > 0.0
+            need = int((lib.endo_loss_head_photo_workspace_floats if photo else lib.endo_loss_head_workspace_floats)(n, h, w))
             if self._head_ws is None or self._head_ws.numel() < need or self._head_ws.device != pred.device:
                 self._head_ws = torch.empty(need, dtype=torch.float32, device=pred.device)
-            losses_t = torch.empty(4, dtype=torch.float32, device=pred.device)          # total, dcl, sfl, guard flag
+            losses_t = torch.empty(5 if photo else 4, dtype=torch.float32, device=pred.device)          # total, dcl, sfl, guard flag (, photo)
             grad_pred = torch.empty_like(pred)
             f = lambda key: _lib.ptr(_lib.dev_f32(batch[key], key))
             pose = lambda key, cols: _lib.ptr(_lib.dev_f32(batch[key], key).reshape(n, cols))
-            _lib.check(lib.endo_loss_head(
+            tensors = [
                 _lib.ptr(pred[:n]), _lib.ptr(pred[n:]), _lib.ptr(b), f("sparse_depths_1"), f("sparse_depths_2"),
                 f("sparse_depth_masks_1"), f("sparse_depth_masks_2"), f("sparse_flows_1"), f("sparse_flows_2"),
                 f("sparse_flow_masks_1"), f("sparse_flow_masks_2"), pose("translations_1_wrt_2", 3), pose("rotations_1_wrt_2", 9),
-                pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9),
-                self.sfl_weight, self.dcl_weight, self.epsilon, _lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]),
-                _lib.ptr(self._head_ws), n, h, w, _lib.stream()), "endo_loss_head")
+                pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9)]
+            outputs = [_lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]), _lib.ptr(self._head_ws), n, h, w, _lib.stream()]
+            if photo:          # the masked network inputs are the term's colours (the head is fp32 under every storage mode)
+                _lib.check(lib.endo_loss_head_photo(
+                    *tensors, _lib.ptr(x[:n]), _lib.ptr(x[n:]), self.sfl_weight, self.dcl_weight, self.photometric_weight, self.epsilon,
+                    models.PADDING_MODES[self.photometric_padding], *outputs), "endo_loss_head_photo")
+            else:
+                _lib.check(lib.endo_loss_head(*tensors, self.sfl_weight, self.dcl_weight, self.epsilon, *outputs), "endo_loss_head")
         self._display_source = (x, b)          # what display_panels() renders with the head workspace's planes
         return losses_t, x, tape, pred, grad_pred
 
@@ -172,9 +198,10 @@ class TrainingStep(object):
             losses_t, _, _, _, _ = self._fused_iteration(batch)
             return losses_t
         with torch.no_grad():
-            loss, dcl, sfl, _ = self.losses(batch)
+            loss, dcl, sfl, extras = self.losses(batch)
             bad = (~torch.isfinite(loss)).to(torch.float32).reshape(1)
-            return torch.cat([loss.reshape(1), dcl.reshape(1), sfl.reshape(1), bad]).to(torch.float32)
+            parts = [loss.reshape(1), dcl.reshape(1), sfl.reshape(1), bad] + ([extras["photo"].reshape(1)] if "photo" in extras else [])
+            return torch.cat(parts).to(torch.float32)
 
     def display_panels(self):
         """The display panel of this step's latest call -- training (``__call__``) or validation (``validation_losses``) -- as
@@ -213,10 +240,13 @@ class TrainingStep(object):
             losses_t, x, tape, pred, grad_pred = self._fused_iteration(batch)
             self._fused_backward(x, tape, grad_pred)
         else:
-            loss, dcl, sfl, _ = self.losses(batch)
+            loss, dcl, sfl, extras = self.losses(batch)
             with torch.no_grad():
                 bad = (~torch.isfinite(loss.detach())).to(torch.float32).reshape(1)
-                losses_t = torch.cat([loss.detach().reshape(1), dcl.detach().reshape(1), sfl.detach().reshape(1), bad]).to(torch.float32)
+                parts = [loss.detach().reshape(1), dcl.detach().reshape(1), sfl.detach().reshape(1), bad]
+                if "photo" in extras:
+                    parts.append(extras["photo"].detach().reshape(1))
+                losses_t = torch.cat(parts).to(torch.float32)
             loss.backward()
         scale, flag = self.bucket.all_reduce(losses_t[3:4])
         norm = self.optimizer.step(grad_scale=scale, skip_flag=flag)
@@ -303,7 +333,7 @@ def validate(step, batches, initial=None, display_each=None, on_display=None):
 
 class _ReadbackSlot(object):
     def __init__(self):
-        self.losses = torch.empty(4, dtype=torch.float32).pin_memory()
+        self.losses = torch.empty(5, dtype=torch.float32).pin_memory()          # the fifth: the photometric term, when the step has one
         self.flag = torch.empty(1, dtype=torch.float32).pin_memory()
         self.norm = torch.empty(1, dtype=torch.float64).pin_memory()
         self.event = torch.cuda.Event()
@@ -321,16 +351,17 @@ class StepOutput(object):
     gradient norm, copied to pinned host buffers asynchronously right behind the step's last kernel (three copies of a few bytes, no
     kernel).  Read like the dict older versions returned; the first read waits for THOSE copies, not for whatever was queued after
     them.  "loss" is a float; "dcl" / "sfl" / "grad_norm" are 0-dim host tensors (NaN for a skipped step's terms, as before);
-    "skipped" is a bool."""
+    "skipped" is a bool.  A step with photometric_weight > 0 also has "photo", like "dcl"."""
 
     def __init__(self, losses, flag, norm, slot):
         import weakref
         self._host = None
         self._slot = slot
+        self._count = int(losses.numel())          # 4, or 5 with the photometric term
         if slot is None:          # host tensors (CPU tests of the glue): copies -- with world > 1 `flag` is a view of the gradient bucket's trailing slot, which the next step overwrites before a one-step-late read
             self._vals = (losses.detach().clone(), flag.detach().clone(), norm.detach().clone())
         else:
-            slot.losses.copy_(losses, non_blocking=True)
+            slot.losses[:self._count].copy_(losses, non_blocking=True)
             slot.flag.copy_(flag.reshape(1), non_blocking=True)
             slot.norm.copy_(norm.reshape(1), non_blocking=True)
             slot.event.record()
@@ -340,7 +371,7 @@ class StepOutput(object):
         if self._host is None:
             if self._slot is not None:
                 self._slot.event.synchronize()
-                losses, flag, norm = self._slot.losses.tolist(), self._slot.flag.tolist(), self._slot.norm.tolist()
+                losses, flag, norm = self._slot.losses[:self._count].tolist(), self._slot.flag.tolist(), self._slot.norm.tolist()
                 self._slot.owner = None
                 self._slot = None
             else:
@@ -350,13 +381,15 @@ class StepOutput(object):
             nan = float("nan")
             self._host = {"loss": losses[0], "dcl": torch.tensor(nan if skipped else losses[1]), "sfl": torch.tensor(nan if skipped else losses[2]),
                           "grad_norm": torch.tensor(norm[0], dtype=torch.float64), "skipped": skipped}
+            if self._count > 4:
+                self._host["photo"] = torch.tensor(nan if skipped else losses[4])
         return self._host
 
     def __getitem__(self, key):
         return self._read()[key]
 
     def __contains__(self, key):
-        return key in ("loss", "dcl", "sfl", "grad_norm", "skipped")
+        return key in ("loss", "dcl", "sfl", "grad_norm", "skipped") or (key == "photo" and self._count > 4)
 
     def keys(self):
         return self._read().keys()

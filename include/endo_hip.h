@@ -71,7 +71,8 @@ extern "C" {
  * 7: the plan of a pass can be read: adds endo_net_last_plan, endo_net_plan_query, endo_net_plan_name and the option
  * ENDO_OPT_CHIP_DIVISOR; no existing signature changes; since then (unchanged by additions) endo_norm_l2_*, endo_norm_l1_*,
  * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each); then endo_warp_coordinates_* and
- * endo_image_warp_* (_fwd / _bwd each). */
+ * endo_image_warp_* (_fwd / _bwd each); then endo_photometric_workspace_floats, endo_photometric_fwd / _bwd,
+ * endo_loss_head_photo_workspace_floats and endo_loss_head_photo. */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -164,6 +165,28 @@ int endo_image_warp_fwd(const float* images, const float* u, const float* v, flo
 int endo_image_warp_bwd(const float* grad_warped, const float* images, const float* u, const float* v,
                         float* grad_images, float* grad_u, float* grad_v,
                         int n, int c, int h, int w, int padding_mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The photometric term as one forward and one backward kernel: the chain
+ *   [u, v] = _warp_coordinate_generate(depth, mask, t, R, K);  warped = images_warping(colors_2, u, v, padding_mode);
+ *   loss = MaskedL1Loss(eps)([colors_1, warped, intersect])        (reference models.py:317-336, 377-429, losses.py:82-91)
+ * with the per-term arithmetic of endo_warp_coordinates_fwd, endo_image_warp_fwd and endo_sparse_l1_fwd, without the planes u, v and
+ * warped.  colors_1, colors_2: n x C x H x W (any C >= 1); depth, mask, intersect: n x 1 x H x W; t n x 3, R / K n x 9.
+ * loss: one fp32 = mean over samples of num_n / (eps + den_n), num_n = sum intersect * sum_c |colors_1 - warped|, den_n = sum intersect
+ * (once, not C times).  stats: n x 2 fp64 [num_n, den_n], zeroed by the call (fp64 atomics, one per block and sum: the order of the
+ * additions is not fixed).  workspace: 16-byte aligned, endo_photometric_workspace_floats(n, h, w) floats; its contents on entry are
+ * ignored, nothing outside it is written, and on return it holds d num_n / d depth per pixel -- STATE for endo_photometric_bwd.
+ * Only the depth is differentiated.  A pixel whose coordinate is not finite samples nothing (warped = 0) and gets zero gradient.
+ * Backward: grad_depth (n x 1 x H x W) = *grad_loss / n / (eps + den_n) * workspace; accumulate = 0 writes every element, 1 adds to
+ * what is there (one writer per element, no atomics); anything else is ENDO_E_BADARG.  n, h, w, eps: the forward call's.
+ * ------------------------------------------------------------------------------------------- */
+int64_t endo_photometric_workspace_floats(int n, int h, int w);
+int endo_photometric_fwd(const float* colors_1, const float* colors_2, const float* depth, const float* mask,
+                         const float* intersect, const float* t, const float* R, const float* K,
+                         float* loss, double* stats, float* workspace,
+                         int n, int c, int h, int w, float eps, int padding_mode, void* stream);
+int endo_photometric_bwd(const float* grad_loss, const double* stats, const float* workspace, float* grad_depth,
+                         int accumulate, int n, int h, int w, float eps, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------
@@ -269,6 +292,27 @@ int endo_loss_head(const float* pred_1, const float* pred_2, const float* bounda
  * endo_display renders after a training or validation call, without a recompute.  The head's own carving, one function for both.
  * ENDO_E_BADARG for bad sizes or a null `offsets`. */
 int endo_loss_head_planes(int n, int h, int w, int64_t* offsets);
+
+/* endo_loss_head with the photometric term (above) in both directions added to the total:
+ *   photo = photo_weight * 0.5 * (P(colors_1, colors_2 sampled at scaled depth 1, pose 1-wrt-2, intersect mask 1) + the roles swapped)
+ * colors_*: n x 3 x H x W, the masked network inputs; the intersect masks are the ones the depth-consistency term has just formed, the
+ * L1's eps is 1 (the reference module's default); padding_mode as endo_image_warp_fwd.  losses: FIVE fp32 = total (now dcl + sfl +
+ * photo), dcl, sfl, the guard flag (which covers the new total), photo -- the first four keep endo_loss_head's positions.  The term's
+ * depth gradients are added to those of the other terms before the depth scaling's backward, in stream order.  workspace:
+ * endo_loss_head_photo_workspace_floats(n, h, w) floats under endo_loss_head's contract; endo_loss_head_planes' offsets hold for it
+ * too.  ENDO_E_BADARG also for null colours, a padding mode outside 0..2 and a photo_weight that is negative or NaN.  With
+ * photo_weight = 0 the values are endo_loss_head's (the term is still evaluated); callers without the term call endo_loss_head. */
+int64_t endo_loss_head_photo_workspace_floats(int n, int h, int w);
+int endo_loss_head_photo(const float* pred_1, const float* pred_2, const float* boundaries,
+                         const float* sparse_depths_1, const float* sparse_depths_2,
+                         const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
+                         const float* sparse_flows_1, const float* sparse_flows_2,
+                         const float* sparse_flow_masks_1, const float* sparse_flow_masks_2,
+                         const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1,
+                         const float* intrinsics, const float* colors_1, const float* colors_2,
+                         float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode,
+                         float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace,
+                         int n, int h, int w, void* stream);
 
 /* Depth warp both ways + depth-consistency loss, forward AND backward, in one call -- reference models.py:454-554 (DepthWarpingLayer,
  * once per direction), losses.py:112-146 (NormalizedDistanceLoss, once per direction), train.py:305-314, and their backward:
