@@ -61,6 +61,7 @@ SIGNATURES = {
     "endo_photometric_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "endo_loss_head_photo_workspace_floats": (_L, [_I, _I, _I]),
     "endo_loss_head_photo": (_I, [_P] * 18 + [_F, _F, _F, _F, _I] + [_P] * 4 + [_I, _I, _I, _P]),
+    "endo_distill_head": (_I, [_P] * 5 + [_F, _F, _I] + [_P] * 4 + [_I, _I, _P]),
     "endo_bf16_pack_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "endo_f16_pack_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "endo_bf16_unpack_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -7,6 +7,9 @@ train.py:272-328, built from the drop-in modules of ``models`` / ``losses`` and 
   non-finite flag, on the device) -> backward
   -> ONE all-reduce of gradients + flag -> fused clip_grad_norm_(10) + SGD(0.9), skipped by the kernel when
   any rank's loss was NaN / Inf.
+
+``DistillationStep`` is the same iteration for teacher-student training (reference utils.py:1462-1482): a teacher forward in front, and
+``endo_distill_head`` in place of, or after, the loss head.
 """
 
 import collections
@@ -267,6 +270,112 @@ class TrainingStep(object):
         return slot
 
 
+def _distill_head(pred, goal, boundaries, weight, epsilon, accumulate, losses_t, grad_pred):
+    """endo_distill_head on the packed (2N, 1, H, W) predictions of student and teacher (frame 1's samples first)."""
+    n2, _, h, w = pred.shape
+    n = n2 // 2
+    stats = torch.empty(6 * n, dtype=torch.float64, device=pred.device)
+    _lib.check(_lib.load().endo_distill_head(
+        _lib.ptr(pred[:n]), _lib.ptr(pred[n:]), _lib.ptr(goal[:n]), _lib.ptr(goal[n:]), _lib.ptr(boundaries), weight, epsilon,
+        1 if accumulate else 0, _lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]), _lib.ptr(stats), n, h * w,
+        _lib.stream()), "endo_distill_head")
+
+
+class DistillationStep(TrainingStep):
+    """One teacher-student iteration: reference utils.learn_from_teacher (utils.py:1462-1482) followed by train.py's guard, clip and SGD
+    on the student (train.py:317-328), fused like ``TrainingStep``: colours * boundary once -> teacher forward (no_grad, its tape
+    dropped) -> student forward -> ``endo_distill_head`` -> student backward -> ONE all-reduce of gradients + flag -> fused clip + SGD.
+
+      distill = distill_weight * 0.5 * (ScaleInvariantLoss(|student(c1)|, |teacher(c1)|, b) + the same for frame 2)
+
+    *Pure mode* (both SfM weights 0, the default): the loss is that term, the batch needs only ``colors_1``, ``colors_2`` and
+    ``boundaries``.  *Combined mode* (sfl_weight or dcl_weight > 0; not in the reference: train.py's body plus learn_from_teacher's term):
+    ``endo_loss_head`` on the student's predictions, then ``endo_distill_head(accumulate=1)`` into the same losses and d loss / d
+    prediction; the batch is a training batch.  The teacher runs in its own current mode; in ``.eval()``, the intended use, a call
+    leaves its parameters, BatchNorm buffers and ``num_batches_tracked`` bit for bit and creates no gradient buffer.  fp32 only.
+    The ``StepOutput`` has "loss", "dcl", "sfl" (0 in pure mode), "distill", "grad_norm" and "skipped"."""
+
+    def __init__(self, student, teacher, optimizer, height, width, distill_weight=1.0, sfl_weight=0.0, dcl_weight=0.0, epsilon=1.0e-8):
+        if teacher is student:
+            raise ValueError("DistillationStep: teacher and student are the same module")
+        for name, value in (("distill_weight", distill_weight), ("sfl_weight", sfl_weight), ("dcl_weight", dcl_weight)):
+            if not float(value) >= 0.0:
+                raise ValueError("%s must be >= 0 (got %r)" % (name, value))
+        for name, model in (("student", student), ("teacher", teacher)):
+            if not hasattr(model, "_run_forward"):
+                raise ValueError("DistillationStep: the %s must be a models.FCDenseNet (the step drives its C entry points)" % name)
+        if student.flat_parameters().device != teacher.flat_parameters().device:
+            raise ValueError("DistillationStep: student on %s, teacher on %s" % (student.flat_parameters().device,
+                                                                                   teacher.flat_parameters().device))
+        TrainingStep.__init__(self, student, optimizer, height, width, sfl_weight=sfl_weight, dcl_weight=dcl_weight, epsilon=epsilon)
+        self.teacher = teacher
+        self.distill_weight = float(distill_weight)
+        self.combined = self.sfl_weight > 0.0 or self.dcl_weight > 0.0
+        distributed.sync_parameters(teacher)
+
+    def losses(self, batch):
+        raise RuntimeError("DistillationStep has no module path; use utils.learn_from_teacher with losses.ScaleInvariantLoss")
+
+    def _fused_iteration(self, batch):
+        """Teacher forward -> student forward -> (combined mode: endo_loss_head ->) endo_distill_head.  Returns what
+        ``TrainingStep._fused_iteration`` does; the losses tensor is [total, dcl, sfl, flag, distill]."""
+        lib = _lib.load()
+        self._display_source = None
+        b = _lib.dev_f32(batch["boundaries"], "boundaries")
+        c1 = _lib.dev_f32(batch["colors_1"], "colors_1")
+        c2 = _lib.dev_f32(batch["colors_2"], "colors_2")
+        n, ch, h, w = c1.shape
+        with torch.no_grad():
+            x = torch.empty((2 * n, ch, h, w), dtype=torch.float32, device=c1.device)
+            _lib.check(lib.endo_mask_mul(_lib.ptr(c1), _lib.ptr(b), _lib.ptr(x[:n]), n, ch, h * w, _lib.stream()), "endo_mask_mul")
+            _lib.check(lib.endo_mask_mul(_lib.ptr(c2), _lib.ptr(b), _lib.ptr(x[n:]), n, ch, h * w, _lib.stream()), "endo_mask_mul")
+            goal, _ = self.teacher._run_forward(x, 2)          # two sample groups, as the student's; the tape goes back to the allocator
+            pred, tape = self.model._run_forward(x, 2)
+            losses_t = torch.empty(5, dtype=torch.float32, device=pred.device)
+            grad_pred = torch.empty_like(pred)
+            if self.combined:
+                need = int(lib.endo_loss_head_workspace_floats(n, h, w))
+                if self._head_ws is None or self._head_ws.numel() < need or self._head_ws.device != pred.device:
+                    self._head_ws = torch.empty(need, dtype=torch.float32, device=pred.device)
+                f = lambda key: _lib.ptr(_lib.dev_f32(batch[key], key))
+                pose = lambda key, cols: _lib.ptr(_lib.dev_f32(batch[key], key).reshape(n, cols))
+                _lib.check(lib.endo_loss_head(
+                    _lib.ptr(pred[:n]), _lib.ptr(pred[n:]), _lib.ptr(b), f("sparse_depths_1"), f("sparse_depths_2"),
+                    f("sparse_depth_masks_1"), f("sparse_depth_masks_2"), f("sparse_flows_1"), f("sparse_flows_2"),
+                    f("sparse_flow_masks_1"), f("sparse_flow_masks_2"), pose("translations_1_wrt_2", 3), pose("rotations_1_wrt_2", 9),
+                    pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9), self.sfl_weight, self.dcl_weight,
+                    self.epsilon, _lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]), _lib.ptr(self._head_ws), n, h, w,
+                    _lib.stream()), "endo_loss_head")
+            _distill_head(pred, goal, b, self.distill_weight, self.epsilon, self.combined, losses_t, grad_pred)
+        if self.combined:
+            self._display_source = (x, b)
+        return losses_t, x, tape, pred, grad_pred
+
+    def validation_losses(self, batch):
+        """The forward part for one batch -- both networks and the head(s), no student backward, no all-reduce, no optimizer: the device
+        fp32 [total, dcl, sfl, flag, distill].  ``validate(step, ...)`` takes its running means from the first three."""
+        return self._fused_iteration(batch)[0]
+
+    def display_panels(self):
+        """``TrainingStep.display_panels`` in combined mode; pure mode has no loss-head planes to render."""
+        if not self.combined:
+            raise RuntimeError("display_panels: a DistillationStep in pure mode (sfl_weight = dcl_weight = 0) runs no loss head, so "
+                               "there are no planes to render")
+        return TrainingStep.display_panels(self)
+
+    def __call__(self, batch, lr=None):
+        """One iteration, as ``TrainingStep.__call__``; the ``StepOutput``'s fifth value is "distill"."""
+        if lr is not None:
+            for group in self.optimizer.param_groups:
+                group["lr"] = lr
+        self.optimizer.zero_grad()
+        losses_t, x, tape, pred, grad_pred = self._fused_iteration(batch)
+        self._fused_backward(x, tape, grad_pred)
+        scale, flag = self.bucket.all_reduce(losses_t[3:4])
+        norm = self.optimizer.step(grad_scale=scale, skip_flag=flag)
+        return StepOutput(losses_t, flag, norm, self._readback_slot(losses_t.device), fifth="distill")
+
+
 ValidationResult = collections.namedtuple("ValidationResult", ["mean_loss", "mean_depth_consistency_loss", "mean_sparse_flow_loss",
                                                                "running_means", "losses"])
 ValidationResult.__doc__ = """What ``validate`` returns: the three running means after the last batch as Python floats (the values train.py's
@@ -333,7 +442,7 @@ def validate(step, batches, initial=None, display_each=None, on_display=None):
 
 class _ReadbackSlot(object):
     def __init__(self):
-        self.losses = torch.empty(5, dtype=torch.float32).pin_memory()          # the fifth: the photometric term, when the step has one
+        self.losses = torch.empty(5, dtype=torch.float32).pin_memory()          # the fifth: the photometric or distillation term, when the step has one
         self.flag = torch.empty(1, dtype=torch.float32).pin_memory()
         self.norm = torch.empty(1, dtype=torch.float64).pin_memory()
         self.event = torch.cuda.Event()
@@ -351,10 +460,12 @@ class StepOutput(object):
     gradient norm, copied to pinned host buffers asynchronously right behind the step's last kernel (three copies of a few bytes, no
     kernel).  Read like the dict older versions returned; the first read waits for THOSE copies, not for whatever was queued after
     them.  "loss" is a float; "dcl" / "sfl" / "grad_norm" are 0-dim host tensors (NaN for a skipped step's terms, as before);
-    "skipped" is a bool.  A step with photometric_weight > 0 also has "photo", like "dcl"."""
+    "skipped" is a bool.  A step with photometric_weight > 0 also has "photo", like "dcl"; ``fifth`` names the fifth loss of another
+    step ("distill" for a DistillationStep)."""
 
-    def __init__(self, losses, flag, norm, slot):
+    def __init__(self, losses, flag, norm, slot, fifth="photo"):
         import weakref
+        self._fifth = fifth
         self._host = None
         self._slot = slot
         self._count = int(losses.numel())          # 4, or 5 with the photometric term
@@ -382,14 +493,14 @@ class StepOutput(object):
             self._host = {"loss": losses[0], "dcl": torch.tensor(nan if skipped else losses[1]), "sfl": torch.tensor(nan if skipped else losses[2]),
                           "grad_norm": torch.tensor(norm[0], dtype=torch.float64), "skipped": skipped}
             if self._count > 4:
-                self._host["photo"] = torch.tensor(nan if skipped else losses[4])
+                self._host[self._fifth] = torch.tensor(nan if skipped else losses[4])
         return self._host
 
     def __getitem__(self, key):
         return self._read()[key]
 
     def __contains__(self, key):
-        return key in ("loss", "dcl", "sfl", "grad_norm", "skipped") or (key == "photo" and self._count > 4)
+        return key in ("loss", "dcl", "sfl", "grad_norm", "skipped") or (key == self._fifth and self._count > 4)
 
     def keys(self):
         return self._read().keys()

@@ -1,4 +1,5 @@
-"""Host-side helpers with the reference's names (reference utils.py:615-682 for the training path, 825-865 and 1405-1412 for the test phase)."""
+"""Host-side helpers with the reference's names (reference utils.py:615-682 for the training path, 825-865 and 1405-1412 for the test phase,
+1462-1482 and 1734-1744 for teacher-student training)."""
 
 import torch
 
@@ -121,6 +122,73 @@ def point_cloud_from_depth(depth_map, color_img, mask_img, intrinsic_matrix, poi
     _lib.check(rc, "endo_point_cloud")
     n = int(count.item())
     return points[:n].cpu().numpy().reshape(-1, 6)
+
+
+class _DistillFn(torch.autograd.Function):
+    """0.5 * (ScaleInvariantLoss(|p1|, |g1|, b) + ScaleInvariantLoss(|p2|, |g2|, b)) on the packed (2N, 1, H, W) predictions as one
+    node: endo_distill_head computes value and d / d prediction together, the backward scales the stored gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, goal, boundaries, eps):
+        from . import _lib, train_step
+        pred = _lib.dev_f32(pred, "predictions")
+        goal = _lib.dev_f32(goal, "goals")
+        boundaries = _lib.dev_f32(boundaries, "boundaries")
+        if pred.dim() != 4 or pred.shape[1] != 1 or pred.shape[0] % 2 or goal.shape != pred.shape:
+            raise ValueError("expected (2N, 1, H, W) predictions and goals (got %s and %s)" % (tuple(pred.shape), tuple(goal.shape)))
+        if tuple(boundaries.shape) != (pred.shape[0] // 2, 1) + tuple(pred.shape[2:]):
+            raise ValueError("expected (N, 1, H, W) boundaries (got %s)" % (tuple(boundaries.shape),))
+        losses_t = torch.empty(5, dtype=torch.float32, device=pred.device)
+        grad_pred = torch.empty_like(pred)
+        train_step._distill_head(pred, goal, boundaries, 1.0, float(eps), False, losses_t, grad_pred)
+        ctx.save_for_backward(grad_pred)
+        return losses_t[4].clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise RuntimeError("learn_from_teacher: the teacher's depths and the boundaries get no gradient")
+        (grad_pred,) = ctx.saved_tensors
+        return grad_pred * grad_loss, None, None, None
+
+
+def _forward_pair(model, x1, x2):
+    if hasattr(model, "forward_pair_packed"):
+        return model.forward_pair_packed(x1, x2)
+    return torch.cat([model(x1), model(x2)], dim=0)
+
+
+def learn_from_teacher(boundaries, colors_1, colors_2, depth_estimation_model_teacher, depth_estimation_model_student,
+                       scale_invariant_loss):
+    """reference utils.py:1462-1482 for callers who keep their own loop: the teacher-student loss of one frame pair,
+    ``0.5 * (SIL(|student(c1)|, |teacher(c1)|, b) + SIL(|student(c2)|, |teacher(c2)|, b))``, differentiable with respect to the
+    student's parameters (one autograd node over endo_distill_head, then the student's), and the four absolute depth maps.  The teacher
+    runs under ``no_grad`` in its current mode; eps is ``scale_invariant_loss.epsilon`` (losses.ScaleInvariantLoss).  The returned maps
+    are the network outputs themselves when the models are FCDenseNets, whose last operation is already ``torch.abs`` (models.py:186).
+    ``train_step.DistillationStep`` is the fused iteration around the same head."""
+    with torch.no_grad():
+        goal = _forward_pair(depth_estimation_model_teacher, colors_1, colors_2)
+    pred = _forward_pair(depth_estimation_model_student, colors_1, colors_2)
+    loss = _DistillFn.apply(pred, goal, boundaries, scale_invariant_loss.epsilon)
+    n = pred.shape[0] // 2
+    outputs = (pred[:n], pred[n:], goal[:n], goal[n:])
+    if not (hasattr(depth_estimation_model_teacher, "forward_pair_packed") and hasattr(depth_estimation_model_student, "forward_pair_packed")):
+        outputs = tuple(torch.abs(t) for t in outputs)
+    return (loss,) + outputs
+
+
+def calculate_outlier_robust_validation_loss(validation_losses, previous_validation_losses):
+    """reference utils.py:1734-1744, the model-selection criterion of the teacher-student loop: for per-sample loss arrays of equal
+    length, (number of increases) * (sum of increases) + (number of decreases) * (sum of decreases, negative); -1.0 when the new
+    array is longer, 1.0 when it is shorter.  Host numpy."""
+    import numpy as np
+    if len(validation_losses) == len(previous_validation_losses):
+        differences = np.asarray(validation_losses) - np.asarray(previous_validation_losses)
+        up, down = differences > 0.0, differences < 0.0
+        positive = np.sum(np.sum(np.int32(up)) * up * differences)
+        negative = np.sum(np.sum(np.int32(down)) * down * differences)
+        return positive + negative
+    return -1.0 if len(validation_losses) > len(previous_validation_losses) else 1.0
 
 
 def get_filenames_from_frame_indexes(sequence_root, frame_index_array):

@@ -72,7 +72,7 @@ extern "C" {
  * ENDO_OPT_CHIP_DIVISOR; no existing signature changes; since then (unchanged by additions) endo_norm_l2_*, endo_norm_l1_*,
  * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each); then endo_warp_coordinates_* and
  * endo_image_warp_* (_fwd / _bwd each); then endo_photometric_workspace_floats, endo_photometric_fwd / _bwd,
- * endo_loss_head_photo_workspace_floats and endo_loss_head_photo. */
+ * endo_loss_head_photo_workspace_floats and endo_loss_head_photo; then endo_distill_head. */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -313,6 +313,26 @@ int endo_loss_head_photo(const float* pred_1, const float* pred_2, const float* 
                          float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode,
                          float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace,
                          int n, int h, int w, void* stream);
+
+/* The teacher-student term of a distillation iteration, both frames, forward AND backward, in one call -- reference
+ * utils.py:1462-1482 (learn_from_teacher: torch.abs of both networks' outputs, ScaleInvariantLoss per frame under the boundary mask,
+ * 0.5 * the sum) and losses.py:22-32.  Per frame f and sample s, with r = log(b |p| + eps) - log(b |g| + eps):
+ *   S = sum b, R1 = sum r, R2 = sum r^2, L_s = R2 / S + R1^2 / S^2, term_f = mean_s L_s, distill = weight * 0.5 * (term_1 + term_2)
+ *   d distill / d p_i = weight * 0.5 / n * (2 r_i / S + 2 R1 / S^2) * b_i * sgn(p_i) / (b_i |p_i| + eps),  sgn(0) = 0 as torch.abs
+ * fp32 per element, fp64 sums (endo_scale_inv_*'s arithmetic).  pred_*: the student's outputs, goal_*: the teacher's (no gradient),
+ * n x 1 x H x W each, of any sign; hw = H * W.  Two launches and the zeroing of `stats`.
+ * losses: FIVE fp32 on the device = total, dcl, sfl, flag, distill -- endo_loss_head's four positions and the term fifth, as in
+ * endo_loss_head_photo.  accumulate = 0: total = distill, dcl = sfl = 0, flag = 1.0 when the total is NaN / Inf else 0.0, grad_pred_*
+ * written; what losses and grad_pred_* held on entry is ignored.  accumulate = 1: losses[0..3] and grad_pred_* hold what an
+ * endo_loss_head earlier on the same stream left: total += distill, the flag stays 1 when it was 1 and becomes 1 when the new total
+ * is not finite, dcl and sfl are kept, the term's gradient is ADDED to grad_pred_*.  losses[4] = distill in both.
+ * stats: 2n x 3 fp64 [sum r^2, sum r, sum b], frame 1's n samples first; zeroed by the call, its contents on entry ignored.
+ * ENDO_E_BADARG before any device work for null pointers, n or hw <= 0, accumulate not 0 / 1 and a weight that is negative or NaN.
+ * Additive: the version stays 7. */
+int endo_distill_head(const float* pred_1, const float* pred_2, const float* goal_1, const float* goal_2,
+                      const float* boundaries, float weight, float eps, int accumulate,
+                      float* losses, float* grad_pred_1, float* grad_pred_2, double* stats,
+                      int n, int hw, void* stream);
 
 /* Depth warp both ways + depth-consistency loss, forward AND backward, in one call -- reference models.py:454-554 (DepthWarpingLayer,
  * once per direction), losses.py:112-146 (NormalizedDistanceLoss, once per direction), train.py:305-314, and their backward:
