@@ -121,6 +121,8 @@ SIGNATURES = {
     "endo_augment": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
     "endo_evaluate_workspace_bytes": (_L, [_I, _I, _I]),
     "endo_evaluate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "endo_evaluate_posed_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_evaluate_posed": (_I, [_P] * 6 + [_I, _I, _I, _I, _I, _I, _F, _F] + [_P] * 7 + [_L, _P]),
     "endo_loss_head_planes": (_I, [_I, _I, _I, ctypes.POINTER(_L)]),
     "endo_display_workspace_bytes": (_L, [_I, _I, _I]),
     "endo_display_panel_shape": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),

@@ -7,6 +7,11 @@ coloured PLY point cloud, for batches of frames (dataset.TestFrames) on the devi
 
 The reference needs cv2 and plyfile here and runs one frame per batch with all per-pixel work on the host (evaluate.py:292, 329-345).
 
+The same frames with poses from the electromagnetic tracker (reader.read_initial_pose_file) give the reference's posed test output
+(utils.write_test_output_with_initial_pose, utils.py:1316-1355): posed_test_outputs / run_posed_test_phase over endo_evaluate_posed
+(csrc/evaluate_posed.hip, three launches per batch) write each frame's colour image, depth image and a point cloud normalised to a z
+range of 20 units and moved into the tracker's frame, and the whole sequence as one merged cloud.
+
 The validation phase (evaluate.py:119-277) compares a trained network with the sparse reconstruction of a sequence, for batches of
 pairs (dataset.TrainingBatches(transform=None, shuffle=False): the reference's SfMDataset(phase="validation")):
 
@@ -127,7 +132,173 @@ def run_test_phase(model, frames, out_dir, write_png=True, write_ply=True, ply_t
     return count
 
 
-VALIDATION_TITLE = "Results (c1, sd1, d1, wd1, sf1, df1, c2, sd2, d2, wd2, sf2, df2)"          # evaluate.py:258
+def _poses_f64(rotations, translations, n, dev):
+    """(N, 3, 3) and (N, 3) float64 device tensors of per-frame poses given as arrays, tensors or lists of per-frame arrays."""
+    def as_tensor(x, shape, name):
+        if torch.is_tensor(x):
+            t = x.detach().to(dtype=torch.float64)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(v, np.float64) for v in x], np.float64)))
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError("%s must hold %s float64 values" % (name, tuple(shape)))
+        return t.reshape(shape).contiguous().to(dev)
+    return as_tensor(rotations, (n, 3, 3), "rotations"), as_tensor(translations, (n, 3), "translations")
+
+
+def posed_outputs_from_predictions(colors, boundaries, predictions, intrinsics, rotations, translations, is_hsv=False,
+                                   point_cloud_downsampling=1, min_threshold=None, max_threshold=None):
+    """endo_evaluate_posed (csrc/evaluate_posed.hip, three launches whatever the batch size) on a batch: what the reference's
+    utils.write_test_output_with_initial_pose (utils.py:1316-1355) computes per frame on the host.  colors (N, 3, H, W) the masked network
+    input, boundaries (N, 1, H, W) in {0, 1}, predictions (N, 1, H, W), intrinsics (N, 3, 3), fp32 on the device; rotations (N, 3, 3) and
+    translations (N, 3) float64, each frame's pose in the tracker's frame (arrays, tensors or lists of per-frame arrays).
+    min_threshold / max_threshold, when both are given, are utils.py:1285-1288's colour test (compared as float32).
+    Returns a dictionary: depth (N, 1, H, W); color_images (N, H, W, 3) uint8 in the reference's channel order -- an RGB input stays
+    R, G, B (the reference has no RGB -> BGR swap before cv2.imwrite, so its colour files have red and blue exchanged), an HSV input
+    becomes B, G, R; depth_images (N, H, W, 3) uint8 B, G, R; points (capacity N * H * W rows of x, y, z, r, g, b with (r, g, b) =
+    channels (2, 1, 0) of the colour image, as the reference reads them); offsets, the host list of N + 1 row offsets; ranges, the host
+    (N, 2) float32 array of each frame's (z_min, z_max) over its kept pixels: (+inf, -inf) for a frame without kept pixels (the
+    reference raises ZeroDivisionError there: its sentinels are Python ints), z_min == z_max for a frame whose coordinates are not
+    finite (scale = 20 / 0).  Offsets and ranges are the batch's one read back to the host."""
+    n, _, height, width = (int(v) for v in colors.shape)
+    colors = _device_f32(colors, (n, 3, height, width), "colors")
+    boundaries = _device_f32(boundaries, (n, 1, height, width), "boundaries")
+    predictions = _device_f32(predictions, (n, 1, height, width), "predictions")
+    intrinsics = _device_f32(intrinsics, (n, 3, 3), "intrinsics")
+    lib = _lib.load()
+    dev = colors.device
+    rotations, translations = _poses_f64(rotations, translations, n, dev)
+    use_thr = max_threshold is not None and min_threshold is not None
+    need = int(lib.endo_evaluate_posed_workspace_bytes(n, height, width))
+    if need < 0:
+        raise ValueError("a batch of %d frames of %d x %d is outside endo_evaluate_posed's sizes" % (n, height, width))
+    with torch.cuda.device(dev):
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        depth = torch.empty((n, 1, height, width), dtype=torch.float32, device=dev)
+        color_images = torch.empty((n, height, width, 3), dtype=torch.uint8, device=dev)
+        depth_images = torch.empty((n, height, width, 3), dtype=torch.uint8, device=dev)
+        points = torch.empty((n * height * width, 6), dtype=torch.float32, device=dev)
+        meta = torch.empty(8 * (n + 1) + 8 * n, dtype=torch.uint8, device=dev)          # offsets, then ranges: one read
+        offsets = meta[:8 * (n + 1)].view(torch.int64)
+        ranges = meta[8 * (n + 1):].view(torch.float32)
+        _lib.check(lib.endo_evaluate_posed(_lib.ptr(colors), _lib.ptr(boundaries), _lib.ptr(predictions), _lib.ptr(intrinsics),
+                                           _lib.ptr(rotations), _lib.ptr(translations), n, height, width, 1 if is_hsv else 0,
+                                           int(point_cloud_downsampling), 1 if use_thr else 0, float(min_threshold) if use_thr else 0.0,
+                                           float(max_threshold) if use_thr else 0.0, _lib.ptr(depth), _lib.ptr(color_images),
+                                           _lib.ptr(depth_images), _lib.ptr(points), _lib.ptr(offsets), _lib.ptr(ranges),
+                                           _lib.ptr(workspace), need, _lib.stream()), "endo_evaluate_posed")
+        host = meta.cpu().numpy()          # the batch's one read back (it waits for the stream)
+    return {"depth": depth, "color_images": color_images, "depth_images": depth_images, "points": points,
+            "offsets": host[:8 * (n + 1)].view(np.int64).tolist(), "ranges": host[8 * (n + 1):].view(np.float32).reshape(n, 2).copy()}
+
+
+def posed_test_outputs(model, batch, rotations, translations, is_hsv=False, point_cloud_downsampling=1, min_threshold=None,
+                       max_threshold=None):
+    """A TestFrames batch through the network in eval mode on ``boundaries * colors`` (evaluate.py:323-327) and
+    posed_outputs_from_predictions with the batch's poses.  Returns its dictionary plus colors (the masked input) and predictions."""
+    if model.training:
+        raise RuntimeError("posed_test_outputs runs the network in eval mode: call model.eval() first (evaluate.py:313)")
+    colors = batch["colors"]
+    if not torch.is_tensor(colors) or colors.dim() != 4 or colors.shape[1] != 3:
+        raise ValueError("colors must be an (N, 3, H, W) tensor")
+    n, _, height, width = (int(v) for v in colors.shape)
+    colors = _device_f32(colors, (n, 3, height, width), "colors")
+    boundaries = _device_f32(batch["boundaries"], (n, 1, height, width), "boundaries")
+    intrinsics = _device_f32(batch["intrinsics"], (n, 3, 3), "intrinsics")
+    with torch.no_grad(), torch.cuda.device(colors.device):
+        masked = boundaries * colors
+        pred = model(masked)
+    out = posed_outputs_from_predictions(masked, boundaries, pred, intrinsics, rotations, translations, is_hsv, point_cloud_downsampling,
+                                         min_threshold, max_threshold)
+    out["colors"], out["predictions"] = masked, pred
+    return out
+
+
+def _write_posed_frames(ready, names, color_images, depth_images, points, offsets, out_dir, write_ply, ply_text):
+    """One batch's files, on a writer thread, once the device-to-host copies have landed."""
+    ready.synchronize()
+    for f, name in enumerate(names):
+        if write_ply:
+            utils.write_point_cloud(os.path.join(out_dir, "test_point_cloud_{}.ply".format(name)),
+                                    points[offsets[f]:offsets[f + 1]].numpy(), text=ply_text)
+        if color_images is not None:
+            utils.write_png(os.path.join(out_dir, "test_color_{}.png".format(name)), color_images[f].numpy())
+            utils.write_png(os.path.join(out_dir, "test_depth_{}.png".format(name)), depth_images[f].numpy())
+
+
+def _write_merged(ready, path, parts, ply_text):
+    ready.synchronize()
+    rows = np.concatenate([p.numpy() for p in parts], axis=0) if parts else np.zeros((0, 6), np.float32)
+    utils.write_point_cloud(path, rows, text=ply_text)
+
+
+def run_posed_test_phase(model, frames, translation_dict, rotation_dict, out_dir, write_images=True, write_ply=True, ply_text=True,
+                         merged="sequence.ply", point_cloud_downsampling=1, min_threshold=None, max_threshold=None, writers=4):
+    """The reference's posed test output for a sequence (utils.write_test_output_with_initial_pose, utils.py:1316-1355, over a test-phase
+    loader): every batch of ``frames`` (a dataset.TestFrames) through posed_test_outputs with the poses
+    ``translation_dict[name]`` / ``rotation_dict[name]`` (reader.read_initial_pose_file), then per frame
+    ``test_point_cloud_<name>.ply``, ``test_color_<name>.png`` and ``test_depth_<name>.png`` in ``out_dir``: the reference's file names with
+    PNG in place of JPEG (there is no JPEG entropy coder here; the pixels are the ones the reference hands to cv2.imwrite, red and blue
+    exchanged for RGB input included).  All clouds are in the tracker's frame, so ``merged`` (a file name in ``out_dir``, or None) also
+    gets the whole sequence as one cloud, frame after frame.  A frame without kept pixels writes an empty cloud (the reference raises
+    ZeroDivisionError); a frame whose kept depths are all equal has non-finite coordinates, as in the reference: its own file is
+    written so, and it is left out of the merged cloud.  A frame whose name is missing from either dictionary raises KeyError before
+    anything runs.  The files are written on run_test_phase's writer pool.
+    Returns a dictionary: frames (the number of frames), empty and zero_range (the names of those two kinds of frames) and
+    merged_points (the number of rows of the merged cloud)."""
+    names_ahead = getattr(frames, "image_file_names", None)
+    if names_ahead is not None:
+        for name in names_ahead:
+            key = os.path.basename(str(name))[-12:-4]
+            translation_dict[key], rotation_dict[key]          # KeyError before anything runs
+    out_dir = str(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    count, merged_points = 0, 0
+    empty, zero_range, parts = [], [], []
+    pending = deque()
+    with ThreadPoolExecutor(max(1, int(writers))) as pool:
+        try:
+            for batch in frames:
+                names = list(batch["names"])
+                rotations = [rotation_dict[name] for name in names]
+                translations = [translation_dict[name] for name in names]
+                out = posed_test_outputs(model, batch, rotations, translations, is_hsv=getattr(frames, "is_hsv", False),
+                                         point_cloud_downsampling=point_cloud_downsampling, min_threshold=min_threshold,
+                                         max_threshold=max_threshold)
+                count += len(names)
+                offsets, ranges = out["offsets"], out["ranges"]
+                good = []
+                for f, name in enumerate(names):
+                    if ranges[f, 0] > ranges[f, 1]:
+                        empty.append(name)
+                    elif ranges[f, 0] == ranges[f, 1]:
+                        zero_range.append(name)
+                    else:
+                        good.append(f)
+                        merged_points += offsets[f + 1] - offsets[f]
+                if not (write_images or write_ply):
+                    continue
+                color_images = out["color_images"].to("cpu", non_blocking=True) if write_images else None
+                depth_images = out["depth_images"].to("cpu", non_blocking=True) if write_images else None
+                points = out["points"][:offsets[-1]].to("cpu", non_blocking=True) if write_ply else None
+                ready = torch.cuda.Event()
+                ready.record()
+                if write_ply and merged:
+                    parts.extend(points[offsets[f]:offsets[f + 1]] for f in good)
+                pending.append(pool.submit(_write_posed_frames, ready, names, color_images, depth_images, points, offsets, out_dir,
+                                           write_ply, ply_text))
+                while len(pending) > 2 * max(1, int(writers)):          # bound the host copies in flight
+                    pending.popleft().result()
+            if write_ply and merged:
+                ready = torch.cuda.Event()
+                ready.record()
+                pending.append(pool.submit(_write_merged, ready, os.path.join(out_dir, str(merged)), parts, ply_text))
+        finally:
+            while pending:
+                pending.popleft().result()
+    return {"frames": count, "empty": empty, "zero_range": zero_range, "merged_points": int(merged_points)}
+
+
+VALIDATION_TITLE ="Results (c1, sd1, d1, wd1, sf1, df1, c2, sd2, d2, wd2, sf2, df2)"          # evaluate.py:258
 
 
 def validation_outputs(model, batch, epsilon=1.0e-8, is_hsv=False, point_cloud_downsampling=1):

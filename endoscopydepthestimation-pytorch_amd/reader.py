@@ -198,6 +198,70 @@ def global_scale_estimation(extrinsics, point_cloud):
 
 
 # ---------------------------------------------------------------------------------------------
+# electromagnetic-tracker poses (utils.py:1298-1313, 1385-1402, 1747-1770, 1887-1897): what evaluate.run_posed_test_phase takes
+# ---------------------------------------------------------------------------------------------
+def read_initial_pose_file(file_path):
+    """-> (sorted frame indexes, {"%08d": translation (3,) float64}, {"%08d": rotation (3, 3) float64})  [utils.py:1385-1402]
+    One line per frame: ``index, tx, ty, tz, qw, qx, qy, qz``.  The rotation's y and z columns are negated, as the reference does."""
+    frame_indexes, translations, rotations = [], {}, {}
+    with open(str(file_path), "r") as stream:
+        for line in stream:
+            array = np.array(line.split(", "), dtype=np.float64)
+            name = "{:08d}".format(int(array[0]))
+            frame_indexes.append(int(array[0]))
+            translations[name] = array[1:4]
+            rotation = quaternion_matrix(array[4:])
+            rotation[:3, 1] = -rotation[:3, 1]          # flip y and z axes
+            rotation[:3, 2] = -rotation[:3, 2]
+            rotations[name] = rotation[:3, :3]
+    frame_indexes.sort()
+    return frame_indexes, translations, rotations
+
+
+def read_pose_messages_from_tracker(file_path):
+    """-> (list of (3,) translations, list of (3, 3) rotations), float64  [utils.py:1298-1313]
+    A header line, then per message five leading columns and ``x, y, z, qx, qy, qz, qw``, comma-separated."""
+    translations, rotations = [], []
+    with open(str(file_path), "r") as stream:
+        for count, line in enumerate(stream):
+            if count == 0:          # the header
+                continue
+            array = np.array(line.split(",")[5:], dtype=np.float64)
+            translations.append(array[:3])
+            qx, qy, qz, qw = array[3:]
+            rotations.append(quaternion_matrix([qw, qx, qy, qz])[:3, :3])
+    return translations, rotations
+
+
+def read_pose_corresponding_image_indexes(file_path):
+    """-> float32 array of the first column  [utils.py:1747-1755; float32 is the reference's dtype]"""
+    with open(str(file_path), "r") as stream:
+        indexes = [int(np.array(line.split(", "), dtype=np.float32)[0]) for line in stream]
+    return np.array(indexes, dtype=np.float32)
+
+
+def read_pose_corresponding_image_indexes_and_time_difference(file_path):
+    """-> (int32 frame indexes, int32 time differences)  [utils.py:1758-1770]"""
+    indexes, differences = [], []
+    with open(str(file_path), "r") as stream:
+        for line in stream:
+            array = np.array(line.split(", "), dtype=np.float32)
+            indexes.append(int(array[0]))
+            differences.append(int(array[1]))
+    return np.array(indexes, dtype=np.int32), np.array(differences, dtype=np.int32)
+
+
+def read_camera_to_tcp_transform(root):
+    """-> (rotation (3, 3), translation (3, 1)), float64, from the last line of ``root/camera_to_tcp``: twelve numbers, a 3 x 4 matrix in
+    row order  [utils.py:1887-1897, with float where the reference says np.float, which numpy 2 no longer has]"""
+    with open(os.path.join(str(root), "camera_to_tcp"), "r") as stream:
+        for line in stream:
+            values = np.array(line.split(" "), dtype=float)
+    transform = np.array(values[:12], dtype=float).reshape(3, 4)
+    return transform[:, :3], transform[:, 3].reshape((3, 1))
+
+
+# ---------------------------------------------------------------------------------------------
 # mask (utils.py:94-135 and dataset.py:27, 47: cv2.imread(..., IMREAD_GRAYSCALE))
 # ---------------------------------------------------------------------------------------------
 def read_mask(path):

@@ -1,5 +1,5 @@
 """Host-side helpers with the reference's names (reference utils.py:615-682 for the training path, 825-865 and 1405-1412 for the test phase,
-1462-1482 and 1734-1744 for teacher-student training)."""
+773-781 and 1246-1295 for the test output in the tracker's frame, 1462-1482 and 1734-1744 for teacher-student training)."""
 
 import torch
 
@@ -122,6 +122,72 @@ def point_cloud_from_depth(depth_map, color_img, mask_img, intrinsic_matrix, poi
     _lib.check(rc, "endo_point_cloud")
     n = int(count.item())
     return points[:n].cpu().numpy().reshape(-1, 6)
+
+
+def _host_f32(x, shape):
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(x.detach().cpu() if torch.is_tensor(x) else x), dtype=np.float32).reshape(shape)
+
+
+def _colors_from_u8(color_img, height, width):
+    """(1, 3, H, W) float32 colours c with uint8(255 * clip(0.5 c + 0.5, 0, 1)) == color_img exactly: c = (u + 0.5) / 127.5 - 1 puts
+    255 * (0.5 c + 0.5) at u + 0.5, half a unit from both truncation edges (u = 255: clipped to 1)."""
+    import numpy as np
+    u = np.asarray(color_img.detach().cpu() if torch.is_tensor(color_img) else color_img).reshape(height, width, 3).astype(np.uint8)
+    c = (u.astype(np.float32) + np.float32(0.5)) / np.float32(127.5) - np.float32(1.0)
+    return np.ascontiguousarray(c.transpose(2, 0, 1).reshape(1, 3, height, width), dtype=np.float32)
+
+
+def point_cloud_from_depth_and_initial_pose(depth_map, color_img, mask_img, intrinsic_matrix, translation, rotation,
+                                            point_cloud_downsampling, min_threshold=None, max_threshold=None, device="cuda"):
+    """Drop-in for reference utils.py:1246-1295 on the GPU (endo_evaluate_posed on one frame): (P, 6) float32 numpy array of
+    (x, y, z, r, g, b) over the kept pixels in row-major order, the cloud normalised to a z range of 20 units and moved into the
+    tracker's frame by ``rotation`` (3, 3) and ``translation`` (3,), float64.  As in the reference, (r, g, b) are channels (2, 1, 0) of
+    ``color_img`` (H, W, 3) uint8, the z range is that of the kept pixels whether or not the thresholds write them, and a mask
+    without kept pixels raises ZeroDivisionError (the reference's z_min / z_max sentinels are Python ints).  The arithmetic is the
+    reference's under numpy 2 (a float32 scale).  Inputs may be numpy arrays or tensors (any device); there is no CPU fallback."""
+    import numpy as np
+    from . import evaluate
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("point_cloud_from_depth_and_initial_pose needs a GPU device: the MI355X path has no CPU fallback")
+    shape = np.asarray(color_img.detach().cpu() if torch.is_tensor(color_img) else color_img).shape
+    height, width = int(shape[0]), int(shape[1])
+    depth = torch.from_numpy(_host_f32(depth_map, (1, 1, height, width))).to(dev)
+    mask = torch.from_numpy(_host_f32(mask_img, (1, 1, height, width))).to(dev)
+    k = torch.from_numpy(_host_f32(intrinsic_matrix, (1, 3, 3))).to(dev)
+    colors = torch.from_numpy(_colors_from_u8(color_img, height, width)).to(dev)
+    # the entry forms d = boundary * prediction: with the {0, 1}-valued mask as the boundary every kept pixel's d is depth_map's value
+    kept_mask = (mask > 0.5).to(torch.float32)
+    out = evaluate.posed_outputs_from_predictions(colors, kept_mask, depth, k, np.asarray(rotation, np.float64).reshape(1, 3, 3),
+                                                  np.asarray(translation, np.float64).reshape(1, 3), False, int(point_cloud_downsampling),
+                                                  min_threshold, max_threshold)
+    if out["ranges"][0, 0] > out["ranges"][0, 1]:
+        raise ZeroDivisionError("float division by zero")
+    return out["points"][:out["offsets"][1]].cpu().numpy().reshape(-1, 6)
+
+
+def display_depth_map(depth_map, min_value=None, max_value=None, device="cuda"):
+    """Drop-in for reference utils.py:773-781 with COLORMAP_JET on the GPU (endo_evaluate_posed's depth image of one frame): (H, W, 3)
+    uint8 B, G, R of COLORMAP_JET[uint8(|(d - min) / (max - min) * 255|)] with the map's own minimum and maximum.  A constant map
+    (0 / 0 in the reference) takes entry 0 everywhere.  The device entry takes the range from the map itself, which is what every call
+    in the reference does; explicit min_value / max_value raise NotImplementedError."""
+    import numpy as np
+    from . import evaluate
+    if min_value is not None and max_value is not None:
+        raise NotImplementedError("display_depth_map with an explicit range: endo_evaluate_posed takes each map's own minimum and maximum")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("display_depth_map needs a GPU device: the MI355X path has no CPU fallback")
+    d = np.asarray(depth_map.detach().cpu() if torch.is_tensor(depth_map) else depth_map, dtype=np.float32)
+    d = d.reshape(d.shape[0], d.shape[1])
+    height, width = d.shape
+    depth = torch.from_numpy(np.ascontiguousarray(d).reshape(1, 1, height, width)).to(dev)
+    ones = torch.ones((1, 1, height, width), dtype=torch.float32, device=dev)
+    zeros = torch.zeros((1, 3, height, width), dtype=torch.float32, device=dev)
+    k = torch.eye(3, dtype=torch.float32, device=dev).reshape(1, 3, 3)
+    out = evaluate.posed_outputs_from_predictions(zeros, ones, depth, k, np.eye(3).reshape(1, 3, 3), np.zeros((1, 3)))
+    return out["depth_images"][0].cpu().numpy()
 
 
 class _DistillFn(torch.autograd.Function):

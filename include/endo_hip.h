@@ -28,7 +28,7 @@
  *   2. The contents of a workspace or output buffer ON ENTRY are ignored: whatever a call reads from one, it has written itself
  *      earlier in the same call.  NaN, stale results of another shape, or zeros give the same result.
  *   SCRATCH (no meaning once the call's work has passed `stream`): gradws, the 16-bit families' `ws`, winner_scratch, row_offsets, and
- *   the workspaces of endo_warp_consistency, endo_jpeg_decode_crop, endo_augment, endo_evaluate, endo_display and
+ *   the workspaces of endo_warp_consistency, endo_jpeg_decode_crop, endo_augment, endo_evaluate, endo_evaluate_posed, endo_display and
  *   endo_evaluate_validation.
  *   STATE, i.e. written by one call and read by a later one, so the caller must leave it untouched in between:
  *     - `tape` (both network families): written by *_fwd, read (never written) by the matching *_bwd;
@@ -72,7 +72,8 @@ extern "C" {
  * ENDO_OPT_CHIP_DIVISOR; no existing signature changes; since then (unchanged by additions) endo_norm_l2_*, endo_norm_l1_*,
  * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each); then endo_warp_coordinates_* and
  * endo_image_warp_* (_fwd / _bwd each); then endo_photometric_workspace_floats, endo_photometric_fwd / _bwd,
- * endo_loss_head_photo_workspace_floats and endo_loss_head_photo; then endo_distill_head. */
+ * endo_loss_head_photo_workspace_floats and endo_loss_head_photo; then endo_distill_head; then endo_evaluate_posed and
+ * endo_evaluate_posed_workspace_bytes. */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -712,6 +713,41 @@ int64_t endo_evaluate_workspace_bytes(int frames, int height, int width);
 int endo_evaluate(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics, int frames,
                   int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
                   int64_t* frame_offsets, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Test output in the electromagnetic tracker's frame -- reference utils.py:1316-1355 (write_test_output_with_initial_pose: colour image,
+ * depth image) with utils.py:1246-1295 (point_cloud_from_depth_and_initial_pose) and utils.py:773-781 (display_depth_map), for N frames
+ * at once; numpy's float32 / float64 roundings under numpy 2's scalar promotion, bit for bit.  colors, boundaries, predictions,
+ * intrinsics: as endo_evaluate.  rotations [N][3][3] fp64 and translations [N][3] fp64: each frame's pose in the tracker's frame
+ * (reader.read_initial_pose_file).  Writes
+ *   depth          [N][1][H][W] fp32    d = boundaries * predictions
+ *   color_images   [N][H][W][3] uint8   u8(255 * clip(0.5 c + 0.5, 0, 1)), NOT multiplied by the boundary again and WITHOUT an RGB -> BGR
+ *                                       swap: channel k of an RGB input is channel k of the image, as the reference hands it to
+ *                                       cv2.imwrite; is_hsv = 1: cv2.COLOR_HSV2BGR_FULL of it, so B, G, R (PARITY UNPINNED against cv2)
+ *   depth_images   [N][H][W][3] uint8   B, G, R: COLORMAP_JET[u8(|(d - min) / (max - min) * 255|)] with the frame's whole-map min and max,
+ *                                       above 255 -> 255, at or below 0 -> 0 (a frame with max == min, 0 / 0 in the reference: entry 0)
+ *   points         capacity N * H * W rows of (x, y, z, r, g, b) fp32, frame-major, row-major inside a frame: every KEPT pixel
+ *                                       (h % downsampling == 0, w % downsampling == 0, boundary > 0.5) that, with use_thresholds = 1,
+ *                                       also has max(r, g, b) >= max_threshold and min(r, g, b) <= min_threshold.
+ *                                       p = ((w - cx) / fx * d, (h - cy) / fy * d, d) * scale in fp32, scale = 20 / (z_max - z_min) over
+ *                                       the frame's KEPT pixels; (x, y, z) = fp32(((R_i0 p_x + R_i1 p_y) + R_i2 p_z) + t_i) in fp64, no
+ *                                       contraction; (r, g, b) = channels (2, 1, 0) of the colour image, as the reference reads them
+ *   frame_offsets  [N + 1] int64        frame f's rows are [frame_offsets[f], frame_offsets[f + 1])
+ *   frame_ranges   [N][2] fp32          (z_min, z_max) of the frame's kept pixels; (+inf, -inf) when there is none (the reference raises
+ *                                       ZeroDivisionError there).  z_max == z_min: scale = inf and the frame's coordinates are not finite,
+ *                                       as in the reference
+ * Three launches whatever N.  N <= 65535, N * H * W < 2^31.  ENDO_E_BADARG for null pointers, bad sizes, is_hsv or use_thresholds not
+ * 0 / 1, NaN thresholds in use, downsampling < 1 or a short workspace. */
+/* device workspace bytes of endo_evaluate_posed (-1 for bad sizes).  The workspace is scratch: contents on entry ignored, nothing
+ * outside workspace_bytes written; depth, both images, frame_offsets and frame_ranges are written in full, `points` up to
+ * frame_offsets[frames] rows.  The outputs and the workspace must not overlap the inputs or one another: the write launch reads the
+ * boundaries and the row offsets again after frame_ranges and depth have been written. */
+int64_t endo_evaluate_posed_workspace_bytes(int frames, int height, int width);
+int endo_evaluate_posed(const float* colors, const float* boundaries, const float* predictions, const float* intrinsics,
+                        const double* rotations, const double* translations, int frames, int height, int width, int is_hsv,
+                        int point_cloud_downsampling, int use_thresholds, float min_threshold, float max_threshold, float* depth,
+                        uint8_t* color_images, uint8_t* depth_images, float* points, int64_t* frame_offsets, float* frame_ranges,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Display panel of a training or validation batch -- reference train.py:353-371 / 460-478 (utils.display_color_depth_sparse_flow_
