@@ -51,6 +51,7 @@ SIGNATURES = {
     "endo_warp_consistency_workspace_floats": (_L, [_I, _I, _I]),
     "endo_warp_consistency_bytes": (_L, [_I, _I, _I]),
     "endo_warp_consistency": (_I, [_P] * 8 + [_F, _F] + [_P] * 4 + [_I, _I, _I, _P]),
+    "endo_warp_consistency_forms": (_I, [_P] * 8 + [_F, _F] + [_P] * 4 + [_I, _I, _I, _I, _F, _P]),
     "endo_warp_fallback_blocks": (_I, [_P, _P, _I]),
     "endo_warp_coordinates_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "endo_warp_coordinates_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
@@ -61,6 +62,7 @@ SIGNATURES = {
     "endo_photometric_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "endo_loss_head_photo_workspace_floats": (_L, [_I, _I, _I]),
     "endo_loss_head_photo": (_I, [_P] * 18 + [_F, _F, _F, _F, _I] + [_P] * 4 + [_I, _I, _I, _P]),
+    "endo_loss_head_forms": (_I, [_P] * 18 + [_F, _F, _F, _F, _I] + [_P] * 4 + [_I, _I, _I, _I, _F, _P]),
     "endo_distill_head": (_I, [_P] * 5 + [_F, _F, _I] + [_P] * 4 + [_I, _I, _P]),
     "endo_bf16_pack_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "endo_f16_pack_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -195,7 +195,9 @@ int endo_sparse_l1_fwd_impl(const float* flows, const float* flows_hat, const fl
 int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
                            const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics, float dcl_weight,
                            float eps, float* loss, float* grad_depth_1, float* grad_depth_2, float* workspace, int n, int h, int w,
-                           int zero_grads, hipStream_t stream);
+                           int zero_grads, int form, float form_eps, hipStream_t stream);
+// geometry.hip: a loss form ENDO_CONSISTENCY_* (include/endo_hip.h) and a finite, positive eps for it
+bool endo_consistency_form_ok(int form, float form_eps);
 // geometry.hip: where phase 1 leaves the two intersect masks (n x h x w floats each) in endo_consistency_phase's workspace
 void endo_consistency_intersect_planes(float* workspace, int n, int h, int w, float** inter_1, float** inter_2);
 

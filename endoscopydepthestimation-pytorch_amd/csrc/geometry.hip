@@ -546,6 +546,8 @@ __global__ void __launch_bounds__(256) warp_bwd_tiled_kernel(const float* __rest
 // pose 1-wrt-2; z = 1: the roles swapped):
 //   consistency_fwd_kernel   the tiled warp forward; per pixel the four NormalizedDistanceLoss sums of its sample (block reduction,
 //                            one fp64 atomic per sum and block); it also ZEROES its tile of this direction's own gradient output.
+//                            (The loss is a template parameter, ConsistencyForm below: the reference's three other consistency losses
+//                            are the same pattern with other integrands -- endo_warp_consistency_forms, endo_loss_head_forms.)
 //   consistency_finalize_kernel  one wave: the 2 x n x 4 sums -> the loss and the per-sample coefficients (d loss / d numerator,
 //                            d loss / d denominator) the backward kernel needs.
 //   consistency_bwd_kernel   per pixel the loss's gradient w.r.t. its own depth and w.r.t. the warped depth, the latter pushed
@@ -568,7 +570,7 @@ struct ConsistencyArgs {
     float* warped[2];                // direction z: depth[1 - z] warped into frame z
     float* inter[2];
     float* grad[2];                  // d loss / d depth[z]
-    double* stats;                   // [2][n][kStatStride], the first 4: sum m a, sum m, sum m |P - Pw|_1, sum m (a + |b|)   (zeroed by the caller)
+    double* stats;                   // [2][n][kStatStride], the first 4: sum m a, sum m, sum m |P - Pw|_1, sum m (a + |b|)   (zeroed by the caller; the other forms' sums: ConsistencyForm)
     float* coef;                     // [2][n][2]  (d loss / d numerator, d loss / d denominator) of sample n in direction z
     float* loss;
     float c_dcl;                     // dcl_weight * 0.5
@@ -576,11 +578,41 @@ struct ConsistencyArgs {
     int n, h, w, tiles_x;
     int zero_grads;                  // 1: the forward kernel zeroes grad[]; 0: the caller has initialised them (endo_loss_head: the flow terms)
     int loss_in_bwd;                 // 1: no finalize kernel ran; the backward kernel's first block writes the loss
+    int form;                        // ConsistencyForm: the finalize kernel's switch (the forward and backward kernels take it as a template parameter)
+    float form_eps;                  // the loss module's eps of the forms other than kFormDistance (which holds its module's 1e-5)
 };
+
+// The loss between a depth map (a), the other frame's warped into it (b) and the intersect mask (m) -- the reference's four consistency
+// losses, each as losses.hip's module kernels write it (norm_dist_*, ratio_reduce<F>, ratio_den<F>, weighted_l2_finalize, ratio_bwd_kernel<F>):
+//   kFormDistance    NormalizedDistanceLoss          (losses.py:112-146)  sums  m a, m, m |P - Pw|_1, m (a + |b|)
+//   kFormL2          NormalizedL2Loss                (losses.py:94-109)   sums  m a, m, m (a-b)^2, m (a^2+b^2);  den = 0.5 s3 + 1e-5 mu^2, mu constant
+//   kFormL1          NormalizedL1Loss                (losses.py:149-164)  sums  m a, m, m |a-b|, m (|a|+|b|);     den = 0.5 s3 + 1e-5 mu, mu differentiated
+//   kFormWeightedL2  NormalizedWeightedMaskedL2Loss  (losses.py:35-54)    sums  m (a-b)^2, m (a^2+b^2);           den = 0.5 s1 + eps,
+//                    batch value sum_n w_n term_n / sum_n w_n with w_n = 1 / (1e-8 + |t_n|) of the direction's translations
+// The forms other than kFormDistance always run the finalize kernel: it leaves (d loss / d num, d loss / d den) of every (direction,
+// sample) in `coef` -- for the weighted form that takes the whole batch's weights, which no block of the backward kernel should re-add.
+enum ConsistencyForm { kFormDistance = 0, kFormL2 = 1, kFormL1 = 2, kFormWeightedL2 = 3 };
+constexpr int kFormCount = 4;
+
+// The intrinsics the distance form's pixel rays need (ax = (x - cx) / fx, ay likewise), loaded once per block; the other forms hold nothing.
+template <int F>
+struct RayIntrinsics {
+    __device__ RayIntrinsics(const float*, int) {}
+};
+template <>
+struct RayIntrinsics<kFormDistance> {
+    float fx, fy, cx, cy;
+    __device__ RayIntrinsics(const float* K, int n) : fx(K[9 * n + 0]), fy(K[9 * n + 4]), cx(K[9 * n + 2]), cy(K[9 * n + 5]) {}
+};
+
+__device__ __forceinline__ float translation_weight(const float* __restrict__ t, int i) {
+    const float tx = t[3 * i], ty = t[3 * i + 1], tz = t[3 * i + 2];
+    return 1.0f / (1.0e-8f + sqrtf(tx * tx + ty * ty + tz * tz));
+}
 
 __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
-template <int TY, int TX>
+template <int TY, int TX, int F>
 __global__ void __launch_bounds__(256) consistency_fwd_kernel(const ConsistencyArgs a) {
     using T = WarpTile<TY, TX>;
     __shared__ Camera cam;
@@ -636,8 +668,11 @@ __global__ void __launch_bounds__(256) consistency_fwd_kernel(const ConsistencyA
         }
         __syncthreads();
     }
-    const float fx = a.K[9 * n + 0], fy = a.K[9 * n + 4], cx = a.K[9 * n + 2], cy = a.K[9 * n + 5];
-    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    constexpr int kSums = (F == kFormWeightedL2) ? 2 : 4;
+    const RayIntrinsics<F> k9(a.K, n);
+    float part[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) part[k] = 0.f;
 #pragma unroll
     for (int k = 0; k < T::kPix; ++k) {
         const int idx = threadIdx.x + k * T::kThreads;
@@ -664,21 +699,78 @@ __global__ void __launch_bounds__(256) consistency_fwd_kernel(const ConsistencyA
         a.warped[z][o] = acc;
         a.inter[z][o] = mi;
         if (a.zero_grads) a.grad[z][o] = 0.f;          // the backward kernel accumulates into it
-        // NormalizedDistanceLoss sums (norm_dist_reduce, losses.hip): a = own depth, b = warped depth
-        const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
-        const float av = dself[k], b = acc;
-        part[0] += mi * av;
-        part[1] += mi;
-        part[2] += mi * fabsf(ax * av - ax * b) + mi * fabsf(ay * av - ay * b) + mi * fabsf(av - b);
-        part[3] += mi * (av + fabsf(b));
+        const float av = dself[k], b = acc;          // a = own depth, b = warped depth
+        if constexpr (F == kFormDistance) {
+            // NormalizedDistanceLoss sums (norm_dist_reduce, losses.hip)
+            const float fx = k9.fx, fy = k9.fy, cx = k9.cx, cy = k9.cy;
+            const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
+            part[0] += mi * av;
+            part[1] += mi;
+            part[2] += mi * fabsf(ax * av - ax * b) + mi * fabsf(ay * av - ay * b) + mi * fabsf(av - b);
+            part[3] += mi * (av + fabsf(b));
+        } else if constexpr (F == kFormWeightedL2) {
+            // ratio_reduce<kWeightedL2> (losses.hip)
+            part[0] += mi * (av - b) * (av - b);
+            part[1] += mi * (av * av + b * b);
+        } else {
+            // ratio_reduce<kNormL2 / kNormL1> (losses.hip)
+            part[0] += mi * av;
+            part[1] += mi;
+            part[2] += (F == kFormL2) ? mi * (av - b) * (av - b) : mi * fabsf(av - b);
+            part[3] += (F == kFormL2) ? mi * (av * av + b * b) : mi * (fabsf(av) + fabsf(b));
+        }
     }
-    block_sum_atomic<4>(part, a.stats + kStatStride * (z * a.n + n), scratch);
+    block_sum_atomic<kSums>(part, a.stats + kStatStride * (z * a.n + n), scratch);
 }
 
 // loss and the backward pass's per-sample coefficients from the 2 x n x 4 sums.  A kernel of its own, one wave: the "last block of the
 // forward kernel finalises" form needs a device-scope fence in every block, which on this part writes back and invalidates the XCD's L2
 // -- 2560 blocks of it made the forward kernel 222 us instead of ~15 (profiles/r04_warp_consistency_kernel_stats.txt history).
 __global__ void consistency_finalize_kernel(const ConsistencyArgs a) {
+    if (a.form == kFormWeightedL2) {
+        // ratio_den<kWeightedL2> and weighted_l2_finalize (losses.hip) per direction: the weights of the direction's translations, their
+        // sum over the batch (lanes stride over the samples, a wave reduction adds), then per (direction, sample) the term and the
+        // coefficients under the upstream factor w_n / sum w
+        float wsum[2], acc[2] = {0.f, 0.f};
+        for (int z = 0; z < 2; ++z) {
+            float part = 0.f;
+            for (int i = threadIdx.x; i < a.n; i += 64) part += translation_weight(a.t[z], i);
+            wsum[z] = __shfl(wave_sum(part), 0, 64);
+        }
+        for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
+            const int z = i / a.n;
+            const double* st = a.stats + kStatStride * i;
+            const float num = static_cast<float>(st[0]);
+            const float den = 0.5f * static_cast<float>(st[1]) + a.form_eps;
+            const float wgt = translation_weight(a.t[z], i - z * a.n);
+            acc[z] += num / den * wgt;
+            const float g = a.c_dcl * wgt / wsum[z];                      // d loss / d (this sample's term)
+            a.coef[2 * i] = g / den;
+            a.coef[2 * i + 1] = -g * num / (den * den);
+        }
+        acc[0] = wave_sum(acc[0]);
+        acc[1] = wave_sum(acc[1]);
+        if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (acc[0] / wsum[0] + acc[1] / wsum[1]);
+        return;
+    }
+    if (a.form == kFormL2 || a.form == kFormL1) {
+        // ratio_den<kNormL2 / kNormL1> and norm_ratio_finalize (losses.hip); the L1 form's third constant, d (1e-5 mu) / d a, is
+        // re-formed from the sums by the backward kernel
+        float term = 0.f;
+        for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
+            const double* st = a.stats + kStatStride * i;
+            const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
+            const float mean_value = s0 / (a.form_eps + s1);
+            const float den = 0.5f * s3 + ((a.form == kFormL2) ? 1.0e-5f * mean_value * mean_value : 1.0e-5f * mean_value);
+            term += s2 / den;
+            const float g = a.c_dcl / static_cast<float>(a.n);
+            a.coef[2 * i] = g / den;
+            a.coef[2 * i + 1] = -g * s2 / (den * den);
+        }
+        term = wave_sum(term);
+        if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
+        return;
+    }
     // lane i < 2 n owns (direction, sample) i: its term and coefficients; a wave reduction adds the terms (n <= 32; larger batches loop)
     float term = 0.f;
     for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
@@ -695,7 +787,7 @@ __global__ void consistency_finalize_kernel(const ConsistencyArgs a) {
     if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
 }
 
-template <int TY, int TX>
+template <int TY, int TX, int F>
 __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyArgs a) {
     using T = WarpTile<TY, TX>;
     __shared__ Camera cam;
@@ -714,8 +806,13 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
     const int tx0 = (blockIdx.x % a.tiles_x) * TX, ty0 = (blockIdx.x / a.tiles_x) * TY;
     // this sample's coefficients from the forward kernel's sums (consistency_finalize_kernel's arithmetic; the stand-alone call skips
     // that kernel and block (0, 0, 0) writes the loss here)
-    float cnum, cden;
-    {
+    float cnum, cden, cmean = 0.f;
+    if constexpr (F != kFormDistance) {
+        // the finalize kernel's coefficients; L1: d (1e-5 mu) / d a per masked pixel (ratio_bwd_kernel's cmean, losses.hip)
+        cnum = a.coef[2 * (z * a.n + n)];
+        cden = a.coef[2 * (z * a.n + n) + 1];
+        if constexpr (F == kFormL1) cmean = 1.0e-5f / (a.form_eps + static_cast<float>(a.stats[kStatStride * (z * a.n + n) + 1]));
+    } else {
         const double* st = a.stats + kStatStride * (z * a.n + n);
         const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
         const float den = 1.0e-5f * (s0 / (1.0e-5f + s1)) + s3;
@@ -723,7 +820,7 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
         cnum = 2.0f * g / den;
         cden = -2.0f * g * s2 / (den * den);
     }
-    if (a.loss_in_bwd && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) {
+    if (F == kFormDistance && a.loss_in_bwd && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) {
         float term = 0.f;
         for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
             const double* st = a.stats + kStatStride * i;
@@ -733,7 +830,7 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
         term = wave_sum(term);
         if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
     }
-    const float fx = a.K[9 * n + 0], fy = a.K[9 * n + 4], cx = a.K[9 * n + 2], cy = a.K[9 * n + 5];
+    const RayIntrinsics<F> k9(a.K, n);
     Taps tp[T::kPix];
     float qxs[T::kPix], qys[T::kPix], qzs[T::kPix], zts[T::kPix], nxs[T::kPix], nys[T::kPix], mpix[T::kPix], dself[T::kPix];
     bool opens[T::kPix];
@@ -786,12 +883,31 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
         if (yy >= h || xx >= w) continue;
         const Taps& q = tp[k];
         const int64_t o = base + static_cast<int64_t>(yy) * w + xx;
-        // the loss's gradient at this pixel (norm_dist_bwd_kernel, losses.hip): a = own depth, b = warped depth, m = intersection mask
-        const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
+        // the loss's gradient at this pixel: a = own depth, b = warped depth, m = intersection mask
         const float mi = a.inter[z][o], av = dself[k], b = a.warped[z][o];
-        const float tt = ax * sgnf(ax * av - ax * b) + ay * sgnf(ay * av - ay * b) + sgnf(av - b);
-        const float g_own = mi * (cnum * tt + cden);
-        const float g = mi * (-cnum * tt + cden * sgnf(b));          // d loss / d warped: the warp backward's incoming gradient
+        float g_own, g;          // d loss / d own depth; d loss / d warped: the warp backward's incoming gradient
+        if constexpr (F == kFormDistance) {
+            // norm_dist_bwd_kernel (losses.hip)
+            const float fx = k9.fx, fy = k9.fy, cx = k9.cx, cy = k9.cy;
+            const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
+            const float tt = ax * sgnf(ax * av - ax * b) + ay * sgnf(ay * av - ay * b) + sgnf(av - b);
+            g_own = mi * (cnum * tt + cden);
+            g = mi * (-cnum * tt + cden * sgnf(b));
+        } else {
+            // ratio_bwd_kernel<F> (losses.hip): d num / d a (= -d num / d b), d den / d a, d den / d b, each per unit of mask
+            float ta, da, db;
+            if constexpr (F == kFormL1) {
+                ta = sgnf(av - b);
+                da = 0.5f * sgnf(av) + cmean;
+                db = 0.5f * sgnf(b);
+            } else {
+                ta = 2.0f * (av - b);
+                da = av;
+                db = b;
+            }
+            g_own = mi * (cnum * ta + cden * da);
+            g = mi * (cnum * -ta + cden * db);
+        }
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         const bool val[4] = {q.vw && q.vn, q.ve && q.vn, q.vw && q.vs, q.ve && q.vs};
         const float wt[4] = {q.wnw, q.wne, q.wsw, q.wse};
@@ -1015,7 +1131,8 @@ extern "C" int64_t endo_warp_consistency_bytes(int n, int h, int w) {
 int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
                            const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics, float dcl_weight,
                            float eps, float* loss, float* grad_depth_1, float* grad_depth_2, float* workspace, int n, int h, int w,
-                           int zero_grads, hipStream_t stream) {
+                           int zero_grads, int form, float form_eps, hipStream_t stream) {
+    if (form < 0 || form >= kFormCount) return ENDO_E_BADARG;
     const int64_t p = static_cast<int64_t>(n) * h * w;
     float* ws = workspace;
     auto take = [&](int64_t count) { float* q = ws; ws += (count + 3) / 4 * 4; return q; };
@@ -1035,17 +1152,29 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
     a.eps = eps;
     a.n = n; a.h = h; a.w = w;
     a.zero_grads = zero_grads;
-    a.loss_in_bwd = zero_grads;          // the stand-alone call (endo_warp_consistency) needs the loss only at its end
+    a.loss_in_bwd = zero_grads && form == kFormDistance;          // the stand-alone call (endo_warp_consistency) needs the loss only at its end
+    a.form = form;
+    a.form_eps = form_eps;
     constexpr int TY = kWarpTileH, TX = kWarpTileW;
     a.tiles_x = (w + TX - 1) / TX;
     const int tiles_y = (h + TY - 1) / TY;
     const dim3 grid(a.tiles_x * tiles_y, n, 2);
     if (phase == 1) {
         ENDO_CHECK(hipMemsetAsync(zeroed, 0, sizeof(float) * (2 * 2 * kStatStride * n), stream));
-        consistency_fwd_kernel<TY, TX><<<grid, 256, 0, stream>>>(a);
+        switch (form) {
+            case kFormDistance: consistency_fwd_kernel<TY, TX, kFormDistance><<<grid, 256, 0, stream>>>(a); break;
+            case kFormL2: consistency_fwd_kernel<TY, TX, kFormL2><<<grid, 256, 0, stream>>>(a); break;
+            case kFormL1: consistency_fwd_kernel<TY, TX, kFormL1><<<grid, 256, 0, stream>>>(a); break;
+            default: consistency_fwd_kernel<TY, TX, kFormWeightedL2><<<grid, 256, 0, stream>>>(a); break;
+        }
         if (!a.loss_in_bwd) consistency_finalize_kernel<<<1, 64, 0, stream>>>(a);          // the loss head reads the loss between the phases
     } else {
-        consistency_bwd_kernel<TY, TX><<<grid, 256, 0, stream>>>(a);
+        switch (form) {
+            case kFormDistance: consistency_bwd_kernel<TY, TX, kFormDistance><<<grid, 256, 0, stream>>>(a); break;
+            case kFormL2: consistency_bwd_kernel<TY, TX, kFormL2><<<grid, 256, 0, stream>>>(a); break;
+            case kFormL1: consistency_bwd_kernel<TY, TX, kFormL1><<<grid, 256, 0, stream>>>(a); break;
+            default: consistency_bwd_kernel<TY, TX, kFormWeightedL2><<<grid, 256, 0, stream>>>(a); break;
+        }
     }
     ENDO_LAUNCH_CHECK();
     return 0;
@@ -1058,10 +1187,10 @@ void endo_consistency_intersect_planes(float* workspace, int n, int h, int w, fl
     *inter_2 = workspace + 3 * piece;
 }
 
-extern "C" int endo_warp_consistency(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
-                                     const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
-                                     float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
-                                     float* workspace, int n, int h, int w, void* stream_) {
+static int warp_consistency_impl(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
+                                 const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
+                                 float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
+                                 float* workspace, int n, int h, int w, int form, float form_eps, void* stream_) {
     if (!depth_1 || !depth_2 || !boundaries || !t_1_wrt_2 || !r_1_wrt_2 || !t_2_wrt_1 || !r_2_wrt_1 || !intrinsics || !loss ||
         !grad_depth_1 || !grad_depth_2 || !workspace || n <= 0 || h <= 0 || w <= 0)
         return ENDO_E_BADARG;
@@ -1071,8 +1200,30 @@ extern "C" int endo_warp_consistency(const float* depth_1, const float* depth_2,
     ProfScope prof(kProfGeometry, stream, 0.0, 160.0 * static_cast<double>(n) * h * w);
     for (int phase = 1; phase <= 2; ++phase) {
         const int rc = endo_consistency_phase(phase, depth_1, depth_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics,
-                                              dcl_weight, eps, loss, grad_depth_1, grad_depth_2, workspace, n, h, w, 1, stream);
+                                              dcl_weight, eps, loss, grad_depth_1, grad_depth_2, workspace, n, h, w, 1, form, form_eps, stream);
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int endo_warp_consistency(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
+                                     const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
+                                     float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
+                                     float* workspace, int n, int h, int w, void* stream_) {
+    return warp_consistency_impl(depth_1, depth_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps, loss,
+                                 grad_depth_1, grad_depth_2, workspace, n, h, w, kFormDistance, 1.0e-5f, stream_);
+}
+
+// form_eps: finite and positive (the comparison is false for NaN)
+bool endo_consistency_form_ok(int form, float form_eps) {
+    return form >= 0 && form < kFormCount && form_eps > 0.0f && form_eps <= 3.0e38f;
+}
+
+extern "C" int endo_warp_consistency_forms(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
+                                           const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
+                                           float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
+                                           float* workspace, int n, int h, int w, int form, float form_eps, void* stream_) {
+    if (!endo_consistency_form_ok(form, form_eps)) return ENDO_E_BADARG;
+    return warp_consistency_impl(depth_1, depth_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps, loss,
+                                 grad_depth_1, grad_depth_2, workspace, n, h, w, form, form_eps, stream_);
 }

@@ -6,6 +6,7 @@
 // step the GPU sat idle for 0.35 ms there.  The backward half runs unconditionally (it is cheap); the caller still decides on
 // the non-finite guard from the loss value before it differentiates the network.
 // endo_loss_head_photo is the same body with the photometric term (image_warp.hip) in both directions: three launches more.
+// endo_loss_head_forms is either of the two with the depth-consistency loss chosen (geometry.hip ConsistencyForm): the same launches.
 #include "common.h"
 
 namespace endo {
@@ -155,9 +156,10 @@ extern "C" int64_t endo_loss_head_photo_workspace_floats(int n, int h, int w) {
     return 36 * p + 128 * n + 264;
 }
 
-// The body of endo_loss_head and endo_loss_head_photo.  photo = false: colors_*, photo_weight and padding_mode are unused, losses has
-// four floats, and the launches, values and workspace layout are endo_loss_head's.
-static int loss_head_impl(bool photo, const float* colors_1, const float* colors_2, float photo_weight, int padding_mode,
+// The body of endo_loss_head, endo_loss_head_photo and endo_loss_head_forms.  photo = false: colors_*, photo_weight and padding_mode are
+// unused, losses has four floats, and the launches, values and workspace layout are endo_loss_head's.  form, form_eps: the
+// depth-consistency loss (ENDO_CONSISTENCY_*) and its module's eps, handed to endo_consistency_phase.
+static int loss_head_impl(bool photo, int form, float form_eps, const float* colors_1, const float* colors_2, float photo_weight, int padding_mode,
                           const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
                               const float* sparse_depths_2, const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
                               const float* sparse_flows_1, const float* sparse_flows_2, const float* sparse_flow_masks_1,
@@ -212,7 +214,7 @@ static int loss_head_impl(bool photo, const float* colors_1, const float* colors
     // depth warp both ways + depth-consistency loss: the two fused kernels of endo_warp_consistency (geometry.hip); the forward one
     // leaves dcl_weight * 0.5 * (term_1 + term_2) in parts[4] and the backward coefficients in its workspace
     HEAD(endo_consistency_phase(1, scaled_1, scaled_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps,
-                                parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, stream));
+                                parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, form, form_eps, stream));
     // the photometric term, both directions in one kernel: each frame's masked colours against the other's sampled at its own scaled
     // depth, under the intersect mask the consistency kernel has just written
     const float* ph_c1[2] = {colors_1, colors_2};
@@ -248,7 +250,7 @@ static int loss_head_impl(bool photo, const float* colors_1, const float* colors
     HEAD(endo_flow_from_depth_bwd(g_flow_1, scaled_1, boundaries, t_1_wrt_2, r_1_wrt_2, intrinsics, g_s1, n, h, w, stream_));
     HEAD(endo_flow_from_depth_bwd(g_flow_2, scaled_2, boundaries, t_2_wrt_1, r_2_wrt_1, intrinsics, g_s2, n, h, w, stream_));
     HEAD(endo_consistency_phase(2, scaled_1, scaled_2, boundaries, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, dcl_weight, eps,
-                                parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, stream));
+                                parts + 4, g_s1, g_s2, cons_ws, n, h, w, 0, form, form_eps, stream));
     if (photo) {          // += the photometric terms: stream order, one writer per element
         const float* ph_up[2] = {up + 2, up + 2};
         float* ph_grad[2] = {g_s1, g_s2};
@@ -267,10 +269,10 @@ extern "C" int endo_loss_head(const float* pred_1, const float* pred_2, const fl
                               const float* sparse_flow_masks_2, const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1,
                               const float* r_2_wrt_1, const float* intrinsics, float sfl_weight, float dcl_weight, float eps,
                               float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace, int n, int h, int w, void* stream_) {
-    return loss_head_impl(false, nullptr, nullptr, 0.0f, 0, pred_1, pred_2, boundaries, sparse_depths_1, sparse_depths_2, sparse_depth_masks_1,
-                          sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1, sparse_flow_masks_2, t_1_wrt_2, r_1_wrt_2,
-                          t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses, grad_pred_1, grad_pred_2, workspace, n, h, w,
-                          stream_);
+    return loss_head_impl(false, ENDO_CONSISTENCY_DISTANCE, 1.0e-5f, nullptr, nullptr, 0.0f, 0, pred_1, pred_2, boundaries, sparse_depths_1,
+                          sparse_depths_2, sparse_depth_masks_1, sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1,
+                          sparse_flow_masks_2, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses,
+                          grad_pred_1, grad_pred_2, workspace, n, h, w, stream_);
 }
 
 extern "C" int endo_loss_head_photo(const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
@@ -281,10 +283,27 @@ extern "C" int endo_loss_head_photo(const float* pred_1, const float* pred_2, co
                                     float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode, float* losses,
                                     float* grad_pred_1, float* grad_pred_2, float* workspace, int n, int h, int w, void* stream_) {
     if (!colors_1 || !colors_2 || padding_mode < 0 || padding_mode > 2 || !(photo_weight >= 0.0f)) return ENDO_E_BADARG;
-    return loss_head_impl(true, colors_1, colors_2, photo_weight, padding_mode, pred_1, pred_2, boundaries, sparse_depths_1, sparse_depths_2,
-                          sparse_depth_masks_1, sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1, sparse_flow_masks_2,
-                          t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses, grad_pred_1,
-                          grad_pred_2, workspace, n, h, w, stream_);
+    return loss_head_impl(true, ENDO_CONSISTENCY_DISTANCE, 1.0e-5f, colors_1, colors_2, photo_weight, padding_mode, pred_1, pred_2, boundaries,
+                          sparse_depths_1, sparse_depths_2, sparse_depth_masks_1, sparse_depth_masks_2, sparse_flows_1, sparse_flows_2,
+                          sparse_flow_masks_1, sparse_flow_masks_2, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight,
+                          eps, losses, grad_pred_1, grad_pred_2, workspace, n, h, w, stream_);
+}
+
+extern "C" int endo_loss_head_forms(const float* pred_1, const float* pred_2, const float* boundaries, const float* sparse_depths_1,
+                                    const float* sparse_depths_2, const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
+                                    const float* sparse_flows_1, const float* sparse_flows_2, const float* sparse_flow_masks_1,
+                                    const float* sparse_flow_masks_2, const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1,
+                                    const float* r_2_wrt_1, const float* intrinsics, const float* colors_1, const float* colors_2,
+                                    float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode, float* losses,
+                                    float* grad_pred_1, float* grad_pred_2, float* workspace, int n, int h, int w, int form, float form_eps,
+                                    void* stream_) {
+    if (!endo_consistency_form_ok(form, form_eps) || !(photo_weight >= 0.0f)) return ENDO_E_BADARG;
+    const bool photo = photo_weight > 0.0f;          // without the term: endo_loss_head's launches, four losses, colours unread
+    if (photo && (!colors_1 || !colors_2 || padding_mode < 0 || padding_mode > 2)) return ENDO_E_BADARG;
+    return loss_head_impl(photo, form, form_eps, colors_1, colors_2, photo_weight, padding_mode, pred_1, pred_2, boundaries, sparse_depths_1,
+                          sparse_depths_2, sparse_depth_masks_1, sparse_depth_masks_2, sparse_flows_1, sparse_flows_2, sparse_flow_masks_1,
+                          sparse_flow_masks_2, t_1_wrt_2, r_1_wrt_2, t_2_wrt_1, r_2_wrt_1, intrinsics, sfl_weight, dcl_weight, eps, losses,
+                          grad_pred_1, grad_pred_2, workspace, n, h, w, stream_);
 }
 
 extern "C" int endo_loss_head_planes(int n, int h, int w, int64_t* offsets) {

@@ -10,6 +10,8 @@ PhotometricLoss (not a reference class) is the chain _warp_coordinate_generate -
 backward kernel.
 """
 
+import collections
+
 import torch
 from torch import nn
 
@@ -414,6 +416,15 @@ class SparseMaskedL1LossDisplay(nn.Module):
 
 
 _consistency_ws = {}
+# The depth-consistency losses the fused kernels hold (csrc/geometry.hip ConsistencyForm): name -> (ENDO_CONSISTENCY_* of
+# include/endo_hip.h, the class, the name of its eps attribute, the class's default eps).  The one table: warp_consistency's ``form`` and
+# TrainingStep's ``consistency_loss`` (train_step.consistency_loss_spec) read it.
+CONSISTENCY_FORMS = collections.OrderedDict((
+    ("distance", (0, NormalizedDistanceLoss, "eps", 1.0e-5)),
+    ("l2", (1, NormalizedL2Loss, "eps", 1.0e-3)),
+    ("l1", (2, NormalizedL1Loss, "eps", 1.0e-3)),
+    ("weighted_l2", (3, NormalizedWeightedMaskedL2Loss, "epsilon", 1.0)),
+))
 
 
 def depth_metrics(scaled_depth_maps, sparse_depth_maps, sparse_depth_masks, eps=1.0e-8):
@@ -459,8 +470,21 @@ class Threshold(nn.Module):
         return [out[:, 1].contiguous(), out[:, 2].contiguous(), out[:, 3].contiguous()]
 
 
+def _consistency_form(form, form_eps):
+    """warp_consistency's ``form`` / ``form_eps`` -> (ENDO_CONSISTENCY_* code, eps), or ValueError."""
+    if form not in CONSISTENCY_FORMS:
+        raise ValueError("form is one of %s, not %r" % (", ".join(repr(k) for k in CONSISTENCY_FORMS), form))
+    code, _, _, default_eps = CONSISTENCY_FORMS[form]
+    form_eps = default_eps if form_eps is None else float(form_eps)
+    if not (0.0 < form_eps < float("inf")):
+        raise ValueError("form_eps must be finite and positive (got %r)" % (form_eps,))
+    if form == "distance" and form_eps != default_eps:
+        raise ValueError("the fused distance form holds NormalizedDistanceLoss's default eps %g" % default_eps)
+    return code, form_eps
+
+
 def warp_consistency(depth_maps_1, depth_maps_2, img_masks, translations_1_wrt_2, rotations_1_wrt_2, translations_2_wrt_1,
-                     rotations_2_wrt_1, intrinsic_matrices, dcl_weight=1.0, epsilon=1.0e-8):
+                     rotations_2_wrt_1, intrinsic_matrices, dcl_weight=1.0, epsilon=1.0e-8, form="distance", form_eps=None):
     """Depth warping both ways + NormalizedDistanceLoss both ways, forward and backward, as one library call
     (``endo_warp_consistency``; reference models.py:454-554 and losses.py:112-146 twice each, train.py:305-314, and the autograd
     backward of that chain):
@@ -469,7 +493,14 @@ def warp_consistency(depth_maps_1, depth_maps_2, img_masks, translations_1_wrt_2
 
     Returns ``(loss, d loss / d depth_maps_1, d loss / d depth_maps_2)``.  The same kernels and arithmetic as
     ``DepthWarpingLayer`` + ``NormalizedDistanceLoss`` under autograd (tests/test_gpu_parity.py::test_warp_consistency_call),
-    without the ~10 autograd nodes around them -- the chain BASELINE.json's second metric times."""
+    without the ~10 autograd nodes around them -- the chain BASELINE.json's second metric times.
+
+    ``form``: the loss in NormalizedDistanceLoss's place -- "distance", "l2" (NormalizedL2Loss), "l1" (NormalizedL1Loss) or "weighted_l2"
+    (NormalizedWeightedMaskedL2Loss, each direction's term weighted by that direction's translations); ``form_eps``: its eps, default
+    the class's own (``CONSISTENCY_FORMS``).  The default runs ``endo_warp_consistency``, anything else ``endo_warp_consistency_forms``."""
+    default = form == "distance" and form_eps is None          # the call as it always was: nothing to look up or check
+    if not default:
+        code, form_eps = _consistency_form(form, form_eps)
     lib = _lib.load()
     d1 = _lib.dev_f32(depth_maps_1, "depth maps 1")
     d2 = _lib.dev_f32(depth_maps_2, "depth maps 2")
@@ -486,7 +517,13 @@ def warp_consistency(depth_maps_1, depth_maps_2, img_masks, translations_1_wrt_2
         ws = _consistency_ws[key] = torch.empty(need, dtype=torch.float32, device=d1.device)
     loss = torch.empty((), dtype=torch.float32, device=d1.device)
     g1, g2 = torch.empty_like(d1), torch.empty_like(d2)
-    _lib.check(lib.endo_warp_consistency(_lib.ptr(d1), _lib.ptr(d2), _lib.ptr(mask), _lib.ptr(t12), _lib.ptr(r12), _lib.ptr(t21),
-                                         _lib.ptr(r21), _lib.ptr(k), float(dcl_weight), float(epsilon), _lib.ptr(loss), _lib.ptr(g1),
-                                         _lib.ptr(g2), _lib.ptr(ws), n, h, w, _lib.stream()), "endo_warp_consistency")
+    if default or code == 0:
+        _lib.check(lib.endo_warp_consistency(_lib.ptr(d1), _lib.ptr(d2), _lib.ptr(mask), _lib.ptr(t12), _lib.ptr(r12), _lib.ptr(t21),
+                                             _lib.ptr(r21), _lib.ptr(k), float(dcl_weight), float(epsilon), _lib.ptr(loss), _lib.ptr(g1),
+                                             _lib.ptr(g2), _lib.ptr(ws), n, h, w, _lib.stream()), "endo_warp_consistency")
+    else:
+        _lib.check(lib.endo_warp_consistency_forms(_lib.ptr(d1), _lib.ptr(d2), _lib.ptr(mask), _lib.ptr(t12), _lib.ptr(r12), _lib.ptr(t21),
+                                                   _lib.ptr(r21), _lib.ptr(k), float(dcl_weight), float(epsilon), _lib.ptr(loss),
+                                                   _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(ws), n, h, w, code, form_eps, _lib.stream()),
+                   "endo_warp_consistency_forms")
     return loss, g1, g2

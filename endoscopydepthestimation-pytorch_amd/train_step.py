@@ -49,10 +49,44 @@ def mask_mul(a, mask):
     return _MaskMulFn.apply(a, mask)
 
 
+def consistency_loss_spec(consistency_loss, height, width):
+    """``TrainingStep``'s ``consistency_loss`` argument -> (name, module, eps): a name of ``losses.CONSISTENCY_FORMS`` stands for that class
+    with its default eps; an instance of one of the four classes is used as it is and supplies its own eps.  Anything else, an eps that
+    is not finite and positive, or a NormalizedDistanceLoss built for another size is a ValueError."""
+    forms = losses.CONSISTENCY_FORMS
+    module = None
+    if isinstance(consistency_loss, str):
+        if consistency_loss in forms:
+            name, cls = consistency_loss, forms[consistency_loss][1]
+            module = cls(height=height, width=width) if name == "distance" else cls()
+    else:
+        for name, (_, cls, _, _) in forms.items():
+            if isinstance(consistency_loss, cls):
+                module = consistency_loss
+                break
+    if module is None:
+        raise ValueError("consistency_loss is one of %s or an instance of losses.%s, not %r" % (
+            ", ".join(repr(k) for k in forms), " / ".join(v[1].__name__ for v in forms.values()), consistency_loss))
+    eps = float(getattr(module, forms[name][2]))
+    if not (0.0 < eps < float("inf")):
+        raise ValueError("consistency_loss: the eps of %s must be finite and positive (got %r)" % (type(module).__name__, eps))
+    if name == "distance" and (module.height, module.width) != (int(height), int(width)):
+        raise ValueError("consistency_loss: this NormalizedDistanceLoss was built for %dx%d, the step for %dx%d" % (
+            module.height, module.width, height, width))
+    return name, module, eps
+
+
 class TrainingStep(object):
     def __init__(self, model, optimizer, height, width, sfl_weight=20.0, dcl_weight=0.1, epsilon=1.0e-8, pair_forward=True,
-                 fused_head=True, bf16_storage=False, fp16_storage=False, photometric_weight=0.0, photometric_padding="zeros"):
+                 fused_head=True, bf16_storage=False, fp16_storage=False, photometric_weight=0.0, photometric_padding="zeros",
+                 consistency_loss="distance"):
         self.model = model
+        # the depth-consistency term's loss: "distance" (NormalizedDistanceLoss, the reference's train.py:211), "l2", "l1" or
+        # "weighted_l2" (the reference's other three, losses.py:94-109, 149-164, 35-54; the weighted form takes each direction's
+        # translations, as utils.py:1700-1703 hands them over), or an instance of one of the four, which supplies its own eps.  The
+        # default issues the calls the step always has; another one goes through endo_loss_head_forms, under every storage mode
+        self.consistency_loss, self.depth_consistency_loss_function, self.consistency_eps = consistency_loss_spec(
+            consistency_loss, height, width)
         # photometric_weight > 0 adds  w * 0.5 * (P(frame 1 against frame 2) + P(frame 2 against frame 1))  of losses.PhotometricLoss on
         # the masked colours, each frame's scaled depth and the depth warp's intersect masks to the total (not in the reference's train.py);
         # 0 is the step without it: the same calls as before the term existed
@@ -76,6 +110,9 @@ class TrainingStep(object):
         # everything between the network outputs and d loss / d prediction as one library call (endo_loss_head: the modules'
         # kernels, composed in C) instead of ~60 autograd nodes; needs the grouped pair forward
         self.fused_head = bool(fused_head) and bool(pair_forward) and hasattr(model, "forward_pair_packed")
+        if self.fused_head and self.consistency_loss == "distance" and self.consistency_eps != losses.CONSISTENCY_FORMS["distance"][3]:
+            raise ValueError("consistency_loss: the fused loss head's distance form holds NormalizedDistanceLoss's default eps %g; "
+                             "eps = %g needs fused_head=False" % (losses.CONSISTENCY_FORMS["distance"][3], self.consistency_eps))
         self._head_ws = None
         # both frames of the pair through the network as one grouped batch (FCDenseNet.forward_pair): same values as the
         # reference's two calls (train.py:276-277), half the kernel launches
@@ -87,7 +124,6 @@ class TrainingStep(object):
         self.depth_warping_layer = models.DepthWarpingLayer(epsilon=epsilon)
         self.flow_from_depth_layer = models.FlowfromDepthLayer()
         self.sparse_flow_loss_function = losses.SparseMaskedL1Loss()
-        self.depth_consistency_loss_function = losses.NormalizedDistanceLoss(height=height, width=width)
         self.bucket = distributed.GradientBucket(model.flat_gradients, getattr(model, "flat_gradient_bucket", None))
         # persistent replicas must start from the same state (nn.DataParallel re-broadcasts on every forward, train.py:197)
         distributed.sync_parameters(model, optimizer)
@@ -123,8 +159,8 @@ class TrainingStep(object):
         warped_12, inter_2 = self.depth_warping_layer([scaled_2, scaled_1, b, batch["translations_2_wrt_1"],
                                                        batch["rotations_2_wrt_1"], batch["intrinsics"]])
         dcl = self.dcl_weight * 0.5 * (
-            self.depth_consistency_loss_function([scaled_1, warped_21, inter_1, batch["intrinsics"]]) +
-            self.depth_consistency_loss_function([scaled_2, warped_12, inter_2, batch["intrinsics"]]))
+            self.depth_consistency_loss_function(self._consistency_inputs(scaled_1, warped_21, inter_1, batch, "translations_1_wrt_2")) +
+            self.depth_consistency_loss_function(self._consistency_inputs(scaled_2, warped_12, inter_2, batch, "translations_2_wrt_1")))
         extras = {"pred_1": pred_1, "pred_2": pred_2, "scaled_1": scaled_1, "scaled_2": scaled_2,
                   "warped_21": warped_21, "warped_12": warped_12, "inter_1": inter_1, "inter_2": inter_2,
                   "std_1": std_1, "std_2": std_2}
@@ -137,6 +173,31 @@ class TrainingStep(object):
             extras["photo"] = photo
             return dcl + sfl + photo, dcl, sfl, extras
         return dcl + sfl, dcl, sfl, extras
+
+    def _consistency_inputs(self, scaled, warped, inter, batch, translations):
+        """The list argument of the chosen consistency class: the intrinsics fourth for the distance loss, the direction's translations
+        fourth for the weighted one, three entries for the other two."""
+        if self.consistency_loss == "distance":
+            return [scaled, warped, inter, batch["intrinsics"]]
+        if self.consistency_loss == "weighted_l2":
+            return [scaled, warped, inter, batch[translations]]
+        return [scaled, warped, inter]
+
+    def _loss_head(self, lib, tensors, colors, outputs):
+        """The loss head call of this step's settings: endo_loss_head / endo_loss_head_photo with the default consistency loss,
+        endo_loss_head_forms with another one (``colors``: the two colour pointers, read with photometric_weight > 0 only)."""
+        photo = self.photometric_weight > 0.0
+        if self.consistency_loss != "distance":
+            _lib.check(lib.endo_loss_head_forms(
+                *tensors, *(colors if photo else (None, None)), self.sfl_weight, self.dcl_weight, self.photometric_weight, self.epsilon,
+                models.PADDING_MODES[self.photometric_padding], *outputs[:-1], losses.CONSISTENCY_FORMS[self.consistency_loss][0],
+                self.consistency_eps, outputs[-1]), "endo_loss_head_forms")
+        elif photo:          # the masked network inputs are the term's colours (the head is fp32 under every storage mode)
+            _lib.check(lib.endo_loss_head_photo(
+                *tensors, *colors, self.sfl_weight, self.dcl_weight, self.photometric_weight, self.epsilon,
+                models.PADDING_MODES[self.photometric_padding], *outputs), "endo_loss_head_photo")
+        else:
+            _lib.check(lib.endo_loss_head(*tensors, self.sfl_weight, self.dcl_weight, self.epsilon, *outputs), "endo_loss_head")
 
     def _fused_iteration(self, batch):
         """Network forward -> endo_loss_head (loss values and d loss / d prediction).  Everything is issued straight through the
@@ -172,12 +233,7 @@ class TrainingStep(object):
                 f("sparse_flow_masks_1"), f("sparse_flow_masks_2"), pose("translations_1_wrt_2", 3), pose("rotations_1_wrt_2", 9),
                 pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9)]
             outputs = [_lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]), _lib.ptr(self._head_ws), n, h, w, _lib.stream()]
-            if photo:          # the masked network inputs are the term's colours (the head is fp32 under every storage mode)
-                _lib.check(lib.endo_loss_head_photo(
-                    *tensors, _lib.ptr(x[:n]), _lib.ptr(x[n:]), self.sfl_weight, self.dcl_weight, self.photometric_weight, self.epsilon,
-                    models.PADDING_MODES[self.photometric_padding], *outputs), "endo_loss_head_photo")
-            else:
-                _lib.check(lib.endo_loss_head(*tensors, self.sfl_weight, self.dcl_weight, self.epsilon, *outputs), "endo_loss_head")
+            self._loss_head(lib, tensors, (_lib.ptr(x[:n]), _lib.ptr(x[n:])), outputs)
         self._display_source = (x, b)          # what display_panels() renders with the head workspace's planes
         return losses_t, x, tape, pred, grad_pred
 
@@ -295,7 +351,8 @@ class DistillationStep(TrainingStep):
     leaves its parameters, BatchNorm buffers and ``num_batches_tracked`` bit for bit and creates no gradient buffer.  fp32 only.
     The ``StepOutput`` has "loss", "dcl", "sfl" (0 in pure mode), "distill", "grad_norm" and "skipped"."""
 
-    def __init__(self, student, teacher, optimizer, height, width, distill_weight=1.0, sfl_weight=0.0, dcl_weight=0.0, epsilon=1.0e-8):
+    def __init__(self, student, teacher, optimizer, height, width, distill_weight=1.0, sfl_weight=0.0, dcl_weight=0.0, epsilon=1.0e-8,
+                 consistency_loss="distance"):
         if teacher is student:
             raise ValueError("DistillationStep: teacher and student are the same module")
         for name, value in (("distill_weight", distill_weight), ("sfl_weight", sfl_weight), ("dcl_weight", dcl_weight)):
@@ -307,7 +364,8 @@ class DistillationStep(TrainingStep):
         if student.flat_parameters().device != teacher.flat_parameters().device:
             raise ValueError("DistillationStep: student on %s, teacher on %s" % (student.flat_parameters().device,
                                                                                    teacher.flat_parameters().device))
-        TrainingStep.__init__(self, student, optimizer, height, width, sfl_weight=sfl_weight, dcl_weight=dcl_weight, epsilon=epsilon)
+        TrainingStep.__init__(self, student, optimizer, height, width, sfl_weight=sfl_weight, dcl_weight=dcl_weight, epsilon=epsilon,
+                              consistency_loss=consistency_loss)          # combined mode's loss head; pure mode has no consistency term
         self.teacher = teacher
         self.distill_weight = float(distill_weight)
         self.combined = self.sfl_weight > 0.0 or self.dcl_weight > 0.0
@@ -339,13 +397,13 @@ class DistillationStep(TrainingStep):
                     self._head_ws = torch.empty(need, dtype=torch.float32, device=pred.device)
                 f = lambda key: _lib.ptr(_lib.dev_f32(batch[key], key))
                 pose = lambda key, cols: _lib.ptr(_lib.dev_f32(batch[key], key).reshape(n, cols))
-                _lib.check(lib.endo_loss_head(
+                tensors = [
                     _lib.ptr(pred[:n]), _lib.ptr(pred[n:]), _lib.ptr(b), f("sparse_depths_1"), f("sparse_depths_2"),
                     f("sparse_depth_masks_1"), f("sparse_depth_masks_2"), f("sparse_flows_1"), f("sparse_flows_2"),
                     f("sparse_flow_masks_1"), f("sparse_flow_masks_2"), pose("translations_1_wrt_2", 3), pose("rotations_1_wrt_2", 9),
-                    pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9), self.sfl_weight, self.dcl_weight,
-                    self.epsilon, _lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]), _lib.ptr(self._head_ws), n, h, w,
-                    _lib.stream()), "endo_loss_head")
+                    pose("translations_2_wrt_1", 3), pose("rotations_2_wrt_1", 9), pose("intrinsics", 9)]
+                self._loss_head(lib, tensors, (None, None), [_lib.ptr(losses_t), _lib.ptr(grad_pred[:n]), _lib.ptr(grad_pred[n:]),
+                                                             _lib.ptr(self._head_ws), n, h, w, _lib.stream()])
             _distill_head(pred, goal, b, self.distill_weight, self.epsilon, self.combined, losses_t, grad_pred)
         if self.combined:
             self._display_source = (x, b)

@@ -73,7 +73,7 @@ extern "C" {
  * endo_weighted_l2_*, endo_masked_scale_inv_* and endo_sparse_l1_display_* (_fwd / _bwd each); then endo_warp_coordinates_* and
  * endo_image_warp_* (_fwd / _bwd each); then endo_photometric_workspace_floats, endo_photometric_fwd / _bwd,
  * endo_loss_head_photo_workspace_floats and endo_loss_head_photo; then endo_distill_head; then endo_evaluate_posed and
- * endo_evaluate_posed_workspace_bytes. */
+ * endo_evaluate_posed_workspace_bytes; then endo_warp_consistency_forms and endo_loss_head_forms. */
 #define ENDO_ABI_VERSION 7
 int endo_abi_version(void);
 /* hipGetErrorString for positive codes, a fixed string for ENDO_E_* */
@@ -349,6 +349,50 @@ int endo_warp_consistency(const float* depth_1, const float* depth_2, const floa
                           const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
                           float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
                           float* workspace, int n, int h, int w, void* stream);
+
+/* The depth-consistency loss of the two calls below: which of the reference's four losses compares a depth map (a), the other frame's
+ * warped into it (b) and the intersect mask (m).  Each is the arithmetic of its module's entry points above, inside the fused kernels:
+ *   ENDO_CONSISTENCY_DISTANCE     NormalizedDistanceLoss          -- reference losses.py:112-146 (endo_norm_dist_*; its eps is the class
+ *                                 default 1e-5 and form_eps is checked, then unused)
+ *   ENDO_CONSISTENCY_L2           NormalizedL2Loss                -- reference losses.py:94-109  (endo_norm_l2_*), class default eps 1e-3
+ *   ENDO_CONSISTENCY_L1           NormalizedL1Loss                -- reference losses.py:149-164 (endo_norm_l1_*), class default eps 1e-3
+ *   ENDO_CONSISTENCY_WEIGHTED_L2  NormalizedWeightedMaskedL2Loss  -- reference losses.py:35-54   (endo_weighted_l2_*), class default eps 1;
+ *                                 each direction's term is weighted over the batch by 1 / (1e-8 + |t_n|) of THAT direction's
+ *                                 translations (t_1_wrt_2 for frame 1's term), as the reference's student training hands them over
+ *                                 (utils.py:1700-1703)
+ * A sample whose intersect mask is empty gives NaN under L2 and L1 (0 / 0, as the reference) and 0 under WEIGHTED_L2. */
+#define ENDO_CONSISTENCY_DISTANCE 0
+#define ENDO_CONSISTENCY_L2 1
+#define ENDO_CONSISTENCY_L1 2
+#define ENDO_CONSISTENCY_WEIGHTED_L2 3
+
+/* endo_warp_consistency with the loss chosen -- reference models.py:454-554 once per direction, the loss class above once per direction,
+ * train.py:305-314 with that class in NormalizedDistanceLoss's place, and their backward.  Arguments, workspace
+ * (endo_warp_consistency_workspace_floats) and contract are endo_warp_consistency's; form = ENDO_CONSISTENCY_DISTANCE runs exactly that
+ * call.  The other forms cost one launch more (the one-wave finalize that leaves the backward kernel's per-sample coefficients).
+ * ENDO_E_BADARG also for an unknown form and a form_eps that is not finite and positive.  Additive: the version stays 7. */
+int endo_warp_consistency_forms(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,
+                                const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1, const float* intrinsics,
+                                float dcl_weight, float eps, float* loss, float* grad_depth_1, float* grad_depth_2,
+                                float* workspace, int n, int h, int w, int form, float form_eps, void* stream);
+
+/* endo_loss_head / endo_loss_head_photo with the depth-consistency loss chosen -- reference train.py:279-315 with the class above in
+ * NormalizedDistanceLoss's place (train.py:211, 305-314), and its backward.  Arguments as endo_loss_head_photo, then form and form_eps.
+ * photo_weight > 0: endo_loss_head_photo's launches, FIVE losses, endo_loss_head_photo_workspace_floats.  photo_weight == 0: the
+ * photometric term is not evaluated -- endo_loss_head's launches, FOUR losses, endo_loss_head_workspace_floats, and colors_* and
+ * padding_mode are not read (the colours may be null).  endo_loss_head_planes' offsets hold in both.  form =
+ * ENDO_CONSISTENCY_DISTANCE runs exactly endo_loss_head's / endo_loss_head_photo's kernels.  ENDO_E_BADARG also for an unknown form
+ * and a form_eps that is not finite and positive.  Additive: the version stays 7. */
+int endo_loss_head_forms(const float* pred_1, const float* pred_2, const float* boundaries,
+                         const float* sparse_depths_1, const float* sparse_depths_2,
+                         const float* sparse_depth_masks_1, const float* sparse_depth_masks_2,
+                         const float* sparse_flows_1, const float* sparse_flows_2,
+                         const float* sparse_flow_masks_1, const float* sparse_flow_masks_2,
+                         const float* t_1_wrt_2, const float* r_1_wrt_2, const float* t_2_wrt_1, const float* r_2_wrt_1,
+                         const float* intrinsics, const float* colors_1, const float* colors_2,
+                         float sfl_weight, float dcl_weight, float photo_weight, float eps, int padding_mode,
+                         float* losses, float* grad_pred_1, float* grad_pred_2, float* workspace,
+                         int n, int h, int w, int form, float form_eps, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------
