@@ -389,8 +389,6 @@ __global__ void __launch_bounds__(256) aug_noise_kernel(const uint8_t* __restric
     }
 }
 
-static int64_t aug_align(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
-
 struct AugLayout {
     int64_t params, a, b, planes, total;
 };
@@ -399,9 +397,9 @@ static AugLayout aug_layout(int frames, int height, int width) {
     AugLayout l;
     const int64_t img = static_cast<int64_t>(frames) * height * width * 3;
     l.params = 0;
-    l.a = aug_align(static_cast<int64_t>(frames) * sizeof(endo_augment_frame));
-    l.b = l.a + aug_align(img);
-    l.planes = l.b + aug_align(img);
+    l.a = align256(static_cast<int64_t>(frames) * sizeof(endo_augment_frame));
+    l.b = l.a + align256(img);
+    l.planes = l.b + align256(img);
     l.total = l.planes + frames * aug_jpeg_geom(height, width).frame_bytes;
     return l;
 }

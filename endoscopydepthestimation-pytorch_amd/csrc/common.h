@@ -22,6 +22,14 @@ namespace endo {
 
 constexpr int kWave = 64;
 
+// workspace sections start on 256-byte boundaries
+inline int64_t align256(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
+
+// a batch of frames a (row, frame) grid can index (blockIdx.y < 65536) and whose pixels a 32-bit number counts
+inline bool frames_sizes_ok(int frames, int height, int width) {
+    return frames > 0 && frames <= 65535 && height > 0 && width > 0 && static_cast<int64_t>(frames) * height * width <= INT32_MAX;
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);

@@ -42,7 +42,7 @@ static inline DisplayGeom display_geom(int n, int h, int w) {
 
 // N, H, W in range and a panel of `sections` stacked grids addressable with 32-bit rows and byte columns
 static inline bool display_sizes_in_range(int n, int h, int w, int sections) {
-    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || static_cast<int64_t>(n) * h * w > INT32_MAX) return false;
+    if (!frames_sizes_ok(n, h, w)) return false;
     const int64_t xmaps = n < kDispNrow ? n : kDispNrow, ymaps = (n + xmaps - 1) / xmaps;
     const int64_t gh = (static_cast<int64_t>(h) + kDispPad) * ymaps + kDispPad, gw = (static_cast<int64_t>(w) + kDispPad) * xmaps + kDispPad;
     return sections * gh <= INT32_MAX && 3 * gw <= INT32_MAX;

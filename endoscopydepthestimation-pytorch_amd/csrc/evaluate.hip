@@ -7,10 +7,11 @@
 //   scan   one block: exclusive prefix of the N * H row counts (frame-major, so each frame's points follow the previous frame's) and
 //          each frame's maximum of d from its row maxima
 //   write  one block per (frame, row): each pixel's colour display formed once, written to the panel and, when kept, to the point
-//          cloud at the row's offset, ordered inside the row by a wave-ballot prefix (as endo_point_cloud)
+//          cloud at the row's offset, ordered inside the row by cloud_device.h's chunk rank
 // numpy's float32 arithmetic rounds every operation on its own: contraction is off and the roundings are explicit.
 #include <cmath>
 
+#include "cloud_device.h"
 #include "common.h"
 #include "hsv_device.h"
 #include "jet_device.h"
@@ -32,71 +33,34 @@ struct EvalParams {
     float* frame_max;             // [N] workspace
 };
 
-__device__ __forceinline__ bool eval_keep(const EvalParams& q, int h, int w, float bnd) {
-    return h % q.downsampling == 0 && w % q.downsampling == 0 && bnd > 0.5f;          // utils.py:836 (no thresholds: evaluate.py:340)
-}
-
-__global__ void __launch_bounds__(256) eval_rows_kernel(const EvalParams q) {
-    __shared__ int s_cnt[4];
+__global__ void __launch_bounds__(kCloudThreads) eval_rows_kernel(const EvalParams q) {
     __shared__ float s_max[4];
     const int h = blockIdx.x, f = blockIdx.y;
     const int64_t row = static_cast<int64_t>(f) * q.height + h;
     const int64_t base = row * q.width;
     int cnt = 0;
     float mx = -INFINITY;
-    for (int w = threadIdx.x; w < q.width; w += 256) {
+    for (int w = threadIdx.x; w < q.width; w += kCloudThreads) {
         const float bnd = q.boundaries[base + w];
         const float d = __fmul_rn(bnd, q.pred[base + w]);          // (boundaries * predicted_depth_maps_1), evaluate.py:338
         q.depth[base + w] = d;
         mx = fmaxf(mx, d);
-        cnt += eval_keep(q, h, w, bnd) ? 1 : 0;
+        cnt += cloud_wave_count(cloud_pixel_keep(q.downsampling, h, w, bnd));          // (no thresholds: evaluate.py:340)
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off, 64);
-        mx = fmaxf(mx, __shfl_down(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_max[threadIdx.x >> 6] = mx; }
-    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    cnt = cloud_block_count(cnt);          // (its barrier publishes s_max too)
     if (threadIdx.x == 0) {
-        q.row_offsets[row] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        q.row_offsets[row] = cnt;
         q.row_max[row] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
     }
 }
 
-constexpr int kScanThreads = 1024;
-
-// one block: thread t owns the rows [t * chunk, (t + 1) * chunk); the block scans the per-thread sums, then each thread rewrites its rows
+// the rows' offsets and the frames' (cloud_scan_block), then each frame's maximum
 __global__ void __launch_bounds__(kScanThreads) eval_scan_kernel(const EvalParams q) {
-    __shared__ int64_t s_wave[kScanThreads / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t rows = static_cast<int64_t>(q.frames) * q.height;
-    const int64_t chunk = (rows + kScanThreads - 1) / kScanThreads;
-    const int64_t r0 = min(rows, t * chunk), r1 = min(rows, r0 + chunk);
-    int64_t sum = 0;
-    for (int64_t r = r0; r < r1; ++r) sum += q.row_offsets[r];
-    int64_t incl = sum;          // inclusive prefix inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t acc = incl - sum;
-    for (int i = 0; i < wave; ++i) acc += s_wave[i];
-    for (int64_t r = r0; r < r1; ++r) {
-        const int64_t c = q.row_offsets[r];
-        q.row_offsets[r] = acc;
-        acc += c;
-    }
-    if (t == kScanThreads - 1) {
-        int64_t total = 0;
-        for (int i = 0; i < kScanThreads / 64; ++i) total += s_wave[i];
-        q.frame_offsets[q.frames] = total;
-    }
-    __syncthreads();          // every row offset is written before the frame offsets read them
-    for (int f = t; f < q.frames; f += kScanThreads) q.frame_offsets[f] = q.row_offsets[static_cast<int64_t>(f) * q.height];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cloud_scan_block(q.row_offsets, q.frames, q.height, q.frame_offsets);
     // np.max(depth_map) of each frame: one wave per frame over its row maxima
     for (int f = wave; f < q.frames; f += kScanThreads / 64) {
         float mx = -INFINITY;
@@ -107,27 +71,18 @@ __global__ void __launch_bounds__(kScanThreads) eval_scan_kernel(const EvalParam
     }
 }
 
-// np.uint8(255 * (0.5 * c + 0.5)), evaluate.py:329-330: three roundings, then truncation (c in [-1, 1] keeps it in [0, 255])
-__device__ __forceinline__ int display_u8(float c) {
-    const float v = __fmul_rn(255.0f, __fadd_rn(__fmul_rn(0.5f, c), 0.5f));
-    return v > 0.0f ? min(static_cast<int>(v), 255) : 0;
-}
-
 // np.uint8(b * x) of a float32 b in [0, 1] and a uint8 x (evaluate.py:336-337)
 __device__ __forceinline__ int masked_u8(float b, int x) {
     const float v = __fmul_rn(b, static_cast<float>(x));
     return v > 0.0f ? min(static_cast<int>(v), 255) : 0;
 }
 
-__global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
+__global__ void __launch_bounds__(kCloudThreads) eval_write_kernel(const EvalParams q) {
     __shared__ uint8_t s_jet[256][3];          // B G R
-    __shared__ int s_wave[4];
-    __shared__ int64_t s_base;
     const int h = blockIdx.x, f = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     jet_fill(s_jet, threadIdx.x);          // COLORMAP_JET (jet_device.h)
-    if (threadIdx.x == 0) s_base = q.row_offsets[static_cast<int64_t>(f) * q.height + h];
     __syncthreads();
+    int64_t at = q.row_offsets[static_cast<int64_t>(f) * q.height + h];          // where this chunk's points start
     const float mx = q.frame_max[f];
     const float* kf = q.k + static_cast<int64_t>(f) * 9;
     const float fx = kf[0], cx = kf[2], fy = kf[4], cy = kf[5];
@@ -135,7 +90,7 @@ __global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
     const int64_t pix0 = (static_cast<int64_t>(f) * q.height + h) * q.width;
     const float* col = q.colors + static_cast<int64_t>(f) * 3 * plane + static_cast<int64_t>(h) * q.width;
     uint8_t* panel = q.panels + pix0 * 6;          // this row of the (H, 2W, 3) panel
-    for (int w0 = 0; w0 < q.width; w0 += 256) {
+    for (int w0 = 0; w0 < q.width; w0 += kCloudThreads) {
         const int w = w0 + threadIdx.x;
         bool keep = false;
         float bnd = 0.0f, d = 0.0f;
@@ -143,7 +98,7 @@ __global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
         if (w < q.width) {
             bnd = q.boundaries[pix0 + w];
             d = q.depth[pix0 + w];
-            keep = eval_keep(q, h, w, bnd);
+            keep = cloud_pixel_keep(q.downsampling, h, w, bnd);
             const int c0 = display_u8(col[w]), c1 = display_u8(col[plane + w]), c2 = display_u8(col[2 * plane + w]);
             if (q.is_hsv) {          // cv2.COLOR_HSV2BGR_FULL of (H, S, V) = (c0, c1, c2)
                 int rgb[3];
@@ -165,30 +120,20 @@ __global__ void __launch_bounds__(256) eval_write_kernel(const EvalParams q) {
             left[0] = static_cast<uint8_t>(bgr[0]); left[1] = static_cast<uint8_t>(bgr[1]); left[2] = static_cast<uint8_t>(bgr[2]);
             right[0] = s_jet[idx][0]; right[1] = s_jet[idx][1]; right[2] = s_jet[idx][2];
         }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int wave_off = 0;
-        for (int i = 0; i < wave; ++i) wave_off += s_wave[i];
-        const int chunk_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        int total;
+        const int rank = cloud_chunk_rank(keep, total);
         if (keep) {
-            // utils.py:838-840 with the reference's operation order, (w - cx) / fx * z: three roundings
-            const float x = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(w), cx), fx), d);
-            const float y = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(h), cy), fy), d);
-            float* dst = q.points + (s_base + wave_off + before) * 6;
+            float x, y;
+            cloud_back_project(w, h, fx, cx, fy, cy, d, x, y);
+            float* dst = q.points + (at + rank) * 6;
             dst[0] = x; dst[1] = y; dst[2] = d;
             dst[3] = static_cast<float>(bgr[2]);
             dst[4] = static_cast<float>(bgr[1]);
             dst[5] = static_cast<float>(bgr[0]);
         }
-        __syncthreads();
-        if (threadIdx.x == 0) s_base += chunk_total;
-        __syncthreads();
+        at += total;
     }
 }
-
-static int64_t eval_align(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
 
 struct EvalLayout {
     int64_t row_offsets, row_max, frame_max, total;
@@ -198,14 +143,10 @@ static EvalLayout eval_layout(int frames, int height) {
     const int64_t rows = static_cast<int64_t>(frames) * height;
     EvalLayout l;
     l.row_offsets = 0;
-    l.row_max = eval_align(rows * static_cast<int64_t>(sizeof(int64_t)));
-    l.frame_max = l.row_max + eval_align(rows * static_cast<int64_t>(sizeof(float)));
-    l.total = l.frame_max + eval_align(static_cast<int64_t>(frames) * sizeof(float));
+    l.row_max = align256(rows * static_cast<int64_t>(sizeof(int64_t)));
+    l.frame_max = l.row_max + align256(rows * static_cast<int64_t>(sizeof(float)));
+    l.total = l.frame_max + align256(static_cast<int64_t>(frames) * sizeof(float));
     return l;
-}
-
-static bool eval_sizes_ok(int frames, int height, int width) {
-    return frames > 0 && frames <= 65535 && height > 0 && width > 0 && static_cast<int64_t>(frames) * height * width <= INT32_MAX;
 }
 
 }  // namespace endo
@@ -213,7 +154,7 @@ static bool eval_sizes_ok(int frames, int height, int width) {
 using namespace endo;
 
 extern "C" int64_t endo_evaluate_workspace_bytes(int frames, int height, int width) {
-    if (!eval_sizes_ok(frames, height, width)) return -1;
+    if (!frames_sizes_ok(frames, height, width)) return -1;
     return eval_layout(frames, height).total;
 }
 
@@ -221,7 +162,7 @@ extern "C" int endo_evaluate(const float* colors, const float* boundaries, const
                              int height, int width, int is_hsv, int point_cloud_downsampling, float* depth, uint8_t* panels, float* points,
                              int64_t* frame_offsets, void* workspace, int64_t workspace_bytes, void* stream_) {
     if (!colors || !boundaries || !predictions || !intrinsics || !depth || !panels || !points || !frame_offsets || !workspace) return ENDO_E_BADARG;
-    if (!eval_sizes_ok(frames, height, width) || (is_hsv != 0 && is_hsv != 1) || point_cloud_downsampling <= 0) return ENDO_E_BADARG;
+    if (!frames_sizes_ok(frames, height, width) || (is_hsv != 0 && is_hsv != 1) || point_cloud_downsampling <= 0) return ENDO_E_BADARG;
     const EvalLayout l = eval_layout(frames, height);
     if (workspace_bytes < l.total) return ENDO_E_BADARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -231,11 +172,11 @@ extern "C" int endo_evaluate(const float* colors, const float* boundaries, const
                        reinterpret_cast<float*>(ws + l.frame_max)};
     const double pixels = static_cast<double>(frames) * height * width;
     ProfScope prof(kProfSmall, stream, 0.0, pixels * (4.0 * 5 + 4.0 + 6.0 + 24.0));
-    eval_rows_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    eval_rows_kernel<<<dim3(height, frames), kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     eval_scan_kernel<<<1, kScanThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
-    eval_write_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    eval_write_kernel<<<dim3(height, frames), kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     return 0;
 }

@@ -12,10 +12,11 @@
 //   scan   one block: exclusive prefix of the N * H row counts, frame-major; each frame's (z_min, z_max) over its kept pixels, (+inf, -inf)
 //          when there is none, and its whole-map (min, max)
 //   write  one block per (frame, row): colour image, depth image and, for written pixels, the transformed point at the row's offset,
-//          ordered inside the row by a wave-ballot prefix
+//          ordered inside the row by cloud_device.h's chunk rank
 // numpy rounds every float32 / float64 operation on its own: the file is compiled with -ffp-contract=off and the roundings are explicit.
 #include <cmath>
 
+#include "cloud_device.h"
 #include "common.h"
 #include "hsv_device.h"
 #include "jet_device.h"
@@ -42,19 +43,6 @@ struct PosedParams {
     float* frame_whole;           // [N][2] workspace: whole-map min, max
 };
 
-__device__ __forceinline__ bool posed_keep(const PosedParams& q, int h, int w, float bnd) {
-    return h % q.downsampling == 0 && w % q.downsampling == 0 && bnd > 0.5f;          // utils.py:1262
-}
-
-// np.uint8(255 * clip(c * 0.5 + 0.5, 0, 1)), utils.py:1331-1334: three roundings, then truncation
-__device__ __forceinline__ int posed_u8(float c) {
-    float v = __fadd_rn(__fmul_rn(c, 0.5f), 0.5f);
-    if (v < 0.0f) v = 0.0f;
-    if (v > 1.0f) v = 1.0f;
-    v = __fmul_rn(255.0f, v);
-    return v > 0.0f ? min(static_cast<int>(v), 255) : 0;          // (a NaN colour: 0)
-}
-
 // The colour image's three channels at pixel w of a row (utils.py:1331-1336).  RGB input: its channels as they are (the reference has no
 // RGB -> BGR swap here); HSV input: cv2.COLOR_HSV2BGR_FULL, so B, G, R.
 __device__ __forceinline__ void posed_color(const PosedParams& q, const float* col, int64_t plane, int w, int (&img)[3]) {
@@ -75,8 +63,7 @@ __device__ __forceinline__ bool posed_written(const PosedParams& q, const int (&
     return static_cast<float>(hi) >= q.max_threshold && static_cast<float>(lo) <= q.min_threshold;
 }
 
-__global__ void __launch_bounds__(256) posed_rows_kernel(const PosedParams q) {
-    __shared__ int s_cnt[4];
+__global__ void __launch_bounds__(kCloudThreads) posed_rows_kernel(const PosedParams q) {
     __shared__ float s_stat[4][4];
     const int h = blockIdx.x, f = blockIdx.y;
     const int64_t row = static_cast<int64_t>(f) * q.height + h;
@@ -85,27 +72,26 @@ __global__ void __launch_bounds__(256) posed_rows_kernel(const PosedParams q) {
     const float* col = q.colors + static_cast<int64_t>(f) * 3 * plane + static_cast<int64_t>(h) * q.width;
     int cnt = 0;
     float kmin = INFINITY, kmax = -INFINITY, amin = INFINITY, amax = -INFINITY;
-    for (int w = threadIdx.x; w < q.width; w += 256) {
+    for (int w = threadIdx.x; w < q.width; w += kCloudThreads) {
         const float bnd = q.boundaries[base + w];
         const float d = __fmul_rn(bnd, q.pred[base + w]);          // (boundaries * scaled_depth_maps_1), utils.py:1321
         q.depth[base + w] = d;
         amin = fminf(amin, d);
         amax = fmaxf(amax, d);
-        if (posed_keep(q, h, w, bnd)) {
+        bool written = cloud_pixel_keep(q.downsampling, h, w, bnd);          // utils.py:1262
+        if (written) {
             kmin = fminf(kmin, d);
             kmax = fmaxf(kmax, d);
             if (q.use_thresholds) {
                 int img[3];
                 posed_color(q, col, plane, w, img);
-                cnt += posed_written(q, img) ? 1 : 0;
-            } else {
-                cnt += 1;
+                written = posed_written(q, img);
             }
         }
+        cnt += cloud_wave_count(written);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off, 64);
         kmin = fminf(kmin, __shfl_down(kmin, off, 64));
         kmax = fmaxf(kmax, __shfl_down(kmax, off, 64));
         amin = fminf(amin, __shfl_down(amin, off, 64));
@@ -113,11 +99,10 @@ __global__ void __launch_bounds__(256) posed_rows_kernel(const PosedParams q) {
     }
     if ((threadIdx.x & 63) == 0) {
         const int wv = threadIdx.x >> 6;
-        s_cnt[wv] = cnt;
         s_stat[wv][0] = kmin; s_stat[wv][1] = kmax; s_stat[wv][2] = amin; s_stat[wv][3] = amax;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) q.row_offsets[row] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    cnt = cloud_block_count(cnt);          // (its barrier publishes s_stat too)
+    if (threadIdx.x == 0) q.row_offsets[row] = cnt;
     if (threadIdx.x < 4) {
         const int j = threadIdx.x;
         const float a = s_stat[0][j], b = s_stat[1][j], c = s_stat[2][j], e = s_stat[3][j];
@@ -125,41 +110,11 @@ __global__ void __launch_bounds__(256) posed_rows_kernel(const PosedParams q) {
     }
 }
 
-constexpr int kPosedScanThreads = 1024;
-
-// one block: thread t owns the rows [t * chunk, (t + 1) * chunk); the block scans the per-thread sums, then each thread rewrites its rows
-// (eval_scan_kernel); then one wave per frame reduces the frame's row statistics
-__global__ void __launch_bounds__(kPosedScanThreads) posed_scan_kernel(const PosedParams q) {
-    __shared__ int64_t s_wave[kPosedScanThreads / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t rows = static_cast<int64_t>(q.frames) * q.height;
-    const int64_t chunk = (rows + kPosedScanThreads - 1) / kPosedScanThreads;
-    const int64_t r0 = min(rows, t * chunk), r1 = min(rows, r0 + chunk);
-    int64_t sum = 0;
-    for (int64_t r = r0; r < r1; ++r) sum += q.row_offsets[r];
-    int64_t incl = sum;          // inclusive prefix inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t acc = incl - sum;
-    for (int i = 0; i < wave; ++i) acc += s_wave[i];
-    for (int64_t r = r0; r < r1; ++r) {
-        const int64_t c = q.row_offsets[r];
-        q.row_offsets[r] = acc;
-        acc += c;
-    }
-    if (t == kPosedScanThreads - 1) {
-        int64_t total = 0;
-        for (int i = 0; i < kPosedScanThreads / 64; ++i) total += s_wave[i];
-        q.frame_offsets[q.frames] = total;
-    }
-    __syncthreads();          // every row offset is written before the frame offsets read them
-    for (int f = t; f < q.frames; f += kPosedScanThreads) q.frame_offsets[f] = q.row_offsets[static_cast<int64_t>(f) * q.height];
-    for (int f = wave; f < q.frames; f += kPosedScanThreads / 64) {
+// the rows' offsets and the frames' (cloud_scan_block); then one wave per frame reduces the frame's row statistics
+__global__ void __launch_bounds__(kScanThreads) posed_scan_kernel(const PosedParams q) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cloud_scan_block(q.row_offsets, q.frames, q.height, q.frame_offsets);
+    for (int f = wave; f < q.frames; f += kScanThreads / 64) {
         float kmin = INFINITY, kmax = -INFINITY, amin = INFINITY, amax = -INFINITY;
         for (int h = lane; h < q.height; h += 64) {
             const float* s = q.row_stats + (static_cast<int64_t>(f) * q.height + h) * 4;
@@ -184,15 +139,12 @@ __global__ void __launch_bounds__(kPosedScanThreads) posed_scan_kernel(const Pos
     }
 }
 
-__global__ void __launch_bounds__(256) posed_write_kernel(const PosedParams q) {
+__global__ void __launch_bounds__(kCloudThreads) posed_write_kernel(const PosedParams q) {
     __shared__ uint8_t s_jet[256][3];          // B G R
-    __shared__ int s_wave[4];
-    __shared__ int64_t s_base;
     const int h = blockIdx.x, f = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     jet_fill(s_jet, threadIdx.x);          // COLORMAP_JET (jet_device.h)
-    if (threadIdx.x == 0) s_base = q.row_offsets[static_cast<int64_t>(f) * q.height + h];
     __syncthreads();
+    int64_t at = q.row_offsets[static_cast<int64_t>(f) * q.height + h];          // where this chunk's points start
     const float amin = q.frame_whole[2 * f], amax = q.frame_whole[2 * f + 1];
     const float span = __fsub_rn(amax, amin);
     // scale = 20.0 / (z_max - z_min), utils.py:1271: float32 under numpy 2's scalar promotion
@@ -204,7 +156,7 @@ __global__ void __launch_bounds__(256) posed_write_kernel(const PosedParams q) {
     const int64_t plane = static_cast<int64_t>(q.height) * q.width;
     const int64_t pix0 = (static_cast<int64_t>(f) * q.height + h) * q.width;
     const float* col = q.colors + static_cast<int64_t>(f) * 3 * plane + static_cast<int64_t>(h) * q.width;
-    for (int w0 = 0; w0 < q.width; w0 += 256) {
+    for (int w0 = 0; w0 < q.width; w0 += kCloudThreads) {
         const int w = w0 + threadIdx.x;
         bool write = false;
         float d = 0.0f;
@@ -213,7 +165,7 @@ __global__ void __launch_bounds__(256) posed_write_kernel(const PosedParams q) {
             const float bnd = q.boundaries[pix0 + w];
             d = q.depth[pix0 + w];
             posed_color(q, col, plane, w, img);
-            write = posed_keep(q, h, w, bnd) && posed_written(q, img);
+            write = cloud_pixel_keep(q.downsampling, h, w, bnd) && posed_written(q, img);
             uint8_t* ci = q.color_images + (pix0 + w) * 3;
             ci[0] = static_cast<uint8_t>(img[0]); ci[1] = static_cast<uint8_t>(img[1]); ci[2] = static_cast<uint8_t>(img[2]);
             // display_depth_map, utils.py:777-780: abs((d - min) / (max - min) * 255), above 255 -> 255, at or below 0 -> 0, truncated.
@@ -226,22 +178,17 @@ __global__ void __launch_bounds__(256) posed_write_kernel(const PosedParams q) {
             uint8_t* di = q.depth_images + (pix0 + w) * 3;
             di[0] = s_jet[idx][0]; di[1] = s_jet[idx][1]; di[2] = s_jet[idx][2];
         }
-        const unsigned long long bal = __ballot(write);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int wave_off = 0;
-        for (int i = 0; i < wave; ++i) wave_off += s_wave[i];
-        const int chunk_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        int total;
+        const int rank = cloud_chunk_rank(write, total);
         if (write) {
             // utils.py:1277-1280: (w - cx) / fx * z in float32, each coordinate times the float32 scale, then R p + t in float64:
             // ((R_i0 p_x + R_i1 p_y) + R_i2 p_z) + t_i, every product and sum rounded, the result rounded to float32 (utils.py:1293)
-            const float x = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(w), cx), fx), d);
-            const float y = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(h), cy), fy), d);
+            float x, y;
+            cloud_back_project(w, h, fx, cx, fy, cy, d, x, y);
             const double px = static_cast<double>(__fmul_rn(x, scale));
             const double py = static_cast<double>(__fmul_rn(y, scale));
             const double pz = static_cast<double>(__fmul_rn(d, scale));
-            float* dst = q.points + (s_base + wave_off + before) * 6;
+            float* dst = q.points + (at + rank) * 6;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const double s01 = __dadd_rn(__dmul_rn(rot[3 * i], px), __dmul_rn(rot[3 * i + 1], py));
@@ -252,13 +199,9 @@ __global__ void __launch_bounds__(256) posed_write_kernel(const PosedParams q) {
             dst[4] = static_cast<float>(img[1]);
             dst[5] = static_cast<float>(img[0]);
         }
-        __syncthreads();
-        if (threadIdx.x == 0) s_base += chunk_total;
-        __syncthreads();
+        at += total;
     }
 }
-
-static int64_t posed_align(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
 
 struct PosedLayout {
     int64_t row_offsets, row_stats, frame_whole, total;
@@ -268,14 +211,10 @@ static PosedLayout posed_layout(int frames, int height) {
     const int64_t rows = static_cast<int64_t>(frames) * height;
     PosedLayout l;
     l.row_offsets = 0;
-    l.row_stats = posed_align(rows * static_cast<int64_t>(sizeof(int64_t)));
-    l.frame_whole = l.row_stats + posed_align(rows * 4 * static_cast<int64_t>(sizeof(float)));
-    l.total = l.frame_whole + posed_align(static_cast<int64_t>(frames) * 2 * sizeof(float));
+    l.row_stats = align256(rows * static_cast<int64_t>(sizeof(int64_t)));
+    l.frame_whole = l.row_stats + align256(rows * 4 * static_cast<int64_t>(sizeof(float)));
+    l.total = l.frame_whole + align256(static_cast<int64_t>(frames) * 2 * sizeof(float));
     return l;
-}
-
-static bool posed_sizes_ok(int frames, int height, int width) {
-    return frames > 0 && frames <= 65535 && height > 0 && width > 0 && static_cast<int64_t>(frames) * height * width <= INT32_MAX;
 }
 
 }  // namespace endo
@@ -283,7 +222,7 @@ static bool posed_sizes_ok(int frames, int height, int width) {
 using namespace endo;
 
 extern "C" int64_t endo_evaluate_posed_workspace_bytes(int frames, int height, int width) {
-    if (!posed_sizes_ok(frames, height, width)) return -1;
+    if (!frames_sizes_ok(frames, height, width)) return -1;
     return posed_layout(frames, height).total;
 }
 
@@ -295,7 +234,7 @@ extern "C" int endo_evaluate_posed(const float* colors, const float* boundaries,
     if (!colors || !boundaries || !predictions || !intrinsics || !rotations || !translations || !depth || !color_images || !depth_images ||
         !points || !frame_offsets || !frame_ranges || !workspace)
         return ENDO_E_BADARG;
-    if (!posed_sizes_ok(frames, height, width) || (is_hsv != 0 && is_hsv != 1) || point_cloud_downsampling <= 0 ||
+    if (!frames_sizes_ok(frames, height, width) || (is_hsv != 0 && is_hsv != 1) || point_cloud_downsampling <= 0 ||
         (use_thresholds != 0 && use_thresholds != 1))
         return ENDO_E_BADARG;
     if (use_thresholds && (std::isnan(min_threshold) || std::isnan(max_threshold))) return ENDO_E_BADARG;
@@ -309,11 +248,11 @@ extern "C" int endo_evaluate_posed(const float* colors, const float* boundaries,
                         reinterpret_cast<float*>(ws + l.row_stats), reinterpret_cast<float*>(ws + l.frame_whole)};
     const double pixels = static_cast<double>(frames) * height * width;
     ProfScope prof(kProfSmall, stream, 0.0, pixels * (4.0 * 5 + 4.0 + 4.0 + 4.0 * 4 + 6.0 + 24.0));
-    posed_rows_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    posed_rows_kernel<<<dim3(height, frames), kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
-    posed_scan_kernel<<<1, kPosedScanThreads, 0, stream>>>(q);
+    posed_scan_kernel<<<1, kScanThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
-    posed_write_kernel<<<dim3(height, frames), 256, 0, stream>>>(q);
+    posed_write_kernel<<<dim3(height, frames), kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     return 0;
 }

@@ -14,7 +14,7 @@
 //   reduce  one block per (band of 8 rows, pair, half): the band's min and max of b * d, its maximum dense-flow magnitude and (half 0)
 //           its count of point-cloud pixels
 //   scan    one block: exclusive prefix of the N * bands point counts (pair-major), the pairs' offsets, each half's range and max_v
-//   write   one block per panel row, one per (band, pair) for the point rows, ordered inside a row by a wave-ballot prefix, and one per
+//   write   one block per panel row, one per (band, pair) for the point rows, ordered inside a row by cloud_device.h's rank, and one per
 //           (pair, half) that runs depth_metrics_block, the device function that is endo_depth_metrics' whole kernel, so the two
 //           entries return the same bits (three IEEE divisions per pixel make a sample one compute unit's arithmetic, about as long
 //           as the panel rows take beside it)
@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "cloud_device.h"
 #include "common.h"
 #include "display_device.h"
 #include "jet_device.h"
@@ -31,7 +32,7 @@ namespace endo {
 constexpr int kValSections = 12;
 constexpr int kValPartial = 4;          // floats per band partial: depth min, depth max, dense-flow max v, (unused)
 constexpr int kValFinal = 4;            // floats per pair half after the scan: depth min, depth max, norm_ip's divisor, max_v
-constexpr int kValScanThreads = 1024;
+static_assert(kDispThreads == kCloudThreads, "the reduce and write blocks use cloud_device.h's 256-thread helpers");
 
 // ---------------------------------------------------------------------------------------------
 // AbsRelError and Threshold of one sample -- losses.py:194-227 -- by one block of 256 threads.  Per-pixel terms with torch's float32
@@ -124,16 +125,6 @@ struct ValParams {
     float* finals;                   // workspace [2][kValFinal]
 };
 
-__device__ __forceinline__ bool val_keep(int downsampling, int h, int w, float bnd) {
-    return h % downsampling == 0 && w % downsampling == 0 && bnd > 0.5f;          // utils.py:837
-}
-
-// np.uint8(255 * (0.5 * c + 0.5)), evaluate.py:329-330: the point colours, taken as the test phase takes them
-__device__ __forceinline__ int cloud_u8(float c) {
-    const float v = __fmul_rn(255.0f, __fadd_rn(__fmul_rn(0.5f, c), 0.5f));
-    return v > 0.0f ? min(static_cast<int>(v), 255) : 0;
-}
-
 // trunc(clip(255 ((0.5 c + 0.5) b))): utils.py:912, then the writer's (and evaluate.py:270's) float-image conversion
 __device__ __forceinline__ int val_color_u8(float c, float b) {
     const float v = __fmul_rn(__fmul_rn(__fadd_rn(__fmul_rn(c, 0.5f), 0.5f), b), 255.0f);
@@ -163,7 +154,7 @@ __global__ void __launch_bounds__(kDispThreads) val_reduce_kernel(const ValParam
             lo = fminf(lo, d);
             hi = fmaxf(hi, d);
             vmax = max_keep_nan(vmax, flow_v(dx[base + w], flow_fy(dy[base + w], gh, gw)));
-            keep += val_keep(q.downsampling, r, w, b) ? 1 : 0;
+            keep += cloud_pixel_keep(q.downsampling, r, w, b) ? 1 : 0;
         }
     }
 #pragma unroll
@@ -192,44 +183,18 @@ __global__ void __launch_bounds__(kDispThreads) val_reduce_kernel(const ValParam
     }
 }
 
-// one block: thread t owns the bands [t * chunk, (t + 1) * chunk) of the pair-major list (as evaluate.hip's eval_scan_kernel)
-__global__ void __launch_bounds__(kValScanThreads) val_scan_kernel(const ValParams q) {
-    __shared__ int64_t s_wave[kValScanThreads / 64];
-    __shared__ float s_red[3][kValScanThreads / 64];
+// the bands' offsets and the pairs' (cloud_scan_block, on the pair-major list), then each half's range and max_v
+__global__ void __launch_bounds__(kScanThreads) val_scan_kernel(const ValParams q) {
+    __shared__ float s_red[3][kScanThreads / 64];
     const DisplayGeom g = q.g;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t items = static_cast<int64_t>(g.n) * g.bands;
-    const int64_t chunk = (items + kValScanThreads - 1) / kValScanThreads;
-    const int64_t i0 = min(items, t * chunk), i1 = min(items, i0 + chunk);
-    int64_t sum = 0;
-    for (int64_t i = i0; i < i1; ++i) sum += q.band_offsets[i];
-    int64_t incl = sum;          // inclusive prefix inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t acc = incl - sum;
-    for (int i = 0; i < wave; ++i) acc += s_wave[i];
-    for (int64_t i = i0; i < i1; ++i) {
-        const int64_t c = q.band_offsets[i];
-        q.band_offsets[i] = acc;
-        acc += c;
-    }
-    if (t == kValScanThreads - 1) {
-        int64_t total = 0;
-        for (int i = 0; i < kValScanThreads / 64; ++i) total += s_wave[i];
-        q.offsets[g.n] = total;
-    }
-    __syncthreads();          // every band offset is written before the pairs' offsets read them
-    for (int f = t; f < g.n; f += kValScanThreads) q.offsets[f] = q.band_offsets[static_cast<int64_t>(f) * g.bands];
+    cloud_scan_block(q.band_offsets, g.n, g.bands, q.offsets);
     // torch.min / torch.max of the half's b * d over the whole batch, and draw_flow(dense flows)'s np.max(v)
     for (int half = 0; half < 2; ++half) {
         const float* p = q.partials + static_cast<int64_t>(half) * items * kValPartial;
         float lo = INFINITY, hi = -INFINITY, vmax = 0.0f;
-        for (int64_t i = t; i < items; i += kValScanThreads) {
+        for (int64_t i = t; i < items; i += kScanThreads) {
             lo = fminf(lo, p[i * kValPartial]);
             hi = fmaxf(hi, p[i * kValPartial + 1]);
             vmax = max_keep_nan(vmax, p[i * kValPartial + 2]);
@@ -244,7 +209,7 @@ __global__ void __launch_bounds__(kValScanThreads) val_scan_kernel(const ValPara
         if (lane == 0) { s_red[0][wave] = lo; s_red[1][wave] = hi; s_red[2][wave] = vmax; }
         __syncthreads();
         if (t == 0) {
-            for (int i = 1; i < kValScanThreads / 64; ++i) {
+            for (int i = 1; i < kScanThreads / 64; ++i) {
                 lo = fminf(lo, s_red[0][i]);
                 hi = fmaxf(hi, s_red[1][i]);
                 vmax = max_keep_nan(vmax, s_red[2][i]);
@@ -258,14 +223,11 @@ __global__ void __launch_bounds__(kValScanThreads) val_scan_kernel(const ValPara
     }
 }
 
-// the point rows of one band of frame 1 of pair f, rows in order (as evaluate.hip's eval_write_kernel, on the unmasked scaled depth)
+// the point rows of one band of frame 1 of pair f, rows in order (cloud_device.h's pieces, on the unmasked scaled depth; the colours
+// are display_u8's, as the test phase takes them)
 __device__ void val_cloud_band(const ValParams& q, int f, int band) {
-    __shared__ int s_wave[kDispThreads / 64];
-    __shared__ int64_t s_base;
     const DisplayGeom g = q.g;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = q.band_offsets[static_cast<int64_t>(f) * g.bands + band];
-    __syncthreads();
+    int64_t at = q.band_offsets[static_cast<int64_t>(f) * g.bands + band];          // where this chunk's points start
     const float* kf = q.k + static_cast<int64_t>(f) * 9;
     const float fx = kf[0], cx = kf[2], fy = kf[4], cy = kf[5];
     const int64_t plane = static_cast<int64_t>(g.h) * g.w;
@@ -276,28 +238,20 @@ __device__ void val_cloud_band(const ValParams& q, int f, int band) {
         const float* col = q.colors[0] + static_cast<int64_t>(f) * 3 * plane + static_cast<int64_t>(h) * g.w;
         for (int w0 = 0; w0 < g.w; w0 += kDispThreads) {
             const int w = w0 + threadIdx.x;
-            const bool keep = w < g.w && val_keep(q.downsampling, h, w, q.boundaries[pix0 + w]);
-            const unsigned long long bal = __ballot(keep);
-            const int before = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) s_wave[wave] = __popcll(bal);
-            __syncthreads();
-            int wave_off = 0;
-            for (int i = 0; i < wave; ++i) wave_off += s_wave[i];
-            const int chunk_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+            const bool keep = w < g.w && cloud_pixel_keep(q.downsampling, h, w, q.boundaries[pix0 + w]);
+            int total;
+            const int rank = cloud_chunk_rank(keep, total);
             if (keep) {
-                // utils.py:838-840 with the reference's operation order, (w - cx) / fx * z: three roundings
                 const float d = q.depths[0][pix0 + w];
-                const float x = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(w), cx), fx), d);
-                const float y = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(h), cy), fy), d);
-                float* dst = q.points + (s_base + wave_off + before) * 6;
+                float x, y;
+                cloud_back_project(w, h, fx, cx, fy, cy, d, x, y);
+                float* dst = q.points + (at + rank) * 6;
                 dst[0] = x; dst[1] = y; dst[2] = d;
-                dst[3] = static_cast<float>(cloud_u8(col[w]));
-                dst[4] = static_cast<float>(cloud_u8(col[plane + w]));
-                dst[5] = static_cast<float>(cloud_u8(col[2 * plane + w]));
+                dst[3] = static_cast<float>(display_u8(col[w]));
+                dst[4] = static_cast<float>(display_u8(col[plane + w]));
+                dst[5] = static_cast<float>(display_u8(col[2 * plane + w]));
             }
-            __syncthreads();
-            if (threadIdx.x == 0) s_base += chunk_total;
-            __syncthreads();
+            at += total;
         }
     }
 }
@@ -377,8 +331,6 @@ __global__ void __launch_bounds__(kDispThreads) val_write_kernel(const ValParams
     }
 }
 
-static int64_t val_align(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
-
 struct ValLayout {
     int64_t partials, band_offsets, finals, total;
 };
@@ -387,15 +339,15 @@ static ValLayout val_layout(int n, int h) {
     const int64_t items = static_cast<int64_t>(n) * ((h + kDispBandRows - 1) / kDispBandRows);
     ValLayout l;
     l.partials = 0;
-    l.band_offsets = val_align(2 * items * kValPartial * static_cast<int64_t>(sizeof(float)));
-    l.finals = l.band_offsets + val_align(items * static_cast<int64_t>(sizeof(int64_t)));
-    l.total = l.finals + val_align(2 * kValFinal * static_cast<int64_t>(sizeof(float)));
+    l.band_offsets = align256(2 * items * kValPartial * static_cast<int64_t>(sizeof(float)));
+    l.finals = l.band_offsets + align256(items * static_cast<int64_t>(sizeof(int64_t)));
+    l.total = l.finals + align256(2 * kValFinal * static_cast<int64_t>(sizeof(float)));
     return l;
 }
 
 // N, H, W in range and one section's rows and columns 32-bit numbers (the write kernel addresses sections by blockIdx.y and bytes in 64 bits)
 static bool val_sizes_ok(int n, int h, int w) {
-    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || static_cast<int64_t>(n) * h * w > INT32_MAX) return false;
+    if (!frames_sizes_ok(n, h, w)) return false;
     const int64_t xmaps = n < kDispNrow ? n : kDispNrow, ymaps = (n + xmaps - 1) / xmaps;
     const int64_t gh = (static_cast<int64_t>(h) + kDispPad) * ymaps + kDispPad, gw = (static_cast<int64_t>(w) + kDispPad) * xmaps + kDispPad;
     return gh <= INT32_MAX && gw <= INT32_MAX;
@@ -408,7 +360,7 @@ using namespace endo;
 extern "C" int endo_depth_metrics(const float* scaled_depths, const float* sparse_depths, const float* sparse_masks, int n, int h, int w,
                                   float eps, float* out, void* stream_) {
     if (!scaled_depths || !sparse_depths || !sparse_masks || !out) return ENDO_E_BADARG;
-    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || static_cast<int64_t>(n) * h * w > INT32_MAX) return ENDO_E_BADARG;
+    if (!frames_sizes_ok(n, h, w)) return ENDO_E_BADARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int64_t pixels = static_cast<int64_t>(h) * w;
     ProfScope prof(kProfSmall, stream, 0.0, static_cast<double>(n) * pixels * 12.0);
@@ -459,7 +411,7 @@ extern "C" int endo_evaluate_validation(const float* colors_1, const float* colo
                    pixels * 4.0 * (2 * 7 + 2 * 12 + 5) + pixels * 24.0 + static_cast<double>(kValSections) * g.gh * g.gw * 3.0);
     val_reduce_kernel<<<dim3(g.bands, n, 2), kDispThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
-    val_scan_kernel<<<1, kValScanThreads, 0, stream>>>(q);
+    val_scan_kernel<<<1, kScanThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     const int64_t items = static_cast<int64_t>(n) * g.bands;
     const int64_t across = std::max<int64_t>(std::max<int64_t>(items, g.gh), 2 * n);

@@ -391,8 +391,6 @@ __global__ void __launch_bounds__(256) jpeg_resize_crop_kernel(const uint8_t* __
     }
 }
 
-static int64_t align256(int64_t v) { return (v + 255) & ~static_cast<int64_t>(255); }
-
 struct JpegLayout {
     int64_t coef_bytes, quant_off, planes_off, total;
     JpegPlanes pl;

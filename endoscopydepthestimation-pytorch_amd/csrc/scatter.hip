@@ -7,6 +7,7 @@
 // Collisions: numpy fancy-index assignment lets the HIGHEST point index win; here an atomicMax on a per-pixel
 // winner plane decides, then only the winner writes.  All projection arithmetic is fp64 with numpy's evaluation
 // order (row-vector times matrix-transpose: a 4-term dot product, left to right), np.round = rint (half to even).
+#include "cloud_device.h"
 #include "common.h"
 
 namespace endo {
@@ -123,8 +124,8 @@ extern "C" int endo_sparse_scatter(const double* points, int n_points, const dou
 // Coloured point cloud of a depth map (reference utils.py:823-852 point_cloud_from_depth, called per frame by
 // evaluate.py:272,340): every `downsampling`-th pixel inside the mask becomes (x, y, z, r, g, b), row-major order.
 // Deterministic compaction: one block per image row counts its hits, a one-thread kernel scans the row counts, then one
-// block per row writes its points at the row's offset, ordered inside the row by a wave-ballot prefix.  fp32 with the reference's operation order ((w - cx) / fx * z: three
-// roundings; the compiler must not contract it into an fma).
+// block per row writes its points at the row's offset, ordered inside the row by cloud_device.h's chunk rank.  fp32 with the reference's
+// operation order ((w - cx) / fx * z: three roundings; the compiler must not contract it into an fma).
 // ---------------------------------------------------------------------------------------------
 namespace endo {
 
@@ -141,9 +142,8 @@ struct CloudParams {
 };
 
 __device__ __forceinline__ bool cloud_keep(const CloudParams& q, int h, int w) {
-    if (h % q.downsampling != 0 || w % q.downsampling != 0) return false;
     const int64_t i = static_cast<int64_t>(h) * q.width + w;
-    if (!(q.mask[i] > 0.5f)) return false;
+    if (!cloud_pixel_keep(q.downsampling, h, w, q.mask[i])) return false;
     if (q.use_threshold) {
         const int b = q.color[3 * i], g = q.color[3 * i + 1], r = q.color[3 * i + 2];
         const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
@@ -152,16 +152,12 @@ __device__ __forceinline__ bool cloud_keep(const CloudParams& q, int h, int w) {
     return true;
 }
 
-__global__ void __launch_bounds__(256) cloud_count_kernel(const CloudParams q) {
-    __shared__ int s_cnt[4];
+__global__ void __launch_bounds__(kCloudThreads) cloud_count_kernel(const CloudParams q) {
     const int h = blockIdx.x;
     int cnt = 0;
-    for (int w = threadIdx.x; w < q.width; w += 256) cnt += cloud_keep(q, h, w) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) q.row_offsets[h + 1] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    for (int w = threadIdx.x; w < q.width; w += kCloudThreads) cnt += cloud_wave_count(cloud_keep(q, h, w));
+    cnt = cloud_block_count(cnt);
+    if (threadIdx.x == 0) q.row_offsets[h + 1] = cnt;
 }
 
 // in place: row_offsets[h + 1] holds row h's count on entry, the inclusive prefix on exit; row_offsets[0] = 0
@@ -174,39 +170,27 @@ __global__ void cloud_scan_kernel(int* row_offsets, int height, int* count) {
     }
 }
 
-__global__ void __launch_bounds__(256) cloud_write_kernel(const CloudParams q) {
-    __shared__ int s_wave[4];
-    __shared__ int s_base;
+__global__ void __launch_bounds__(kCloudThreads) cloud_write_kernel(const CloudParams q) {
     const int h = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = q.row_offsets[h];
-    __syncthreads();
+    int64_t at = q.row_offsets[h];          // where this chunk's points start
     const float fx = q.k[0], cx = q.k[2], fy = q.k[4], cy = q.k[5];
-    for (int w0 = 0; w0 < q.width; w0 += 256) {
+    for (int w0 = 0; w0 < q.width; w0 += kCloudThreads) {
         const int w = w0 + threadIdx.x;
         const bool keep = w < q.width && cloud_keep(q, h, w);
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int wave_off = 0;
-        for (int i = 0; i < wave; ++i) wave_off += s_wave[i];
-        const int chunk_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        int total;
+        const int rank = cloud_chunk_rank(keep, total);
         if (keep) {
             const int64_t i = static_cast<int64_t>(h) * q.width + w;
             const float z = q.depth[i];
-            // separate roundings, as numpy evaluates (w - cx) / fx * z
-            const float x = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(w), cx), fx), z);
-            const float y = __fmul_rn(__fdiv_rn(__fsub_rn(static_cast<float>(h), cy), fy), z);
-            float* dst = q.points + static_cast<int64_t>(s_base + wave_off + before) * 6;
+            float x, y;
+            cloud_back_project(w, h, fx, cx, fy, cy, z, x, y);
+            float* dst = q.points + (at + rank) * 6;
             dst[0] = x; dst[1] = y; dst[2] = z;
             dst[3] = static_cast<float>(q.color[3 * i + 2]);
             dst[4] = static_cast<float>(q.color[3 * i + 1]);
             dst[5] = static_cast<float>(q.color[3 * i]);
         }
-        __syncthreads();
-        if (threadIdx.x == 0) s_base += chunk_total;
-        __syncthreads();
+        at += total;
     }
 }
 
@@ -284,11 +268,11 @@ extern "C" int endo_point_cloud(const float* depth, const uint8_t* color_bgr, co
     CloudParams q{depth, color_bgr, mask, intrinsics, height, width, downsampling, use_threshold, min_threshold, max_threshold,
                   row_offsets, points, count_out};
     ProfScope prof(kProfGeometry, stream, 0.0, 4.0 * height * width * 3);
-    cloud_count_kernel<<<height, 256, 0, stream>>>(q);
+    cloud_count_kernel<<<height, kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     cloud_scan_kernel<<<1, 64, 0, stream>>>(row_offsets, height, count_out);
     ENDO_LAUNCH_CHECK();
-    cloud_write_kernel<<<height, 256, 0, stream>>>(q);
+    cloud_write_kernel<<<height, kCloudThreads, 0, stream>>>(q);
     ENDO_LAUNCH_CHECK();
     return 0;
 }

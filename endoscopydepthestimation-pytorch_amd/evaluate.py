@@ -42,13 +42,18 @@ def _device_f32(t, shape, name):
     return t.contiguous()
 
 
-def test_outputs(model, batch, is_hsv=False, point_cloud_downsampling=1):
-    """evaluate.py:323-344 for a TestFrames batch: the network on ``boundaries * colors`` and the per-frame outputs, on the device.
-    Returns a dictionary: colors (the masked network input), predictions, depth (N, 1, H, W) fp32, panels (N, H, 2W, 3) uint8 B, G, R
-    (what evaluate.py:345 hands to cv2.imwrite), points (capacity N * H * W rows of x, y, z, r, g, b) and offsets: the host list of N + 1
-    row offsets, frame f's points being points[offsets[f]:offsets[f + 1]] -- the batch's one read back to the host."""
+def _checked_inputs(colors, boundaries, predictions, intrinsics):
+    """The four inputs of the two *_from_predictions functions, checked and contiguous, and the batch's (N, H, W)."""
+    n, _, height, width = (int(v) for v in colors.shape)
+    return (_device_f32(colors, (n, 3, height, width), "colors"), _device_f32(boundaries, (n, 1, height, width), "boundaries"),
+            _device_f32(predictions, (n, 1, height, width), "predictions"), _device_f32(intrinsics, (n, 3, 3), "intrinsics"), n, height, width)
+
+
+def _masked_forward(model, batch, caller):
+    """evaluate.py:323-327 for a TestFrames batch: the network in eval mode on ``boundaries * colors``.  Returns the masked input,
+    the boundaries, the predictions and the intrinsics."""
     if model.training:
-        raise RuntimeError("test_outputs runs the network in eval mode: call model.eval() first (evaluate.py:313)")
+        raise RuntimeError("%s runs the network in eval mode: call model.eval() first (evaluate.py:313)" % caller)
     colors = batch["colors"]
     if not torch.is_tensor(colors) or colors.dim() != 4 or colors.shape[1] != 3:
         raise ValueError("colors must be an (N, 3, H, W) tensor")
@@ -59,6 +64,44 @@ def test_outputs(model, batch, is_hsv=False, point_cloud_downsampling=1):
     with torch.no_grad(), torch.cuda.device(colors.device):
         masked = boundaries * colors          # evaluate.py:325
         pred = model(masked)
+    return masked, boundaries, pred, intrinsics
+
+
+class _WriterPool:
+    """The writer threads of a run_* phase.  submit(fn, *args) records an event behind the non-blocking copies queued so far and
+    runs fn(event, *args) on a thread; at most 2 * writers batches of host copies are in flight; leaving the block waits for every
+    file and re-raises a writer's exception, after an exception in the block too."""
+
+    def __init__(self, writers):
+        self._bound = 2 * max(1, int(writers))
+        self._pool = ThreadPoolExecutor(max(1, int(writers)))
+        self._pending = deque()
+
+    def __enter__(self):
+        return self
+
+    def submit(self, fn, *args):
+        ready = torch.cuda.Event()
+        ready.record()
+        self._pending.append(self._pool.submit(fn, ready, *args))
+        while len(self._pending) > self._bound:          # bound the host copies in flight
+            self._pending.popleft().result()
+
+    def __exit__(self, *exc):
+        try:
+            while self._pending:
+                self._pending.popleft().result()
+        finally:
+            self._pool.shutdown(wait=True)
+        return False
+
+
+def test_outputs(model, batch, is_hsv=False, point_cloud_downsampling=1):
+    """evaluate.py:323-344 for a TestFrames batch: the network on ``boundaries * colors`` and the per-frame outputs, on the device.
+    Returns a dictionary: colors (the masked network input), predictions, depth (N, 1, H, W) fp32, panels (N, H, 2W, 3) uint8 B, G, R
+    (what evaluate.py:345 hands to cv2.imwrite), points (capacity N * H * W rows of x, y, z, r, g, b) and offsets: the host list of N + 1
+    row offsets, frame f's points being points[offsets[f]:offsets[f + 1]] -- the batch's one read back to the host."""
+    masked, boundaries, pred, intrinsics = _masked_forward(model, batch, "test_outputs")
     out = outputs_from_predictions(masked, boundaries, pred, intrinsics, is_hsv, point_cloud_downsampling)
     out["colors"], out["predictions"] = masked, pred
     return out
@@ -68,11 +111,7 @@ def outputs_from_predictions(colors, boundaries, predictions, intrinsics, is_hsv
     """endo_evaluate on a batch: colors (N, 3, H, W) the masked network input, boundaries (N, 1, H, W) in {0, 1}, predictions
     (N, 1, H, W) the network's output, intrinsics (N, 3, 3), all fp32 on the device.  Returns depth, panels, points and the host list
     of offsets as test_outputs does."""
-    n, _, height, width = (int(v) for v in colors.shape)
-    colors = _device_f32(colors, (n, 3, height, width), "colors")
-    boundaries = _device_f32(boundaries, (n, 1, height, width), "boundaries")
-    predictions = _device_f32(predictions, (n, 1, height, width), "predictions")
-    intrinsics = _device_f32(intrinsics, (n, 3, 3), "intrinsics")
+    colors, boundaries, predictions, intrinsics, n, height, width = _checked_inputs(colors, boundaries, predictions, intrinsics)
     lib = _lib.load()
     dev = colors.device
     need = int(lib.endo_evaluate_workspace_bytes(n, height, width))
@@ -109,26 +148,17 @@ def run_test_phase(model, frames, out_dir, write_png=True, write_ply=True, ply_t
     out_dir = str(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     count = 0
-    pending = deque()
-    with ThreadPoolExecutor(max(1, int(writers))) as pool:
-        try:
-            for batch in frames:
-                out = test_outputs(model, batch, is_hsv=frames.is_hsv, point_cloud_downsampling=point_cloud_downsampling)
-                names = list(batch["names"])
-                count += len(names)
-                if not (write_png or write_ply):
-                    continue
-                offsets = out["offsets"]
-                panels = out["panels"].to("cpu", non_blocking=True) if write_png else None
-                points = out["points"][:offsets[-1]].to("cpu", non_blocking=True) if write_ply else None
-                ready = torch.cuda.Event()
-                ready.record()
-                pending.append(pool.submit(_write_frames, ready, names, panels, points, offsets, out_dir, write_png, write_ply, ply_text))
-                while len(pending) > 2 * max(1, int(writers)):          # bound the host copies in flight
-                    pending.popleft().result()
-        finally:
-            while pending:
-                pending.popleft().result()
+    with _WriterPool(writers) as pool:
+        for batch in frames:
+            out = test_outputs(model, batch, is_hsv=frames.is_hsv, point_cloud_downsampling=point_cloud_downsampling)
+            names = list(batch["names"])
+            count += len(names)
+            if not (write_png or write_ply):
+                continue
+            offsets = out["offsets"]
+            panels = out["panels"].to("cpu", non_blocking=True) if write_png else None
+            points = out["points"][:offsets[-1]].to("cpu", non_blocking=True) if write_ply else None
+            pool.submit(_write_frames, names, panels, points, offsets, out_dir, write_png, write_ply, ply_text)
     return count
 
 
@@ -159,11 +189,7 @@ def posed_outputs_from_predictions(colors, boundaries, predictions, intrinsics, 
     (N, 2) float32 array of each frame's (z_min, z_max) over its kept pixels: (+inf, -inf) for a frame without kept pixels (the
     reference raises ZeroDivisionError there: its sentinels are Python ints), z_min == z_max for a frame whose coordinates are not
     finite (scale = 20 / 0).  Offsets and ranges are the batch's one read back to the host."""
-    n, _, height, width = (int(v) for v in colors.shape)
-    colors = _device_f32(colors, (n, 3, height, width), "colors")
-    boundaries = _device_f32(boundaries, (n, 1, height, width), "boundaries")
-    predictions = _device_f32(predictions, (n, 1, height, width), "predictions")
-    intrinsics = _device_f32(intrinsics, (n, 3, 3), "intrinsics")
+    colors, boundaries, predictions, intrinsics, n, height, width = _checked_inputs(colors, boundaries, predictions, intrinsics)
     lib = _lib.load()
     dev = colors.device
     rotations, translations = _poses_f64(rotations, translations, n, dev)
@@ -195,18 +221,7 @@ def posed_test_outputs(model, batch, rotations, translations, is_hsv=False, poin
                        max_threshold=None):
     """A TestFrames batch through the network in eval mode on ``boundaries * colors`` (evaluate.py:323-327) and
     posed_outputs_from_predictions with the batch's poses.  Returns its dictionary plus colors (the masked input) and predictions."""
-    if model.training:
-        raise RuntimeError("posed_test_outputs runs the network in eval mode: call model.eval() first (evaluate.py:313)")
-    colors = batch["colors"]
-    if not torch.is_tensor(colors) or colors.dim() != 4 or colors.shape[1] != 3:
-        raise ValueError("colors must be an (N, 3, H, W) tensor")
-    n, _, height, width = (int(v) for v in colors.shape)
-    colors = _device_f32(colors, (n, 3, height, width), "colors")
-    boundaries = _device_f32(batch["boundaries"], (n, 1, height, width), "boundaries")
-    intrinsics = _device_f32(batch["intrinsics"], (n, 3, 3), "intrinsics")
-    with torch.no_grad(), torch.cuda.device(colors.device):
-        masked = boundaries * colors
-        pred = model(masked)
+    masked, boundaries, pred, intrinsics = _masked_forward(model, batch, "posed_test_outputs")
     out = posed_outputs_from_predictions(masked, boundaries, pred, intrinsics, rotations, translations, is_hsv, point_cloud_downsampling,
                                          min_threshold, max_threshold)
     out["colors"], out["predictions"] = masked, pred
@@ -254,47 +269,35 @@ def run_posed_test_phase(model, frames, translation_dict, rotation_dict, out_dir
     os.makedirs(out_dir, exist_ok=True)
     count, merged_points = 0, 0
     empty, zero_range, parts = [], [], []
-    pending = deque()
-    with ThreadPoolExecutor(max(1, int(writers))) as pool:
-        try:
-            for batch in frames:
-                names = list(batch["names"])
-                rotations = [rotation_dict[name] for name in names]
-                translations = [translation_dict[name] for name in names]
-                out = posed_test_outputs(model, batch, rotations, translations, is_hsv=getattr(frames, "is_hsv", False),
-                                         point_cloud_downsampling=point_cloud_downsampling, min_threshold=min_threshold,
-                                         max_threshold=max_threshold)
-                count += len(names)
-                offsets, ranges = out["offsets"], out["ranges"]
-                good = []
-                for f, name in enumerate(names):
-                    if ranges[f, 0] > ranges[f, 1]:
-                        empty.append(name)
-                    elif ranges[f, 0] == ranges[f, 1]:
-                        zero_range.append(name)
-                    else:
-                        good.append(f)
-                        merged_points += offsets[f + 1] - offsets[f]
-                if not (write_images or write_ply):
-                    continue
-                color_images = out["color_images"].to("cpu", non_blocking=True) if write_images else None
-                depth_images = out["depth_images"].to("cpu", non_blocking=True) if write_images else None
-                points = out["points"][:offsets[-1]].to("cpu", non_blocking=True) if write_ply else None
-                ready = torch.cuda.Event()
-                ready.record()
-                if write_ply and merged:
-                    parts.extend(points[offsets[f]:offsets[f + 1]] for f in good)
-                pending.append(pool.submit(_write_posed_frames, ready, names, color_images, depth_images, points, offsets, out_dir,
-                                           write_ply, ply_text))
-                while len(pending) > 2 * max(1, int(writers)):          # bound the host copies in flight
-                    pending.popleft().result()
+    with _WriterPool(writers) as pool:
+        for batch in frames:
+            names = list(batch["names"])
+            rotations = [rotation_dict[name] for name in names]
+            translations = [translation_dict[name] for name in names]
+            out = posed_test_outputs(model, batch, rotations, translations, is_hsv=getattr(frames, "is_hsv", False),
+                                     point_cloud_downsampling=point_cloud_downsampling, min_threshold=min_threshold,
+                                     max_threshold=max_threshold)
+            count += len(names)
+            offsets, ranges = out["offsets"], out["ranges"]
+            good = []
+            for f, name in enumerate(names):
+                if ranges[f, 0] > ranges[f, 1]:
+                    empty.append(name)
+                elif ranges[f, 0] == ranges[f, 1]:
+                    zero_range.append(name)
+                else:
+                    good.append(f)
+                    merged_points += offsets[f + 1] - offsets[f]
+            if not (write_images or write_ply):
+                continue
+            color_images = out["color_images"].to("cpu", non_blocking=True) if write_images else None
+            depth_images = out["depth_images"].to("cpu", non_blocking=True) if write_images else None
+            points = out["points"][:offsets[-1]].to("cpu", non_blocking=True) if write_ply else None
             if write_ply and merged:
-                ready = torch.cuda.Event()
-                ready.record()
-                pending.append(pool.submit(_write_merged, ready, os.path.join(out_dir, str(merged)), parts, ply_text))
-        finally:
-            while pending:
-                pending.popleft().result()
+                parts.extend(points[offsets[f]:offsets[f + 1]] for f in good)
+            pool.submit(_write_posed_frames, names, color_images, depth_images, points, offsets, out_dir, write_ply, ply_text)
+        if write_ply and merged:
+            pool.submit(_write_merged, os.path.join(out_dir, str(merged)), parts, ply_text)
     return {"frames": count, "empty": empty, "zero_range": zero_range, "merged_points": int(merged_points)}
 
 
@@ -371,29 +374,20 @@ def run_validation_phase(model, batches, out_dir, write_png=True, write_ply=True
     left out of them: pairs without sparse points in that frame)."""
     out_dir = str(out_dir)
     os.makedirs(out_dir, exist_ok=True)
-    pending = deque()
     collected = []
-    with ThreadPoolExecutor(max(1, int(writers))) as pool:
-        try:
-            for index, batch in enumerate(batches):
-                out = validation_outputs(model, batch, is_hsv=getattr(batches, "is_hsv", False))
-                collected.append(out["metrics"])
-                if writer is not None:
-                    display.stack_and_display("validation", VALIDATION_TITLE, step, writer, out["panel"])
-                if not (write_png or write_ply):
-                    continue
-                offsets = out["offsets"]
-                samples = range(len(offsets) - 1) if all_samples else range(1)
-                panel = out["panel"].to("cpu", non_blocking=True) if write_png else None
-                points = out["points"][:offsets[samples[-1] + 1]].to("cpu", non_blocking=True) if write_ply else None
-                ready = torch.cuda.Event()
-                ready.record()
-                pending.append(pool.submit(_write_validation_batch, ready, index, panel, points, offsets, samples, out_dir, ply_text))
-                while len(pending) > 2 * max(1, int(writers)):          # bound the host copies in flight
-                    pending.popleft().result()
-        finally:
-            while pending:
-                pending.popleft().result()
+    with _WriterPool(writers) as pool:
+        for index, batch in enumerate(batches):
+            out = validation_outputs(model, batch, is_hsv=getattr(batches, "is_hsv", False))
+            collected.append(out["metrics"])
+            if writer is not None:
+                display.stack_and_display("validation", VALIDATION_TITLE, step, writer, out["panel"])
+            if not (write_png or write_ply):
+                continue
+            offsets = out["offsets"]
+            samples = range(len(offsets) - 1) if all_samples else range(1)
+            panel = out["panel"].to("cpu", non_blocking=True) if write_png else None
+            points = out["points"][:offsets[samples[-1] + 1]].to("cpu", non_blocking=True) if write_ply else None
+            pool.submit(_write_validation_batch, index, panel, points, offsets, samples, out_dir, ply_text)
     if collected:
         metrics = torch.cat(collected, dim=0).cpu().numpy()          # the pass's one read of the measures
     else:

@@ -69,9 +69,13 @@ def device_outputs(c, b, pred, kk, is_hsv, ds=1):
     return out["depth"].cpu().numpy(), out["panels"].cpu().numpy(), out["points"].cpu().numpy(), out["offsets"]
 
 
-@pytest.mark.parametrize("is_hsv", [False, True])
-@pytest.mark.parametrize("size", [(64, 96), (256, 320)])
-@pytest.mark.parametrize("n", [1, 3, 8])
+# sizes 2 .. 4 (at n = 2): a row one pixel short of the write kernel's 256-pixel chunk, exactly one chunk, and one pixel into a second
+SIZES = [(64, 96), (256, 320), (5, 255), (5, 256), (5, 257)]
+CASES = ([(n, s, hsv) for hsv in (False, True) for s in (0, 1) for n in (1, 3, 8)] +
+         [(2, s, hsv) for hsv in (False, True) for s in (2, 3, 4)])
+
+
+@pytest.mark.parametrize("n, size, is_hsv", [(n, SIZES[s], hsv) for n, s, hsv in CASES], ids=["%d-size%d-%s" % c for c in CASES])
 def test_outputs_match_restatement(n, size, is_hsv):
     h, w = size
     c, b, pred, kk = random_batch(n, h, w, seed=n * 100 + h + int(is_hsv))

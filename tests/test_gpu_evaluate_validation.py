@@ -204,11 +204,17 @@ def test_panel_matches_restatement(n, h, w, constant):
     assert out["metrics"].shape == (n, 2, 4)
 
 
-@pytest.mark.parametrize("ds", [1, 2])
-def test_points_match_point_cloud(ds):
+# (2, 9, 257): a second, one-pixel chunk of every row and a partial last band; (130, 64, 8): 130 * 8 = 1040 bands, more than the scan
+# block's 1024 threads, so a thread owns two.  The first shape keeps the ids it had before the shape was a parameter.
+CLOUD_SHAPES = [(3, 64, 96), (2, 9, 257), (130, 64, 8)]
+
+
+@pytest.mark.parametrize("ds, shape", [pytest.param(ds, s, id=str(ds) if s == CLOUD_SHAPES[0] else "%d-%dx%dx%d" % ((ds,) + s))
+                                       for s in CLOUD_SHAPES for ds in (1, 2)])
+def test_points_match_point_cloud(ds, shape):
     """Point rows and offsets = utils.point_cloud_from_depth (endo_point_cloud) per frame on the unmasked scaled depth 1, the frame's own
     colour bytes, the boundary and the intrinsics."""
-    n, h, w = 3, 64, 96
+    n, h, w = shape
     x = validation_inputs(n, h, w, seed=5)
     out = device_outputs(x, ds)
     offsets = out["offsets"].tolist()
