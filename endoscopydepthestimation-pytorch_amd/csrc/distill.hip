@@ -2,9 +2,10 @@
 // |teacher| under the boundary mask, both frames, forward and backward, as two launches: one reduction over the 2n sample rows (frame 1's
 // n samples, then frame 2's) and one apply pass whose first block also writes the loss values and the guard flag.  The apply pass forms
 // the two logarithms again instead of reading a plane the reduction would have stored: 4 floats moved per element instead of 5, and
-// the kernels are bound by their launches at the sizes of a training step anyway.  Arithmetic: scale_inv_reduce /
-// scale_inv_finalize / scale_inv_bwd_kernel (losses.hip) with |.| on both maps -- fp32 per element, fp64 per-sample sums.
+// the kernels are bound by their launches at the sizes of a training step anyway.  The arithmetic is
+// loss_device.h's scale_inv_* with |.| on both maps.
 #include "common.h"
+#include "loss_device.h"
 
 namespace endo {
 
@@ -17,13 +18,8 @@ struct DistillMaps {
     float* grad[2];
 };
 
-__device__ __forceinline__ float distill_sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
-
 __device__ __forceinline__ void distill_accumulate(float p, float g, float m, float eps, float (&part)[3]) {
-    const float r = logf(m * fabsf(p) + eps) - logf(m * fabsf(g) + eps);
-    part[0] += r * r;
-    part[1] += r;
-    part[2] += m;
+    scale_inv_accumulate(fabsf(p), fabsf(g), m, eps, part);
 }
 
 // V = 4: hw is a multiple of 4 and every map starts on 16 bytes, so each sample row does too; V = 1: any hw, any alignment.
@@ -57,19 +53,9 @@ __global__ void __launch_bounds__(kDistillThreads) distill_reduce(DistillMaps ma
 }
 
 __device__ __forceinline__ float distill_grad(float p, float g, float m, float eps, float c2, float c1) {
-    const float up = m * fabsf(p) + eps, ug = m * fabsf(g) + eps;
-    const float r = logf(up) - logf(ug);
-    return (c2 * r + c1) * m / up * distill_sgn(p);
-}
-
-// one frame's mean over its n samples of R2 / S + R1^2 / S^2 (scale_inv_finalize)
-__device__ __forceinline__ float distill_term(const double* stats, int n) {
-    float acc = 0.f;
-    for (int i = 0; i < n; ++i) {
-        const float r2 = static_cast<float>(stats[3 * i]), r1 = static_cast<float>(stats[3 * i + 1]), wsum = static_cast<float>(stats[3 * i + 2]);
-        acc += r2 / wsum + (r1 * r1) / (wsum * wsum);
-    }
-    return acc / static_cast<float>(n);
+    float gp, gg;
+    scale_inv_grad(fabsf(p), fabsf(g), m, eps, c2, c1, gp, gg);
+    return gp * sgn(p);
 }
 
 template <int V, int ACC>
@@ -77,7 +63,7 @@ __global__ void __launch_bounds__(kDistillThreads) distill_apply(DistillMaps map
                                                                  float* losses, float weight, int n, int hw, float eps) {
     const int row = blockIdx.y, frame = row >= n ? 1 : 0, sample = row - frame * n;
     if (blockIdx.x == 0 && row == 0 && threadIdx.x == 0) {          // the loss values and the guard of train.py:317, on the device
-        const float distill = weight * 0.5f * (distill_term(stats, n) + distill_term(stats + 3 * n, n));
+        const float distill = weight * 0.5f * (scale_inv_mean(stats, n) + scale_inv_mean(stats + 3 * n, n));
         const float total = ACC ? losses[0] + distill : distill;
         const float bad = (isnan(total) || isinf(total)) ? 1.f : 0.f;
         losses[0] = total;
@@ -95,10 +81,8 @@ __global__ void __launch_bounds__(kDistillThreads) distill_apply(DistillMaps map
     const float* __restrict__ g = maps.goal[frame] + base;
     const float* __restrict__ m = b + base;
     float* __restrict__ out = maps.grad[frame] + base;
-    const float wsum = static_cast<float>(stats[3 * row + 2]);
-    const float up = weight * 0.5f / static_cast<float>(n);          // d distill / d L_s
-    const float c2 = 2.0f * up / wsum;                                              // * r
-    const float c1 = 2.0f * up * static_cast<float>(stats[3 * row + 1]) / (wsum * wsum);
+    float c2, c1;
+    scale_inv_coefs(weight * 0.5f / static_cast<float>(n), stats + 3 * row, c2, c1);          // under d distill / d L_s
     if (V == 4) {
         const int hw4 = hw >> 2;
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += gridDim.x * blockDim.x) {

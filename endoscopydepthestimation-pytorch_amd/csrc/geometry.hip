@@ -4,6 +4,7 @@
 // materialised, reductions use wave shuffles + one fp64 atomic per block.
 #include "common.h"
 #include "geometry_device.h"
+#include "loss_device.h"
 
 namespace endo {
 
@@ -360,6 +361,158 @@ __device__ __forceinline__ void block_tap_box(int minx, int miny, int maxx, int 
     bh = maxy - miny + 2;
 }
 
+// ---- the steps the four tiled kernels share (warp_*_tiled_kernel, consistency_*_kernel): what differs between them -- the pixel's
+// own depth, the loss sums, where the incoming gradient comes from, how the own-pixel gradient is written -- stays in the kernels ----
+
+// A thread's kPix pixels of the block's tile: the taps of each sample position, the pixel's mask and own depth, and what the backward
+// chain rule needs of the projection.  A kernel that does not read a member does not pay for it.
+template <int TY, int TX>
+struct WarpPixels {
+    using T = WarpTile<TY, TX>;
+    Taps tp[T::kPix];
+    float m[T::kPix], dself[T::kPix];
+    float qx[T::kPix], qy[T::kPix], qz[T::kPix], zt[T::kPix], nx[T::kPix], ny[T::kPix];
+    bool open[T::kPix];
+};
+
+// pixel k of this thread in the tile at (tx0, ty0); false: outside the image
+template <int TY, int TX>
+__device__ __forceinline__ bool tile_pixel(int k, int tx0, int ty0, int h, int w, int& xx, int& yy) {
+    const int idx = threadIdx.x + k * WarpTile<TY, TX>::kThreads;
+    yy = ty0 + idx / TX;
+    xx = tx0 + idx % TX;
+    return yy < h && xx < w;
+}
+
+// the source tile of frame 2 a block's taps fall into, and whether it fits the staging buffers (block-uniform)
+struct SourceBox {
+    int x0, y0, w, h;
+    bool staged;
+};
+
+// Every pixel's sample position, then the block's source box; a block whose box does not fit counts itself in g_warp_fallback[which].
+template <int TY, int TX>
+__device__ __forceinline__ SourceBox warp_sample_tile(const Camera& cam, const float* __restrict__ d1, const float* __restrict__ mask, int64_t base,
+                                                      int h, int w, int tx0, int ty0, float eps, int which, int* s_box, WarpPixels<TY, TX>& px) {
+    // the projection's three multiply-adds are written out: left to contraction, the instantiation with one pixel per thread lost
+    // one to the vectoriser and its d1 gradient left the gather kernels' by a rounding
+#pragma clang fp contract(off)
+    using T = WarpTile<TY, TX>;
+    int minx = 1 << 30, miny = 1 << 30, maxx = -(1 << 30), maxy = -(1 << 30);
+#pragma unroll
+    for (int k = 0; k < T::kPix; ++k) {
+        int xx, yy;
+        const bool inside = tile_pixel<TY, TX>(k, tx0, ty0, h, w, xx, yy);
+        Taps& tp = px.tp[k];
+        tp.vw = tp.ve = tp.vn = tp.vs = false;
+        tp.x0 = tp.y0 = 0;
+        px.m[k] = 0.f; px.open[k] = false; px.dself[k] = 0.f;
+        px.qx[k] = px.qy[k] = px.qz[k] = px.nx[k] = px.ny[k] = 0.f; px.zt[k] = 1.f;
+        if (inside) {
+            ray(cam, static_cast<float>(xx), static_cast<float>(yy), px.qx[k], px.qy[k], px.qz[k]);
+            const float m = mask[base + static_cast<int64_t>(yy) * w + xx];
+            px.dself[k] = d1[base + static_cast<int64_t>(yy) * w + xx];
+            const float dm = px.dself[k] * m;
+            const float z2 = fmaf(dm, px.qz[k], cam.w[2]);
+            float zt = (m > 0.5f) ? z2 : eps;
+            px.open[k] = (m > 0.5f) && (zt > 0.0f);
+            zt = (zt > 0.0f) ? zt : eps;
+            px.zt[k] = zt; px.m[k] = m;
+            px.nx[k] = fmaf(dm, px.qx[k], cam.w[0]);
+            px.ny[k] = fmaf(dm, px.qy[k], cam.w[1]);
+            tp = make_taps(px.nx[k] / zt, px.ny[k] / zt, w, h);
+            if ((tp.vw || tp.ve) && (tp.vn || tp.vs)) {
+                minx = min(minx, tp.x0); maxx = max(maxx, tp.x0);
+                miny = min(miny, tp.y0); maxy = max(maxy, tp.y0);
+            }
+        }
+    }
+    SourceBox box;
+    block_tap_box(minx, miny, maxx, maxy, s_box, box.x0, box.y0, box.w, box.h);
+    box.staged = box.w <= T::BW && box.h <= T::BH && box.w > 0;          // box.w <= 0: no pixel of the block has a tap in range
+    if (!box.staged && box.w > 0 && threadIdx.x == 0) count_fallback(which);
+    return box;
+}
+
+// D and m of the source tile into LDS, once per source pixel (GRAD: and the tile of d2 gradients cleared)
+template <class T, bool GRAD>
+__device__ __forceinline__ void stage_source_tile(const Camera& cam, const float* __restrict__ d2, const float* __restrict__ mask, int64_t base, int h,
+                                                  int w, const SourceBox& box, float* s_d, float* s_m, float* s_g) {
+    if (!box.staged) return;
+    const int bx0 = box.x0, by0 = box.y0, bw = box.w, bh = box.h;
+    for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
+        const int ry = e / T::BW, rx = e - ry * T::BW;
+        const int sy = by0 + ry, sx = bx0 + rx;
+        float dv = 0.f, mv = 0.f, ss;
+        if (rx < bw && sy >= 0 && sy < h && sx >= 0 && sx < w) dv = depth_in_1(cam, d2, mask, base, w, sx, sy, &mv, &ss);
+        s_d[e] = dv; s_m[e] = mv;
+        if (GRAD) s_g[e] = 0.f;
+    }
+    __syncthreads();
+}
+
+// the four taps' D and m of one pixel, from the staged tile or by gather
+template <class T>
+__device__ __forceinline__ void fetch_taps(const Camera& cam, const float* __restrict__ d2, const float* __restrict__ mask, int64_t base, int w,
+                                           const Taps& q, const SourceBox& box, const float* s_d, const float* s_m, float (&v)[4], float (&mm)[4]) {
+    float ss;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = mm[c] = 0.f;
+    if (box.staged) {
+        const int o = (q.y0 - box.y0) * T::BW + (q.x0 - box.x0);
+        if (q.vw && q.vn) { v[0] = s_d[o]; mm[0] = s_m[o]; }
+        if (q.ve && q.vn) { v[1] = s_d[o + 1]; mm[1] = s_m[o + 1]; }
+        if (q.vw && q.vs) { v[2] = s_d[o + T::BW]; mm[2] = s_m[o + T::BW]; }
+        if (q.ve && q.vs) { v[3] = s_d[o + T::BW + 1]; mm[3] = s_m[o + T::BW + 1]; }
+    } else {
+        if (q.vw && q.vn) v[0] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0, &mm[0], &ss);
+        if (q.ve && q.vn) v[1] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0, &mm[1], &ss);
+        if (q.vw && q.vs) v[2] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0 + 1, &mm[2], &ss);
+        if (q.ve && q.vs) v[3] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0 + 1, &mm[3], &ss);
+    }
+}
+
+// backward: the four taps' D of one pixel, and the pixel's incoming gradient g scattered to the taps' d2 -- into the LDS tile, or
+// straight into global memory where the block gathers
+template <class T>
+__device__ __forceinline__ void scatter_taps(const Camera& cam, const float* __restrict__ d2, const float* __restrict__ mask, int64_t base, int w,
+                                             const Taps& q, const SourceBox& box, const float* s_d, const float* s_m, float* s_g, float* gd2,
+                                             float g, float (&v)[4]) {
+    const bool val[4] = {q.vw && q.vn, q.ve && q.vn, q.vw && q.vs, q.ve && q.vs};
+    const float wt[4] = {q.wnw, q.wne, q.wsw, q.wse};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        v[c] = 0.f;
+        if (!val[c]) continue;
+        const int sx = q.x0 + (c & 1), sy = q.y0 + (c >> 1);
+        float mm, ss;
+        if (box.staged) {
+            const int o = (sy - box.y0) * T::BW + (sx - box.x0);
+            v[c] = s_d[o]; mm = s_m[o];
+            ss = plane_s(cam, sx, sy);
+            atomicAdd(&s_g[o], warp_grad_d2_term(g, wt[c], mm, ss));
+        } else {
+            v[c] = depth_in_1(cam, d2, mask, base, w, sx, sy, &mm, &ss);
+            atomicAdd(gd2 + base + static_cast<int64_t>(sy) * w + sx, warp_grad_d2_term(g, wt[c], mm, ss));
+        }
+    }
+}
+
+// the LDS tile of d2 gradients into global memory: one atomic per touched source pixel
+template <class T>
+__device__ __forceinline__ void flush_source_grad(const SourceBox& box, const float* s_g, float* gd2, int64_t base, int w) {
+    if (!box.staged) return;
+    const int bx0 = box.x0, by0 = box.y0, bh = box.h;
+    __syncthreads();
+    for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
+        const float gsum = s_g[e];
+        if (gsum != 0.f) {
+            const int ry = e / T::BW, rx = e - ry * T::BW;
+            atomicAdd(gd2 + base + static_cast<int64_t>(by0 + ry) * w + bx0 + rx, gsum);
+        }
+    }
+}
+
 template <int TY, int TX>
 __global__ void __launch_bounds__(256) warp_fwd_tiled_kernel(const float* __restrict__ d1, const float* __restrict__ d2,
                                                              const float* __restrict__ mask, const float* __restrict__ t,
@@ -374,70 +527,20 @@ __global__ void __launch_bounds__(256) warp_fwd_tiled_kernel(const float* __rest
     load_camera(K, R, t, n, &cam);
     const int64_t base = static_cast<int64_t>(n) * h * w;
     const int tx0 = (blockIdx.x % tiles_x) * TX, ty0 = (blockIdx.x / tiles_x) * TY;
-    Taps tp[T::kPix];
-    float mpix[T::kPix];
-    int minx = 1 << 30, miny = 1 << 30, maxx = -(1 << 30), maxy = -(1 << 30);
+    WarpPixels<TY, TX> px;
+    const SourceBox box = warp_sample_tile(cam, d1, mask, base, h, w, tx0, ty0, eps, 0, s_box, px);
+    stage_source_tile<T, false>(cam, d2, mask, base, h, w, box, s_d, s_m, nullptr);
 #pragma unroll
     for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        tp[k].vw = tp[k].ve = tp[k].vn = tp[k].vs = false;
-        tp[k].x0 = tp[k].y0 = 0;
-        mpix[k] = 0.f;
-        if (yy < h && xx < w) {
-            float qx, qy, qz;
-            ray(cam, static_cast<float>(xx), static_cast<float>(yy), qx, qy, qz);
-            const float m = mask[base + static_cast<int64_t>(yy) * w + xx];
-            const float dm = d1[base + static_cast<int64_t>(yy) * w + xx] * m;
-            float zt = cam.w[2] + dm * qz;
-            zt = (m > 0.5f) ? zt : eps;
-            zt = (zt > 0.0f) ? zt : eps;
-            tp[k] = make_taps((cam.w[0] + dm * qx) / zt, (cam.w[1] + dm * qy) / zt, w, h);
-            mpix[k] = m;
-            if ((tp[k].vw || tp[k].ve) && (tp[k].vn || tp[k].vs)) {
-                minx = min(minx, tp[k].x0); maxx = max(maxx, tp[k].x0);
-                miny = min(miny, tp[k].y0); maxy = max(maxy, tp[k].y0);
-            }
-        }
-    }
-    int bx0, by0, bw, bh;
-    block_tap_box(minx, miny, maxx, maxy, s_box, bx0, by0, bw, bh);
-    const bool staged = bw <= T::BW && bh <= T::BH && bw > 0;          // block-uniform; bw <= 0: no pixel of the block has a tap in range
-    if (!staged && bw > 0 && threadIdx.x == 0) count_fallback(0);
-    if (staged) {
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const int ry = e / T::BW, rx = e - ry * T::BW;
-            const int sy = by0 + ry, sx = bx0 + rx;
-            float dv = 0.f, mv = 0.f, ss;
-            if (rx < bw && sy >= 0 && sy < h && sx >= 0 && sx < w) dv = depth_in_1(cam, d2, mask, base, w, sx, sy, &mv, &ss);
-            s_d[e] = dv; s_m[e] = mv;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        if (yy >= h || xx >= w) continue;
-        const Taps& q = tp[k];
-        float v[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {0.f, 0.f, 0.f, 0.f}, ss;
-        if (staged) {
-            const int o = (q.y0 - by0) * T::BW + (q.x0 - bx0);
-            if (q.vw && q.vn) { v[0] = s_d[o]; mm[0] = s_m[o]; }
-            if (q.ve && q.vn) { v[1] = s_d[o + 1]; mm[1] = s_m[o + 1]; }
-            if (q.vw && q.vs) { v[2] = s_d[o + T::BW]; mm[2] = s_m[o + T::BW]; }
-            if (q.ve && q.vs) { v[3] = s_d[o + T::BW + 1]; mm[3] = s_m[o + T::BW + 1]; }
-        } else {
-            if (q.vw && q.vn) v[0] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0, &mm[0], &ss);
-            if (q.ve && q.vn) v[1] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0, &mm[1], &ss);
-            if (q.vw && q.vs) v[2] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0 + 1, &mm[2], &ss);
-            if (q.ve && q.vs) v[3] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0 + 1, &mm[3], &ss);
-        }
+        int xx, yy;
+        if (!tile_pixel<TY, TX>(k, tx0, ty0, h, w, xx, yy)) continue;
+        float v[4], mm[4];
+        fetch_taps<T>(cam, d2, mask, base, w, px.tp[k], box, s_d, s_m, v, mm);
         float acc, macc;
-        tap_blend(q, v, mm, acc, macc);
+        tap_blend(px.tp[k], v, mm, acc, macc);
         const int64_t o = base + static_cast<int64_t>(yy) * w + xx;
         warped[o] = acc;
-        intersect[o] = (macc * mpix[k] >= 0.9f) ? 1.0f : 0.0f;
+        intersect[o] = (macc * px.m[k] >= 0.9f) ? 1.0f : 0.0f;
     }
 }
 
@@ -456,87 +559,20 @@ __global__ void __launch_bounds__(256) warp_bwd_tiled_kernel(const float* __rest
     const int64_t base = static_cast<int64_t>(n) * h * w;
     const float fw = static_cast<float>(w), fh = static_cast<float>(h);
     const int tx0 = (blockIdx.x % tiles_x) * TX, ty0 = (blockIdx.x / tiles_x) * TY;
-    Taps tp[T::kPix];
-    float qxs[T::kPix], qys[T::kPix], qzs[T::kPix], zts[T::kPix], nxs[T::kPix], nys[T::kPix], mpix[T::kPix];
-    bool opens[T::kPix];
-    int minx = 1 << 30, miny = 1 << 30, maxx = -(1 << 30), maxy = -(1 << 30);
+    WarpPixels<TY, TX> px;
+    const SourceBox box = warp_sample_tile(cam, d1, mask, base, h, w, tx0, ty0, eps, 1, s_box, px);
+    stage_source_tile<T, true>(cam, d2, mask, base, h, w, box, s_d, s_m, s_g);
 #pragma unroll
     for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        tp[k].vw = tp[k].ve = tp[k].vn = tp[k].vs = false;
-        tp[k].x0 = tp[k].y0 = 0;
-        mpix[k] = 0.f; opens[k] = false;
-        qxs[k] = qys[k] = qzs[k] = nxs[k] = nys[k] = 0.f; zts[k] = 1.f;
-        if (yy < h && xx < w) {
-            ray(cam, static_cast<float>(xx), static_cast<float>(yy), qxs[k], qys[k], qzs[k]);
-            const float m = mask[base + static_cast<int64_t>(yy) * w + xx];
-            const float dm = d1[base + static_cast<int64_t>(yy) * w + xx] * m;
-            const float z2 = cam.w[2] + dm * qzs[k];
-            float zt = (m > 0.5f) ? z2 : eps;
-            opens[k] = (m > 0.5f) && (zt > 0.0f);
-            zt = (zt > 0.0f) ? zt : eps;
-            zts[k] = zt; mpix[k] = m;
-            nxs[k] = cam.w[0] + dm * qxs[k];
-            nys[k] = cam.w[1] + dm * qys[k];
-            tp[k] = make_taps(nxs[k] / zt, nys[k] / zt, w, h);
-            if ((tp[k].vw || tp[k].ve) && (tp[k].vn || tp[k].vs)) {
-                minx = min(minx, tp[k].x0); maxx = max(maxx, tp[k].x0);
-                miny = min(miny, tp[k].y0); maxy = max(maxy, tp[k].y0);
-            }
-        }
+        int xx, yy;
+        if (!tile_pixel<TY, TX>(k, tx0, ty0, h, w, xx, yy)) continue;
+        const int64_t o = base + static_cast<int64_t>(yy) * w + xx;
+        const float g = gw[o];
+        float v[4];
+        scatter_taps<T>(cam, d2, mask, base, w, px.tp[k], box, s_d, s_m, s_g, gd2, g, v);
+        gd1[o] = warp_grad_d1(px.tp[k], v, g, fw, fh, px.qx[k], px.qy[k], px.qz[k], px.zt[k], px.nx[k], px.ny[k], px.open[k], px.m[k]);
     }
-    int bx0, by0, bw, bh;
-    block_tap_box(minx, miny, maxx, maxy, s_box, bx0, by0, bw, bh);
-    const bool staged = bw <= T::BW && bh <= T::BH && bw > 0;
-    if (!staged && bw > 0 && threadIdx.x == 0) count_fallback(1);
-    if (staged) {
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const int ry = e / T::BW, rx = e - ry * T::BW;
-            const int sy = by0 + ry, sx = bx0 + rx;
-            float dv = 0.f, mv = 0.f, ss;
-            if (rx < bw && sy >= 0 && sy < h && sx >= 0 && sx < w) dv = depth_in_1(cam, d2, mask, base, w, sx, sy, &mv, &ss);
-            s_d[e] = dv; s_m[e] = mv; s_g[e] = 0.f;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        if (yy >= h || xx >= w) continue;
-        const Taps& q = tp[k];
-        const float g = gw[base + static_cast<int64_t>(yy) * w + xx];
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool val[4] = {q.vw && q.vn, q.ve && q.vn, q.vw && q.vs, q.ve && q.vs};
-        const float wt[4] = {q.wnw, q.wne, q.wsw, q.wse};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (!val[c]) continue;
-            const int sx = q.x0 + (c & 1), sy = q.y0 + (c >> 1);
-            float mm, ss;
-            if (staged) {
-                const int o = (sy - by0) * T::BW + (sx - bx0);
-                v[c] = s_d[o]; mm = s_m[o];
-                ss = plane_s(cam, sx, sy);
-                atomicAdd(&s_g[o], warp_grad_d2_term(g, wt[c], mm, ss));
-            } else {
-                v[c] = depth_in_1(cam, d2, mask, base, w, sx, sy, &mm, &ss);
-                atomicAdd(gd2 + base + static_cast<int64_t>(sy) * w + sx, warp_grad_d2_term(g, wt[c], mm, ss));
-            }
-        }
-        gd1[base + static_cast<int64_t>(yy) * w + xx] = warp_grad_d1(q, v, g, fw, fh, qxs[k], qys[k], qzs[k], zts[k], nxs[k], nys[k], opens[k], mpix[k]);
-    }
-    if (staged) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const float gsum = s_g[e];
-            if (gsum != 0.f) {
-                const int ry = e / T::BW, rx = e - ry * T::BW;
-                atomicAdd(gd2 + base + static_cast<int64_t>(by0 + ry) * w + bx0 + rx, gsum);
-            }
-        }
-    }
+    flush_source_grad<T>(box, s_g, gd2, base, w);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -544,18 +580,18 @@ __global__ void __launch_bounds__(256) warp_bwd_tiled_kernel(const float* __rest
 // the chain of BASELINE's second metric (endo_warp_consistency, train.py:305-314).  Round 3 composed it from the entry points above:
 // 11 launches, ~100 us per call for 105 MB.  Here gridDim.z = 2 covers the two directions (z = 0: frame 1 warped from frame 2,
 // pose 1-wrt-2; z = 1: the roles swapped):
-//   consistency_fwd_kernel   the tiled warp forward; per pixel the four NormalizedDistanceLoss sums of its sample (block reduction,
-//                            one fp64 atomic per sum and block); it also ZEROES its tile of this direction's own gradient output.
-//                            (The loss is a template parameter, ConsistencyForm below: the reference's three other consistency losses
-//                            are the same pattern with other integrands -- endo_warp_consistency_forms, endo_loss_head_forms.)
+//   consistency_fwd_kernel   the tiled warp forward; per pixel the loss sums of its sample (block reduction, one fp64 atomic per sum
+//                            and block); it also ZEROES its tile of this direction's own gradient output.  The loss is a template
+//                            parameter, a ConsistencyForm of loss_device.h: the reference's four consistency losses.
 //   consistency_finalize_kernel  one wave: the 2 x n x 4 sums -> the loss and the per-sample coefficients (d loss / d numerator,
 //                            d loss / d denominator) the backward kernel needs.
 //   consistency_bwd_kernel   per pixel the loss's gradient w.r.t. its own depth and w.r.t. the warped depth, the latter pushed
 //                            straight through the warp backward of the same pixel (taps recomputed, source tile staged as in the
 //                            forward kernel): its own-pixel terms are ONE atomic add into this direction's gradient, the source terms
 //                            go through the LDS tile into the other direction's gradient.
-// Same arithmetic per term as the kernels above; the three contributions of a gradient element arrive by fp32 atomics in any order
-// (the composed path added them in a fixed order: differences at fp32 rounding, test bound 1e-6).
+// The warp is the tiled kernels' (the helpers above) and the loss the module kernels' (loss_device.h); the three contributions of a
+// gradient element arrive by fp32 atomics in any order (the composed path added them in a fixed order: differences at fp32 rounding,
+// test bound 1e-6).
 // ------------------------------------------------------------------------------------------
 // One cache line per (direction, sample) for the forward kernel's four sums: its 2 560 blocks add them with one 32-byte atomic each, and
 // atomics on one line are served one after the other (~8 ns) -- packed 4 doubles apart, four samples shared a line.
@@ -570,7 +606,7 @@ struct ConsistencyArgs {
     float* warped[2];                // direction z: depth[1 - z] warped into frame z
     float* inter[2];
     float* grad[2];                  // d loss / d depth[z]
-    double* stats;                   // [2][n][kStatStride], the first 4: sum m a, sum m, sum m |P - Pw|_1, sum m (a + |b|)   (zeroed by the caller; the other forms' sums: ConsistencyForm)
+    double* stats;                   // [2][n][kStatStride], the first form_sums(form): the form's sums (zeroed by the caller)
     float* coef;                     // [2][n][2]  (d loss / d numerator, d loss / d denominator) of sample n in direction z
     float* loss;
     float c_dcl;                     // dcl_weight * 0.5
@@ -582,35 +618,21 @@ struct ConsistencyArgs {
     float form_eps;                  // the loss module's eps of the forms other than kFormDistance (which holds its module's 1e-5)
 };
 
-// The loss between a depth map (a), the other frame's warped into it (b) and the intersect mask (m) -- the reference's four consistency
-// losses, each as losses.hip's module kernels write it (norm_dist_*, ratio_reduce<F>, ratio_den<F>, weighted_l2_finalize, ratio_bwd_kernel<F>):
-//   kFormDistance    NormalizedDistanceLoss          (losses.py:112-146)  sums  m a, m, m |P - Pw|_1, m (a + |b|)
-//   kFormL2          NormalizedL2Loss                (losses.py:94-109)   sums  m a, m, m (a-b)^2, m (a^2+b^2);  den = 0.5 s3 + 1e-5 mu^2, mu constant
-//   kFormL1          NormalizedL1Loss                (losses.py:149-164)  sums  m a, m, m |a-b|, m (|a|+|b|);     den = 0.5 s3 + 1e-5 mu, mu differentiated
-//   kFormWeightedL2  NormalizedWeightedMaskedL2Loss  (losses.py:35-54)    sums  m (a-b)^2, m (a^2+b^2);           den = 0.5 s1 + eps,
-//                    batch value sum_n w_n term_n / sum_n w_n with w_n = 1 / (1e-8 + |t_n|) of the direction's translations
-// The forms other than kFormDistance always run the finalize kernel: it leaves (d loss / d num, d loss / d den) of every (direction,
-// sample) in `coef` -- for the weighted form that takes the whole batch's weights, which no block of the backward kernel should re-add.
-enum ConsistencyForm { kFormDistance = 0, kFormL2 = 1, kFormL1 = 2, kFormWeightedL2 = 3 };
-constexpr int kFormCount = 4;
+__device__ __forceinline__ float consistency_eps(int form, const ConsistencyArgs& a) { return (form == kFormDistance) ? 1.0e-5f : a.form_eps; }
 
-// The intrinsics the distance form's pixel rays need (ax = (x - cx) / fx, ay likewise), loaded once per block; the other forms hold nothing.
-template <int F>
-struct RayIntrinsics {
-    __device__ RayIntrinsics(const float*, int) {}
-};
-template <>
-struct RayIntrinsics<kFormDistance> {
-    float fx, fy, cx, cy;
-    __device__ RayIntrinsics(const float* K, int n) : fx(K[9 * n + 0]), fy(K[9 * n + 4]), cx(K[9 * n + 2]), cy(K[9 * n + 5]) {}
-};
-
-__device__ __forceinline__ float translation_weight(const float* __restrict__ t, int i) {
-    const float tx = t[3 * i], ty = t[3 * i + 1], tz = t[3 * i + 2];
-    return 1.0f / (1.0e-8f + sqrtf(tx * tx + ty * ty + tz * tz));
+// One wave, the forms whose batch value is the plain mean: the loss from the 2 x n sums.  Lane i < 2 n owns (direction, sample) i, a
+// wave reduction adds the terms (n <= 32; larger batches loop).  coefs: also every (direction, sample)'s backward coefficients.
+__device__ __forceinline__ void consistency_mean_loss(int form, const ConsistencyArgs& a, bool coefs) {
+    float term = 0.f;
+    for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
+        const double* st = a.stats + kStatStride * i;
+        const float num = static_cast<float>(st[2]), den = form_den(form, st, consistency_eps(form, a));
+        term += form_term(form, num, den);
+        if (coefs) form_coefs(form, a.c_dcl / static_cast<float>(a.n), num, den, a.coef[2 * i], a.coef[2 * i + 1]);
+    }
+    term = wave_sum(term);
+    if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
 }
-
-__device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
 template <int TY, int TX, int F>
 __global__ void __launch_bounds__(256) consistency_fwd_kernel(const ConsistencyArgs a) {
@@ -627,164 +649,58 @@ __global__ void __launch_bounds__(256) consistency_fwd_kernel(const ConsistencyA
     load_camera(a.K, a.R[z], a.t[z], n, &cam);
     const int64_t base = static_cast<int64_t>(n) * h * w;
     const int tx0 = (blockIdx.x % a.tiles_x) * TX, ty0 = (blockIdx.x / a.tiles_x) * TY;
-    Taps tp[T::kPix];
-    float mpix[T::kPix], dself[T::kPix];
-    int minx = 1 << 30, miny = 1 << 30, maxx = -(1 << 30), maxy = -(1 << 30);
-#pragma unroll
-    for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        tp[k].vw = tp[k].ve = tp[k].vn = tp[k].vs = false;
-        tp[k].x0 = tp[k].y0 = 0;
-        mpix[k] = 0.f; dself[k] = 0.f;
-        if (yy < h && xx < w) {
-            float qx, qy, qz;
-            ray(cam, static_cast<float>(xx), static_cast<float>(yy), qx, qy, qz);
-            const float m = mask[base + static_cast<int64_t>(yy) * w + xx];
-            dself[k] = d1[base + static_cast<int64_t>(yy) * w + xx];
-            const float dm = dself[k] * m;
-            float zt = cam.w[2] + dm * qz;
-            zt = (m > 0.5f) ? zt : a.eps;
-            zt = (zt > 0.0f) ? zt : a.eps;
-            tp[k] = make_taps((cam.w[0] + dm * qx) / zt, (cam.w[1] + dm * qy) / zt, w, h);
-            mpix[k] = m;
-            if ((tp[k].vw || tp[k].ve) && (tp[k].vn || tp[k].vs)) {
-                minx = min(minx, tp[k].x0); maxx = max(maxx, tp[k].x0);
-                miny = min(miny, tp[k].y0); maxy = max(maxy, tp[k].y0);
-            }
-        }
-    }
-    int bx0, by0, bw, bh;
-    block_tap_box(minx, miny, maxx, maxy, s_box, bx0, by0, bw, bh);
-    const bool staged = bw <= T::BW && bh <= T::BH && bw > 0;
-    if (!staged && bw > 0 && threadIdx.x == 0) count_fallback(0);
-    if (staged) {
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const int ry = e / T::BW, rx = e - ry * T::BW;
-            const int sy = by0 + ry, sx = bx0 + rx;
-            float dv = 0.f, mv = 0.f, ss;
-            if (rx < bw && sy >= 0 && sy < h && sx >= 0 && sx < w) dv = depth_in_1(cam, d2, mask, base, w, sx, sy, &mv, &ss);
-            s_d[e] = dv; s_m[e] = mv;
-        }
-        __syncthreads();
-    }
-    constexpr int kSums = (F == kFormWeightedL2) ? 2 : 4;
+    WarpPixels<TY, TX> px;
+    const SourceBox box = warp_sample_tile(cam, d1, mask, base, h, w, tx0, ty0, a.eps, 0, s_box, px);
+    stage_source_tile<T, false>(cam, d2, mask, base, h, w, box, s_d, s_m, nullptr);
     const RayIntrinsics<F> k9(a.K, n);
-    float part[kSums];
+    float part[form_sums(F)];
 #pragma unroll
-    for (int k = 0; k < kSums; ++k) part[k] = 0.f;
+    for (int k = 0; k < form_sums(F); ++k) part[k] = 0.f;
 #pragma unroll
     for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        if (yy >= h || xx >= w) continue;
-        const Taps& q = tp[k];
-        float v[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {0.f, 0.f, 0.f, 0.f}, ss;
-        if (staged) {
-            const int o = (q.y0 - by0) * T::BW + (q.x0 - bx0);
-            if (q.vw && q.vn) { v[0] = s_d[o]; mm[0] = s_m[o]; }
-            if (q.ve && q.vn) { v[1] = s_d[o + 1]; mm[1] = s_m[o + 1]; }
-            if (q.vw && q.vs) { v[2] = s_d[o + T::BW]; mm[2] = s_m[o + T::BW]; }
-            if (q.ve && q.vs) { v[3] = s_d[o + T::BW + 1]; mm[3] = s_m[o + T::BW + 1]; }
-        } else {
-            if (q.vw && q.vn) v[0] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0, &mm[0], &ss);
-            if (q.ve && q.vn) v[1] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0, &mm[1], &ss);
-            if (q.vw && q.vs) v[2] = depth_in_1(cam, d2, mask, base, w, q.x0, q.y0 + 1, &mm[2], &ss);
-            if (q.ve && q.vs) v[3] = depth_in_1(cam, d2, mask, base, w, q.x0 + 1, q.y0 + 1, &mm[3], &ss);
-        }
+        int xx, yy;
+        if (!tile_pixel<TY, TX>(k, tx0, ty0, h, w, xx, yy)) continue;
+        float v[4], mm[4];
+        fetch_taps<T>(cam, d2, mask, base, w, px.tp[k], box, s_d, s_m, v, mm);
         float acc, macc;
-        tap_blend(q, v, mm, acc, macc);
+        tap_blend(px.tp[k], v, mm, acc, macc);
         const int64_t o = base + static_cast<int64_t>(yy) * w + xx;
-        const float mi = (macc * mpix[k] >= 0.9f) ? 1.0f : 0.0f;
+        const float mi = (macc * px.m[k] >= 0.9f) ? 1.0f : 0.0f;
         a.warped[z][o] = acc;
         a.inter[z][o] = mi;
         if (a.zero_grads) a.grad[z][o] = 0.f;          // the backward kernel accumulates into it
-        const float av = dself[k], b = acc;          // a = own depth, b = warped depth
-        if constexpr (F == kFormDistance) {
-            // NormalizedDistanceLoss sums (norm_dist_reduce, losses.hip)
-            const float fx = k9.fx, fy = k9.fy, cx = k9.cx, cy = k9.cy;
-            const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
-            part[0] += mi * av;
-            part[1] += mi;
-            part[2] += mi * fabsf(ax * av - ax * b) + mi * fabsf(ay * av - ay * b) + mi * fabsf(av - b);
-            part[3] += mi * (av + fabsf(b));
-        } else if constexpr (F == kFormWeightedL2) {
-            // ratio_reduce<kWeightedL2> (losses.hip)
-            part[0] += mi * (av - b) * (av - b);
-            part[1] += mi * (av * av + b * b);
-        } else {
-            // ratio_reduce<kNormL2 / kNormL1> (losses.hip)
-            part[0] += mi * av;
-            part[1] += mi;
-            part[2] += (F == kFormL2) ? mi * (av - b) * (av - b) : mi * fabsf(av - b);
-            part[3] += (F == kFormL2) ? mi * (av * av + b * b) : mi * (fabsf(av) + fabsf(b));
-        }
+        form_accumulate(F, mi, px.dself[k], acc, k9.ax(xx), k9.ay(yy), part);          // a = own depth, b = warped depth
     }
-    block_sum_atomic<kSums>(part, a.stats + kStatStride * (z * a.n + n), scratch);
+    block_sum_atomic<form_sums(F)>(part, a.stats + kStatStride * (z * a.n + n), scratch);
 }
 
 // loss and the backward pass's per-sample coefficients from the 2 x n x 4 sums.  A kernel of its own, one wave: the "last block of the
 // forward kernel finalises" form needs a device-scope fence in every block, which on this part writes back and invalidates the XCD's L2
 // -- 2560 blocks of it made the forward kernel 222 us instead of ~15 (profiles/r04_warp_consistency_kernel_stats.txt history).
 __global__ void consistency_finalize_kernel(const ConsistencyArgs a) {
-    if (a.form == kFormWeightedL2) {
-        // ratio_den<kWeightedL2> and weighted_l2_finalize (losses.hip) per direction: the weights of the direction's translations, their
-        // sum over the batch (lanes stride over the samples, a wave reduction adds), then per (direction, sample) the term and the
-        // coefficients under the upstream factor w_n / sum w
-        float wsum[2], acc[2] = {0.f, 0.f};
-        for (int z = 0; z < 2; ++z) {
-            float part = 0.f;
-            for (int i = threadIdx.x; i < a.n; i += 64) part += translation_weight(a.t[z], i);
-            wsum[z] = __shfl(wave_sum(part), 0, 64);
-        }
-        for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
-            const int z = i / a.n;
-            const double* st = a.stats + kStatStride * i;
-            const float num = static_cast<float>(st[0]);
-            const float den = 0.5f * static_cast<float>(st[1]) + a.form_eps;
-            const float wgt = translation_weight(a.t[z], i - z * a.n);
-            acc[z] += num / den * wgt;
-            const float g = a.c_dcl * wgt / wsum[z];                      // d loss / d (this sample's term)
-            a.coef[2 * i] = g / den;
-            a.coef[2 * i + 1] = -g * num / (den * den);
-        }
-        acc[0] = wave_sum(acc[0]);
-        acc[1] = wave_sum(acc[1]);
-        if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (acc[0] / wsum[0] + acc[1] / wsum[1]);
+    if (a.form != kFormWeightedL2) {
+        consistency_mean_loss(a.form, a, true);
         return;
     }
-    if (a.form == kFormL2 || a.form == kFormL1) {
-        // ratio_den<kNormL2 / kNormL1> and norm_ratio_finalize (losses.hip); the L1 form's third constant, d (1e-5 mu) / d a, is
-        // re-formed from the sums by the backward kernel
-        float term = 0.f;
-        for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
-            const double* st = a.stats + kStatStride * i;
-            const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
-            const float mean_value = s0 / (a.form_eps + s1);
-            const float den = 0.5f * s3 + ((a.form == kFormL2) ? 1.0e-5f * mean_value * mean_value : 1.0e-5f * mean_value);
-            term += s2 / den;
-            const float g = a.c_dcl / static_cast<float>(a.n);
-            a.coef[2 * i] = g / den;
-            a.coef[2 * i + 1] = -g * s2 / (den * den);
-        }
-        term = wave_sum(term);
-        if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
-        return;
+    // per direction: the weights of the direction's translations, their sum over the batch (lanes stride over the samples, a wave
+    // reduction adds), then per (direction, sample) the term and the coefficients under the upstream factor w_n / sum w
+    float wsum[2], acc[2] = {0.f, 0.f};
+    for (int z = 0; z < 2; ++z) {
+        float part = 0.f;
+        for (int i = threadIdx.x; i < a.n; i += 64) part += translation_weight(a.t[z], i);
+        wsum[z] = __shfl(wave_sum(part), 0, 64);
     }
-    // lane i < 2 n owns (direction, sample) i: its term and coefficients; a wave reduction adds the terms (n <= 32; larger batches loop)
-    float term = 0.f;
     for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
+        const int z = i / a.n;
         const double* st = a.stats + kStatStride * i;
-        const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
-        const float mean_value = s0 / (1.0e-5f + s1);                  // norm_dist_den (losses.hip) with the module's eps
-        const float den = 1.0e-5f * mean_value + s3;
-        term += 2.0f * s2 / den;
-        const float g = a.c_dcl / static_cast<float>(a.n);             // d loss / d (this sample's term)
-        a.coef[2 * i] = 2.0f * g / den;
-        a.coef[2 * i + 1] = -2.0f * g * s2 / (den * den);
+        const float num = static_cast<float>(st[0]), den = form_den(kFormWeightedL2, st, a.form_eps);
+        const float wgt = translation_weight(a.t[z], i - z * a.n);
+        acc[z] += form_term(kFormWeightedL2, num, den) * wgt;
+        form_coefs(kFormWeightedL2, a.c_dcl * wgt / wsum[z], num, den, a.coef[2 * i], a.coef[2 * i + 1]);
     }
-    term = wave_sum(term);
-    if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
+    acc[0] = wave_sum(acc[0]);
+    acc[1] = wave_sum(acc[1]);
+    if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (acc[0] / wsum[0] + acc[1] / wsum[1]);
 }
 
 template <int TY, int TX, int F>
@@ -804,102 +720,42 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
     const int64_t base = static_cast<int64_t>(n) * h * w;
     const float fw = static_cast<float>(w), fh = static_cast<float>(h);
     const int tx0 = (blockIdx.x % a.tiles_x) * TX, ty0 = (blockIdx.x / a.tiles_x) * TY;
-    // this sample's coefficients from the forward kernel's sums (consistency_finalize_kernel's arithmetic; the stand-alone call skips
-    // that kernel and block (0, 0, 0) writes the loss here)
-    float cnum, cden, cmean = 0.f;
-    if constexpr (F != kFormDistance) {
-        // the finalize kernel's coefficients; L1: d (1e-5 mu) / d a per masked pixel (ratio_bwd_kernel's cmean, losses.hip)
+    // this sample's coefficients: the finalize kernel's, or -- the stand-alone call of the distance form skips that kernel -- formed
+    // here from the forward kernel's sums, and block (0, 0, 0) writes the loss
+    const double* st = a.stats + kStatStride * (z * a.n + n);
+    float cnum, cden;
+    if constexpr (F == kFormDistance) {
+        form_coefs(F, a.c_dcl / static_cast<float>(a.n), static_cast<float>(st[2]), form_den(F, st, consistency_eps(F, a)), cnum, cden);
+        if (a.loss_in_bwd && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) consistency_mean_loss(F, a, false);
+    } else {
         cnum = a.coef[2 * (z * a.n + n)];
         cden = a.coef[2 * (z * a.n + n) + 1];
-        if constexpr (F == kFormL1) cmean = 1.0e-5f / (a.form_eps + static_cast<float>(a.stats[kStatStride * (z * a.n + n) + 1]));
-    } else {
-        const double* st = a.stats + kStatStride * (z * a.n + n);
-        const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
-        const float den = 1.0e-5f * (s0 / (1.0e-5f + s1)) + s3;
-        const float g = a.c_dcl / static_cast<float>(a.n);
-        cnum = 2.0f * g / den;
-        cden = -2.0f * g * s2 / (den * den);
     }
-    if (F == kFormDistance && a.loss_in_bwd && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) {
-        float term = 0.f;
-        for (int i = threadIdx.x; i < 2 * a.n; i += 64) {
-            const double* st = a.stats + kStatStride * i;
-            const float s0 = static_cast<float>(st[0]), s1 = static_cast<float>(st[1]), s2 = static_cast<float>(st[2]), s3 = static_cast<float>(st[3]);
-            term += 2.0f * s2 / (1.0e-5f * (s0 / (1.0e-5f + s1)) + s3);
-        }
-        term = wave_sum(term);
-        if (threadIdx.x == 0) a.loss[0] = a.c_dcl * (term / static_cast<float>(a.n));
-    }
+    const float cmean = form_cmean(F, st, a.form_eps);
     const RayIntrinsics<F> k9(a.K, n);
-    Taps tp[T::kPix];
-    float qxs[T::kPix], qys[T::kPix], qzs[T::kPix], zts[T::kPix], nxs[T::kPix], nys[T::kPix], mpix[T::kPix], dself[T::kPix];
-    bool opens[T::kPix];
-    int minx = 1 << 30, miny = 1 << 30, maxx = -(1 << 30), maxy = -(1 << 30);
+    WarpPixels<TY, TX> px;
+    const SourceBox box = warp_sample_tile(cam, d1, mask, base, h, w, tx0, ty0, a.eps, 1, s_box, px);
+    stage_source_tile<T, true>(cam, d2, mask, base, h, w, box, s_d, s_m, s_g);
 #pragma unroll
     for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        tp[k].vw = tp[k].ve = tp[k].vn = tp[k].vs = false;
-        tp[k].x0 = tp[k].y0 = 0;
-        mpix[k] = 0.f; opens[k] = false; dself[k] = 0.f;
-        qxs[k] = qys[k] = qzs[k] = nxs[k] = nys[k] = 0.f; zts[k] = 1.f;
-        if (yy < h && xx < w) {
-            ray(cam, static_cast<float>(xx), static_cast<float>(yy), qxs[k], qys[k], qzs[k]);
-            const float m = mask[base + static_cast<int64_t>(yy) * w + xx];
-            dself[k] = d1[base + static_cast<int64_t>(yy) * w + xx];
-            const float dm = dself[k] * m;
-            const float z2 = cam.w[2] + dm * qzs[k];
-            float zt = (m > 0.5f) ? z2 : a.eps;
-            opens[k] = (m > 0.5f) && (zt > 0.0f);
-            zt = (zt > 0.0f) ? zt : a.eps;
-            zts[k] = zt; mpix[k] = m;
-            nxs[k] = cam.w[0] + dm * qxs[k];
-            nys[k] = cam.w[1] + dm * qys[k];
-            tp[k] = make_taps(nxs[k] / zt, nys[k] / zt, w, h);
-            if ((tp[k].vw || tp[k].ve) && (tp[k].vn || tp[k].vs)) {
-                minx = min(minx, tp[k].x0); maxx = max(maxx, tp[k].x0);
-                miny = min(miny, tp[k].y0); maxy = max(maxy, tp[k].y0);
-            }
-        }
-    }
-    int bx0, by0, bw, bh;
-    block_tap_box(minx, miny, maxx, maxy, s_box, bx0, by0, bw, bh);
-    const bool staged = bw <= T::BW && bh <= T::BH && bw > 0;
-    if (!staged && bw > 0 && threadIdx.x == 0) count_fallback(1);
-    if (staged) {
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const int ry = e / T::BW, rx = e - ry * T::BW;
-            const int sy = by0 + ry, sx = bx0 + rx;
-            float dv = 0.f, mv = 0.f, ss;
-            if (rx < bw && sy >= 0 && sy < h && sx >= 0 && sx < w) dv = depth_in_1(cam, d2, mask, base, w, sx, sy, &mv, &ss);
-            s_d[e] = dv; s_m[e] = mv; s_g[e] = 0.f;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < T::kPix; ++k) {
-        const int idx = threadIdx.x + k * T::kThreads;
-        const int yy = ty0 + idx / TX, xx = tx0 + idx % TX;
-        if (yy >= h || xx >= w) continue;
-        const Taps& q = tp[k];
+        int xx, yy;
+        if (!tile_pixel<TY, TX>(k, tx0, ty0, h, w, xx, yy)) continue;
         const int64_t o = base + static_cast<int64_t>(yy) * w + xx;
-        // the loss's gradient at this pixel: a = own depth, b = warped depth, m = intersection mask
-        const float mi = a.inter[z][o], av = dself[k], b = a.warped[z][o];
-        float g_own, g;          // d loss / d own depth; d loss / d warped: the warp backward's incoming gradient
+        // the loss's gradient at this pixel (a = own depth, b = warped depth, m = intersection mask): d loss / d own depth, and
+        // d loss / d warped -- the warp backward's incoming gradient
+        const float mi = a.inter[z][o], av = px.dself[k], b = a.warped[z][o];
+        float g_own, g;          // norm_dist_bwd_kernel's / ratio_bwd_kernel<F>'s per-pixel pair (losses.hip: why it is written twice)
         if constexpr (F == kFormDistance) {
-            // norm_dist_bwd_kernel (losses.hip)
-            const float fx = k9.fx, fy = k9.fy, cx = k9.cx, cy = k9.cy;
-            const float ax = (static_cast<float>(xx) - cx) / fx, ay = (static_cast<float>(yy) - cy) / fy;
-            const float tt = ax * sgnf(ax * av - ax * b) + ay * sgnf(ay * av - ay * b) + sgnf(av - b);
+            const float ax = k9.ax(xx), ay = k9.ay(yy);
+            const float tt = ax * sgn(ax * av - ax * b) + ay * sgn(ay * av - ay * b) + sgn(av - b);
             g_own = mi * (cnum * tt + cden);
-            g = mi * (-cnum * tt + cden * sgnf(b));
+            g = mi * (-cnum * tt + cden * sgn(b));
         } else {
-            // ratio_bwd_kernel<F> (losses.hip): d num / d a (= -d num / d b), d den / d a, d den / d b, each per unit of mask
-            float ta, da, db;
+            float ta, da, db;          // d num / d a (= -d num / d b), d den / d a, d den / d b, each per unit of mask
             if constexpr (F == kFormL1) {
-                ta = sgnf(av - b);
-                da = 0.5f * sgnf(av) + cmean;
-                db = 0.5f * sgnf(b);
+                ta = sgn(av - b);
+                da = 0.5f * sgn(av) + cmean;
+                db = 0.5f * sgn(b);
             } else {
                 ta = 2.0f * (av - b);
                 da = av;
@@ -908,36 +764,11 @@ __global__ void __launch_bounds__(256) consistency_bwd_kernel(const ConsistencyA
             g_own = mi * (cnum * ta + cden * da);
             g = mi * (cnum * -ta + cden * db);
         }
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool val[4] = {q.vw && q.vn, q.ve && q.vn, q.vw && q.vs, q.ve && q.vs};
-        const float wt[4] = {q.wnw, q.wne, q.wsw, q.wse};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (!val[c]) continue;
-            const int sx = q.x0 + (c & 1), sy = q.y0 + (c >> 1);
-            float mm, ss;
-            if (staged) {
-                const int oo = (sy - by0) * T::BW + (sx - bx0);
-                v[c] = s_d[oo]; mm = s_m[oo];
-                ss = plane_s(cam, sx, sy);
-                atomicAdd(&s_g[oo], warp_grad_d2_term(g, wt[c], mm, ss));
-            } else {
-                v[c] = depth_in_1(cam, d2, mask, base, w, sx, sy, &mm, &ss);
-                atomicAdd(gd2 + base + static_cast<int64_t>(sy) * w + sx, warp_grad_d2_term(g, wt[c], mm, ss));
-            }
-        }
-        atomicAdd(gd1 + o, g_own + warp_grad_d1(q, v, g, fw, fh, qxs[k], qys[k], qzs[k], zts[k], nxs[k], nys[k], opens[k], mpix[k]));
+        float v[4];
+        scatter_taps<T>(cam, d2, mask, base, w, px.tp[k], box, s_d, s_m, s_g, gd2, g, v);
+        atomicAdd(gd1 + o, g_own + warp_grad_d1(px.tp[k], v, g, fw, fh, px.qx[k], px.qy[k], px.qz[k], px.zt[k], px.nx[k], px.ny[k], px.open[k], px.m[k]));
     }
-    if (staged) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < bh * T::BW; e += T::kThreads) {
-            const float gsum = s_g[e];
-            if (gsum != 0.f) {
-                const int ry = e / T::BW, rx = e - ry * T::BW;
-                atomicAdd(gd2 + base + static_cast<int64_t>(by0 + ry) * w + bx0 + rx, gsum);
-            }
-        }
-    }
+    flush_source_grad<T>(box, s_g, gd2, base, w);
 }
 
 __global__ void __launch_bounds__(256) mask_mul_kernel(const float* __restrict__ a, const float* __restrict__ mask,
@@ -1111,10 +942,33 @@ extern "C" int endo_mask_mul(const float* a, const float* mask, float* out, int 
 }
 
 // Depth warp both ways + depth-consistency loss, forward and backward (include/endo_hip.h): one small memset and two kernels.
+// The carving of its workspace (offsets in floats), the one statement of it; every piece starts on a 4-float boundary.
+struct ConsistencyLayout {
+    int64_t warped[2], inter[2];         // direction z's warped depth and intersect mask: n x h x w each
+    int64_t sums, sums_floats;           // the forward kernel's sums (doubles), zeroed per call
+    int64_t coef;                        // the finalize kernel's coefficients
+    int64_t end;
+    int64_t floats;                      // what endo_warp_consistency_workspace_floats asks for: the carving with room to spare
+};
+
+static ConsistencyLayout consistency_layout(int n, int h, int w) {
+    const int64_t p = static_cast<int64_t>(n) * h * w;
+    int64_t at = 0;
+    auto take = [&](int64_t count) { const int64_t q = at; at += (count + 3) / 4 * 4; return q; };
+    ConsistencyLayout l;
+    l.warped[0] = take(p); l.warped[1] = take(p);
+    l.inter[0] = take(p);  l.inter[1] = take(p);
+    l.sums_floats = 2 * 2 * kStatStride * n;
+    l.sums = take(l.sums_floats);
+    l.coef = take(4 * n);
+    l.end = at;
+    l.floats = 4 * (p + 3) + (4 * kStatStride + 16) * n + 64;
+    return l;
+}
+
 extern "C" int64_t endo_warp_consistency_workspace_floats(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return -1;
-    const int64_t p = static_cast<int64_t>(n) * h * w;
-    return 4 * (p + 3) + (4 * kStatStride + 16) * n + 64;
+    return consistency_layout(n, h, w).floats;
 }
 
 // Algorithmic HBM bytes of one endo_warp_consistency call, as SURVEY.md 8(d) counts the chain per pixel and frame pair, both directions:
@@ -1133,20 +987,17 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
                            float eps, float* loss, float* grad_depth_1, float* grad_depth_2, float* workspace, int n, int h, int w,
                            int zero_grads, int form, float form_eps, hipStream_t stream) {
     if (form < 0 || form >= kFormCount) return ENDO_E_BADARG;
-    const int64_t p = static_cast<int64_t>(n) * h * w;
-    float* ws = workspace;
-    auto take = [&](int64_t count) { float* q = ws; ws += (count + 3) / 4 * 4; return q; };
+    const ConsistencyLayout l = consistency_layout(n, h, w);
     ConsistencyArgs a{};
     a.depth[0] = depth_1; a.depth[1] = depth_2;
     a.t[0] = t_1_wrt_2; a.t[1] = t_2_wrt_1;
     a.R[0] = r_1_wrt_2; a.R[1] = r_2_wrt_1;
     a.K = intrinsics; a.mask = boundaries;
-    a.warped[0] = take(p); a.warped[1] = take(p);
-    a.inter[0] = take(p); a.inter[1] = take(p);
+    a.warped[0] = workspace + l.warped[0]; a.warped[1] = workspace + l.warped[1];
+    a.inter[0] = workspace + l.inter[0]; a.inter[1] = workspace + l.inter[1];
     a.grad[0] = grad_depth_1; a.grad[1] = grad_depth_2;
-    float* zeroed = take(2 * 2 * kStatStride * n);          // the sums (doubles), zeroed per call; the coefficients are written by the finalize kernel
-    a.stats = reinterpret_cast<double*>(zeroed);
-    a.coef = take(4 * n);
+    a.stats = reinterpret_cast<double*>(workspace + l.sums);
+    a.coef = workspace + l.coef;
     a.loss = loss;
     a.c_dcl = static_cast<float>(static_cast<double>(dcl_weight) * 0.5);
     a.eps = eps;
@@ -1160,7 +1011,7 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
     const int tiles_y = (h + TY - 1) / TY;
     const dim3 grid(a.tiles_x * tiles_y, n, 2);
     if (phase == 1) {
-        ENDO_CHECK(hipMemsetAsync(zeroed, 0, sizeof(float) * (2 * 2 * kStatStride * n), stream));
+        ENDO_CHECK(hipMemsetAsync(a.stats, 0, sizeof(float) * l.sums_floats, stream));
         switch (form) {
             case kFormDistance: consistency_fwd_kernel<TY, TX, kFormDistance><<<grid, 256, 0, stream>>>(a); break;
             case kFormL2: consistency_fwd_kernel<TY, TX, kFormL2><<<grid, 256, 0, stream>>>(a); break;
@@ -1180,11 +1031,10 @@ int endo_consistency_phase(int phase, const float* depth_1, const float* depth_2
     return 0;
 }
 
-// the third and fourth piece of the carving above
 void endo_consistency_intersect_planes(float* workspace, int n, int h, int w, float** inter_1, float** inter_2) {
-    const int64_t piece = (static_cast<int64_t>(n) * h * w + 3) / 4 * 4;
-    *inter_1 = workspace + 2 * piece;
-    *inter_2 = workspace + 3 * piece;
+    const ConsistencyLayout l = consistency_layout(n, h, w);
+    *inter_1 = workspace + l.inter[0];
+    *inter_2 = workspace + l.inter[1];
 }
 
 static int warp_consistency_impl(const float* depth_1, const float* depth_2, const float* boundaries, const float* t_1_wrt_2,

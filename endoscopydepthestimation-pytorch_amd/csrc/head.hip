@@ -8,6 +8,7 @@
 // endo_loss_head_photo is the same body with the photometric term (image_warp.hip) in both directions: three launches more.
 // endo_loss_head_forms is either of the two with the depth-consistency loss chosen (geometry.hip ConsistencyForm): the same launches.
 #include "common.h"
+#include "loss_device.h"
 
 namespace endo {
 
@@ -70,7 +71,7 @@ __global__ void head_combine_kernel(const float* __restrict__ parts, float c_sfl
 }
 
 // head_combine_kernel with the photometric term: the two directions' terms from their reduction tables ([2][n][2] doubles:
-// photometric_fwd_kernel's sums, image_warp.hip) as photometric_finalize_kernel forms them, losses[4] = c_photo * (term_1 + term_2)
+// photometric_fwd_kernel's sums, image_warp.hip) by loss_device.h's masked_l1_mean, losses[4] = c_photo * (term_1 + term_2)
 // added to the total before the non-finite test; up[2] = d total / d (each photometric term)
 __global__ void head_combine_photo_kernel(const float* __restrict__ parts, float c_sfl, const float* __restrict__ dcl_weighted,
                                           const double* __restrict__ photo_stats, int n, float photo_eps, float c_photo,
@@ -78,14 +79,7 @@ __global__ void head_combine_photo_kernel(const float* __restrict__ parts, float
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         const float sfl = c_sfl * (parts[0] + parts[1]);
         const float dcl = dcl_weighted[0];
-        float term[2];
-        for (int z = 0; z < 2; ++z) {
-            float acc = 0.f;
-            for (int i = 0; i < n; ++i)
-                acc += static_cast<float>(photo_stats[2 * (z * n + i)]) / (photo_eps + static_cast<float>(photo_stats[2 * (z * n + i) + 1]));
-            term[z] = acc / static_cast<float>(n);
-        }
-        const float photo = c_photo * (term[0] + term[1]);
+        const float photo = c_photo * (masked_l1_mean(photo_stats, n, photo_eps) + masked_l1_mean(photo_stats + 2 * n, n, photo_eps));
         const float total = dcl + sfl + photo;
         losses[0] = total;
         losses[1] = dcl;

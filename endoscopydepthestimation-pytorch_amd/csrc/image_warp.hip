@@ -8,6 +8,7 @@
 // kernel that share the helpers above; its workspace is one plane.
 #include "common.h"
 #include "geometry_device.h"
+#include "loss_device.h"
 
 #include <float.h>
 #include <limits.h>
@@ -244,8 +245,6 @@ struct PhotoArgs {
 
 constexpr int kPhotoItems = 4;          // pixels per thread of the forward kernel (its grid; the kernel itself is grid-stride)
 
-__device__ __forceinline__ float photo_sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
-
 __global__ void __launch_bounds__(256) photometric_fwd_kernel(const PhotoArgs a) {
     __shared__ Camera cam;
     __shared__ double scratch[2 * 4];
@@ -288,7 +287,7 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const PhotoArgs a)
             acc = fmaf(tp.wse, s[3], acc);
             const float diff = c1[ibase + static_cast<int64_t>(ch) * hw + i] - acc;
             num += mi * fabsf(diff);
-            const float g = -(photo_sgn(diff) * mi);          // d (m |c1 - warped|) / d warped
+            const float g = -(sgn(diff) * mi);          // d (m |c1 - warped|) / d warped
             gix = fmaf(fmaf(s[3] - s[2], tp.fy, (s[1] - s[0]) * sfrac), g, gix);
             giy = fmaf(fmaf(s[3] - s[1], tp.fx, (s[2] - s[0]) * efrac), g, giy);
         }
@@ -309,12 +308,10 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const PhotoArgs a)
     block_sum_atomic<2>(part, a.stats + 2 * (static_cast<int64_t>(z) * a.n + n), scratch);
 }
 
-// loss = mean_n num_n / (eps + den_n)  (sparse_l1_finalize's form)
+// loss = mean_n num_n / (eps + den_n)
 __global__ void photometric_finalize_kernel(const double* stats, float* loss, int n, float eps) {
     if (threadIdx.x != 0) return;
-    float acc = 0.f;
-    for (int i = 0; i < n; ++i) acc += static_cast<float>(stats[2 * i]) / (eps + static_cast<float>(stats[2 * i + 1]));
-    *loss = acc / static_cast<float>(n);
+    *loss = masked_l1_mean(stats, n, eps);
 }
 
 // grad_depth = upstream / N / (eps + den_n) * plane: one writer per element, no atomics; accumulate adds to what is there
@@ -323,7 +320,7 @@ __global__ void __launch_bounds__(256) photometric_bwd_kernel(const PhotoArgs a)
     const float* __restrict__ plane = z ? a.plane[1] : a.plane[0];
     float* __restrict__ grad = z ? a.grad[1] : a.grad[0];
     const float up = *(z ? a.upstream[1] : a.upstream[0]);
-    const float coef = up / static_cast<float>(a.n) / (a.eps + static_cast<float>(a.stats[2 * (static_cast<int64_t>(z) * a.n + n) + 1]));
+    const float coef = masked_l1_coef(up / static_cast<float>(a.n), a.stats + 2 * (static_cast<int64_t>(z) * a.n + n), a.eps);
     const int hw = a.h * a.w;
     const int64_t base = static_cast<int64_t>(n) * hw;
     if (a.accumulate) {          // the product rounded, then added: what accumulate = 0 writes, plus what was there (no fused multiply-add)
