@@ -71,6 +71,9 @@ SIGNATURES = {
     "endo_bf16_conv_weight_elems": (_L, [_I, _I, _I]),
     "endo_bf16_conv_weights": (_I, [_P, _I, _I, _I, _P, _P]),
     "endo_bf16_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "endo_f16_conv_weight_elems": (_L, [_I, _I, _I]),
+    "endo_f16_conv_weights": (_I, [_P, _I, _I, _I, _P, _P]),
+    "endo_f16_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "endo_net16_create": (_I, [ctypes.POINTER(_P), _I, _I, _I, _I]),
     "endo_net16h_create": (_I, [ctypes.POINTER(_P), _I, _I, _I, _I]),
     "endo_net16_destroy": (None, [_P]),
@@ -142,6 +145,21 @@ SIGNATURES = {
                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "endo_prof_family_name": (ctypes.c_char_p, [_I]),
 }
+
+# the backward bricks of the 16-bit-storage family (one launch of endo_net16_bwd each), over bf16 and over half
+_U = ctypes.c_uint
+BACKWARD_BRICKS = {
+    "dgrad_weight_elems": (_L, [_I, _I, _I]),
+    "dgrad_weights": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "wgrad_partial_floats": (_L, [_I, _I, _I, _I, _I, _I]),
+    "wgrad": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _L, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P]),
+    "dgrad_bn": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _L, _P, _L, _L, _U, _P, _I, _I, _I, _I, _P]),
+    "dgrad_sumpool": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _U, _I, _I, _I, _P]),
+    "dgrad_block": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _U, _I, _I, _I, _P]),
+}
+for _prefix in ("endo_bf16_", "endo_f16_"):
+    for _name, _sig in BACKWARD_BRICKS.items():
+        SIGNATURES[_prefix + _name] = _sig
 
 _lib = None
 

@@ -12,7 +12,7 @@
 extern "C" int64_t endo_net_param_offset(int index);
 extern "C" int64_t endo_net_bn_offset(int bn_index, int which);
 
-// the half-storage build (net16h.hip) exports the network entry points as endo_net16h_*; the single-convolution bricks exist once (bf16)
+// the half-storage build (net16h.hip) exports the network entry points as endo_net16h_* and the single-kernel bricks as endo_f16_* (B16() below)
 #ifdef ENDO16_HALF
 #define N16(name) endo_net16h_##name
 #else
@@ -247,16 +247,15 @@ extern "C" int B16(unpack_nhwc)(const void* in, float* x, int n, int c, int h, i
     ENDO_LAUNCH_CHECK();
     return 0;
 }
-#ifndef ENDO16_HALF
-extern "C" int64_t endo_bf16_conv_weight_elems(int cout, int cin, int ks) {
+extern "C" int64_t B16(conv_weight_elems)(int cout, int cin, int ks) {
     if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3)) return -1;
     const int nt = cout <= 16 ? 1 : 3;
     const int64_t groups = (cout + nt * 16 - 1) / (nt * 16), chunks = (cin + kBfKC - 1) / kBfKC;
     return chunks * groups * ks * ks * nt * 16 * 32;
 }
 
-extern "C" int endo_bf16_conv_weights(const float* w, int cout, int cin, int ks, void* out, void* stream) {
-    if (!w || !out || endo_bf16_conv_weight_elems(cout, cin, ks) < 0) return ENDO_E_BADARG;
+extern "C" int B16(conv_weights)(const float* w, int cout, int cin, int ks, void* out, void* stream) {
+    if (!w || !out || B16(conv_weight_elems)(cout, cin, ks) < 0) return ENDO_E_BADARG;
     const int nt = cout <= 16 ? 1 : 3;
     bf16_conv_weights_kernel<<<256, 256, 0, static_cast<hipStream_t>(stream)>>>(w, cout, cin, ks, nt, static_cast<uint16_t*>(out), 0, 0);
     ENDO_LAUNCH_CHECK();
@@ -267,7 +266,7 @@ extern "C" int endo_bf16_conv_weights(const float* w, int cout, int cin, int ks,
 // in: [n][in_t / in_blk][in_h][in_w][in_blk] bf16, channels [ic0, ic0 + cin); out: [n][out_t / out_blk][h][w][out_blk] bf16, channels
 // [oc0, oc0 + cout) (blk 0 = t: channels-last; cout % 4 == 0, cin % 4 == 0, ic0 % 8 == 0, in_blk % 8 == 0, oc0 % 4 == 0, out_blk % 4 == 0); bn: [cin][2] (scale, shift) or null; wgt from endo_bf16_conv_weights;
 // out_sums: [cout][2] fp64 (sum, sum^2 of the stored values, ACCUMULATED) or null; ups: input is (h / 2) x (w / 2), nearest x2.
-extern "C" int endo_bf16_conv(const void* in, int in_t, int in_blk, int ic0, int cin, const float* bn, const void* wgt, const float* bias, void* out,
+extern "C" int B16(conv)(const void* in, int in_t, int in_blk, int ic0, int cin, const float* bn, const void* wgt, const float* bias, void* out,
                               int out_t, int out_blk, int oc0, int cout, double* out_sums, int n, int h, int w, int ks, int ups, void* stream_) {
     if (!in || !wgt || !out || n <= 0 || h <= 0 || w <= 0 || (ks != 1 && ks != 3) || cin <= 0 || cout <= 0 || (cin & 3) || (cout & 3) || (ic0 & 7) ||
         (in_t & 7) || (oc0 & 3) || (out_t & 3) || ic0 + cin > in_t || oc0 + cout > out_t || (ups && ((h | w) & 1)))
@@ -285,8 +284,156 @@ extern "C" int endo_bf16_conv(const void* in, int in_t, int in_blk, int ic0, int
     return cout <= 16 ? launch_bf16_conv<1, 1, 0, 8, 4>(p, stream) : launch_bf16_conv<1, 3, 0, 8, 4>(p, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward bricks: ONE launch of endo_net16_bwd each, with the template arguments it uses (include/endo_hip.h has the contracts).
+// Thin wrappers: arguments are validated before anything touches the device, then the network's own parameter struct and launcher.
+// ---------------------------------------------------------------------------------------------
+namespace {
+bool rot_ok(int rot, int rot_n, int c) { return rot_n == 0 ? rot == 0 : (rot >= 0 && rot < rot_n && rot_n <= c); }
+int up8(int v) { return (v + 7) & ~7; }
+}  // namespace
 
-#endif  // !ENDO16_HALF
+// data-gradient weights of a layer W[cout][cin][ks][ks]: the convolution over the gradient has cin output rows in groups of 48 and K = cout
+extern "C" int64_t B16(dgrad_weight_elems)(int cout, int cin, int ks) {
+    if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3)) return -1;
+    const int64_t groups = (cin + 47) / 48, chunks = (cout + kBfKC - 1) / kBfKC;
+    return chunks * groups * ks * ks * 3 * 16 * 32;
+}
+
+extern "C" int B16(dgrad_weights)(const float* w, int cout, int cin, int ks, int rot, int rot_n, int base, int koff, void* out, void* stream) {
+    if (!w || !out || B16(dgrad_weight_elems)(cout, cin, ks) < 0 || !rot_ok(rot, rot_n, cin)) return ENDO_E_BADARG;
+    // rows below `base` are stored as bf16_dgrad_block_kernel's LDS image: one K-chunk, the layer's couts at k = koff + co
+    if (base < 0 || base > cin || koff < 0 || (base > 0 && (ks != 3 || (base % 48) || koff + cout > kBfKC))) return ENDO_E_BADARG;
+    W16Table t{};
+    t.layers = 1; t.dgrad = 1;
+    t.start[0] = 0; t.start[1] = B16(dgrad_weight_elems)(cout, cin, ks);
+    t.w[0] = 0; t.out[0] = 0; t.cout[0] = cin; t.cin[0] = cout; t.cin_k[0] = cout; t.ks[0] = ks; t.nt[0] = 3;
+    t.rot[0] = rot; t.rot_n[0] = rot_n; t.base[0] = base; t.koff[0] = koff;
+    bf16_all_weights_kernel<<<1024, 256, 0, static_cast<hipStream_t>(stream)>>>(t, w, static_cast<uint16_t*>(out));
+    ENDO_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t B16(wgrad_partial_floats)(int n, int h, int w, int cin, int cout, int ks) {
+    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || (ks != 1 && ks != 3)) return -1;
+    Wgrad16Params q{};
+    q.n = n; q.h = h; q.w = w; q.cin = cin; q.cout = cout;
+    return bf16_wgrad_partial_floats(cin, cout, ks, bf16_wgrad_blocks(q, ks));
+}
+
+extern "C" int B16(wgrad)(const void* a, int a_t, int a_blk, int ac0, int cin, int cin_w, int ups, const float* saved, const float* gamma,
+                          const float* beta, int rot, int rot_n, int group_n, int64_t gs_saved, const void* g, int g_t, int g_blk, int gc0, int cout,
+                          const void* g_idx, const float* gscale, float* partial, int64_t partial_cap, float* dw, int n, int h, int w, int ks,
+                          void* stream) {
+    if (!a || !g || !partial || !dw || n <= 0 || h <= 0 || w <= 0 || (ks != 1 && ks != 3) || cin <= 0 || cout <= 0) return ENDO_E_BADARG;
+    if (a_blk <= 0) a_blk = a_t;
+    if (g_blk <= 0) g_blk = g_t;
+    if (a_t <= 0 || g_t <= 0 || a_t % a_blk || g_t % g_blk || ac0 < 0 || gc0 < 0 || ac0 + up8(cin) > a_t || gc0 + cout > g_t) return ENDO_E_BADARG;
+    if ((cin & 3) || (cout & 3) || (ac0 & 7) || (gc0 & 3) || (a_blk & 7) || (g_blk & 3)) return ENDO_E_BADARG;
+    if (ks == 1 && ((cout & 7) || (gc0 & 7) || (g_blk & 7))) return ENDO_E_BADARG;
+    if (cin_w < 0 || cin_w > cin || !rot_ok(rot, rot_n, cin_w > 0 ? cin_w : cin)) return ENDO_E_BADARG;
+    if (saved && (!gamma || !beta)) return ENDO_E_BADARG;
+    if (group_n < 0 || (group_n > 0 && (n > 2 * group_n || gs_saved < 0))) return ENDO_E_BADARG;
+    if ((ups || g_idx) && ((h | w) & 1)) return ENDO_E_BADARG;
+    if (g_idx && (ks != 1 || ups)) return ENDO_E_BADARG;
+    const int64_t need = B16(wgrad_partial_floats)(n, h, w, cin, cout, ks);
+    if (partial_cap < need) return ENDO_E_BADARG;
+    Wgrad16Params p{};
+    p.n = n; p.h = h; p.w = w;
+    p.a = static_cast<const uint16_t*>(a); p.a_blk = a_blk; p.a_h = ups ? h / 2 : h; p.a_w = ups ? w / 2 : w;
+    p.a_ns = static_cast<int64_t>(p.a_h) * p.a_w * a_t; p.ac0 = ac0; p.cin = cin; p.cin_w = cin_w; p.ups = ups;
+    p.saved = saved; p.gamma = gamma; p.beta = beta; p.rot = rot; p.rot_n = rot_n; p.group_n = group_n; p.gs_saved = gs_saved;
+    p.g = static_cast<const uint16_t*>(g); p.g_blk = g_blk; p.gc0 = gc0; p.cout = cout;
+    p.g_ns = (g_idx ? static_cast<int64_t>(h / 2) * (w / 2) : static_cast<int64_t>(h) * w) * g_t;
+    p.g_idx = static_cast<const uint8_t*>(g_idx); p.gscale = gscale;
+    p.partial = partial; p.partial_cap = partial_cap;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return ks == 3 ? launch_bf16_wgrad<3>(p, dw, s) : launch_bf16_wgrad<1>(p, dw, s);
+}
+
+// kEpiDgradBn.  ks = 3, in_idx null: the new-map sub-range of a dense layer as dense_bwd16 launches it; ks = 1 with in_idx: the
+// transition down as td_bwd16 launches it (g and in_idx on the (h / 2) x (w / 2) grid)
+extern "C" int B16(dgrad_bn)(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, int layer_cin, void* out, const void* x,
+                             int out_t, int out_blk, int co_off, int cout, const float* saved, const float* gamma, const float* beta, int rot,
+                             int rot_n, int group_n, int64_t gs_saved, double* out_sums, int64_t gs_out_sums, int64_t out_sums_slot_stride,
+                             unsigned sr_salt, const void* in_idx, int n, int h, int w, int ks, void* stream) {
+    if (!g || !wgt || !out || !x || !saved || !gamma || !beta || !out_sums || n <= 0 || h <= 0 || w <= 0 || (ks != 1 && ks != 3)) return ENDO_E_BADARG;
+    if ((ks == 1) != (in_idx != nullptr)) return ENDO_E_BADARG;
+    if (g_blk <= 0) g_blk = g_t;
+    if (out_blk <= 0) out_blk = out_t;
+    if (g_t <= 0 || out_t <= 0 || g_t % g_blk || out_t % out_blk || (g_blk & 7) || (out_blk & 3)) return ENDO_E_BADARG;
+    if (gcount <= 0 || cout <= 0 || layer_cin <= 0 || (gcount & 3) || (cout & 3) || gc0 < 0 || co_off < 0) return ENDO_E_BADARG;
+    if (gc0 + gcount > g_t || co_off + cout > layer_cin || co_off + cout > out_t || !rot_ok(rot, rot_n, layer_cin)) return ENDO_E_BADARG;
+    if (group_n < 0 || (group_n > 0 && (n % group_n || n > 2 * group_n || gs_saved < 0 || gs_out_sums < 0))) return ENDO_E_BADARG;
+    if (out_sums_slot_stride < 0 || (out_sums_slot_stride > 0 && out_sums_slot_stride < (group_n > 0 ? gs_out_sums : 0) + 2 * layer_cin)) return ENDO_E_BADARG;
+    Conv16Params p{};
+    p.n = n; p.h = h; p.w = w;
+    p.in = static_cast<const uint16_t*>(g); p.in_t = g_t; p.in_blk = g_blk; p.ic0 = gc0; p.cin = gcount;
+    p.wgt = static_cast<const uint16_t*>(wgt);
+    p.out = static_cast<uint16_t*>(out); p.out_t = out_t; p.out_blk = out_blk; p.out_ns = static_cast<int64_t>(h) * w * out_t;
+    p.oc0 = co_off; p.cout = cout;
+    p.x = static_cast<const uint16_t*>(x); p.x_saved = saved; p.gamma = gamma; p.beta = beta; p.rot = rot; p.rot_n = rot_n;
+    p.out_sums = out_sums; p.out_sums_slot_stride = out_sums_slot_stride;
+    p.group_n = group_n; p.gs_saved = gs_saved; p.gs_out_sums = gs_out_sums;
+    p.sr_salt = sr_salt;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ks == 3) {
+        if ((gc0 & 3) || (co_off % 48)) return ENDO_E_BADARG;          // the weights are addressed in 48-row groups from grp0
+        p.in_h = h; p.in_w = w; p.in_ns = static_cast<int64_t>(h) * w * g_t;
+        p.co_off = co_off; p.grp0 = co_off / 48; p.wgroups = (layer_cin + 47) / 48;
+        return launch_bf16_conv<3, 3, kEpiDgradBn, 4, 1, 0, 0, 8>(p, s);
+    }
+    if (((h | w) & 1) || (gc0 & 7) || (gcount & 7) || co_off != 0 || cout != layer_cin) return ENDO_E_BADARG;
+    p.in_h = h / 2; p.in_w = w / 2; p.in_ns = static_cast<int64_t>(p.in_h) * p.in_w * g_t;
+    p.ups = 1; p.in_idx = static_cast<const uint8_t*>(in_idx);
+    return launch_bf16_conv<1, 3, kEpiDgradBn, 8, 2, 0, 1>(p, s);
+}
+
+// kEpiSumPool as tu_bwd16 launches it: a 3 x 3 convolution over g on the h x w grid, its 2 x 2 sums added into channels [oc0, oc0 + cout) of
+// the (h / 2) x (w / 2) buffer `out`; out_sums[c][0] += the pixel sum of what channel c received
+extern "C" int B16(dgrad_sumpool)(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, void* out, int out_t, int out_blk, int oc0,
+                                  int cout, double* out_sums, unsigned sr_salt, int n, int h, int w, void* stream) {
+    if (!g || !wgt || !out || !out_sums || n <= 0 || h <= 0 || w <= 0 || ((h | w) & 1)) return ENDO_E_BADARG;
+    if (g_blk <= 0) g_blk = g_t;
+    if (out_blk <= 0) out_blk = out_t;
+    if (g_t <= 0 || out_t <= 0 || g_t % g_blk || out_t % out_blk || (g_blk & 7) || (out_blk & 3)) return ENDO_E_BADARG;
+    if (gcount <= 0 || cout <= 0 || (gcount & 3) || (cout & 3) || gc0 < 0 || (gc0 & 7) || oc0 < 0 || (oc0 & 3)) return ENDO_E_BADARG;
+    if (gc0 + up8(gcount) > g_t || oc0 + cout > out_t) return ENDO_E_BADARG;
+    Conv16Params p{};
+    p.n = n; p.h = h; p.w = w;
+    p.in = static_cast<const uint16_t*>(g); p.in_t = g_t; p.in_blk = g_blk; p.in_h = h; p.in_w = w; p.in_ns = static_cast<int64_t>(h) * w * g_t;
+    p.ic0 = gc0; p.cin = gcount;
+    p.wgt = static_cast<const uint16_t*>(wgt);
+    p.out = static_cast<uint16_t*>(out); p.out_t = out_t; p.out_blk = out_blk; p.out_ns = static_cast<int64_t>(h / 2) * (w / 2) * out_t;
+    p.oc0 = oc0; p.cout = cout;
+    p.out_sums = out_sums; p.sr_salt = sr_salt;
+    return launch_bf16_conv<3, 3, kEpiSumPool, 8, 2>(p, static_cast<hipStream_t>(stream));
+}
+
+// bf16_dgrad_block_kernel as dense_block_bwd16 launches it: d is the gradient buffer (the four layers' prepared gradients at
+// [gc0, gc0 + 48), base channels [0, c0) read-modify-written), x the forward buffer; wgt / saved / gamma / beta / sums: HOST arrays of four
+// device pointers, layer j's
+extern "C" int B16(dgrad_block)(void* d, const void* x, int t, int blk, int gc0, int c0, const void* const* wgt, const float* const* saved,
+                                const float* const* gamma, const float* const* beta, double* const* sums, int rot, int rot_n, int group_n,
+                                int64_t gs_saved, int64_t gs_sums, int64_t sums_slot_stride, unsigned sr_salt, int n, int h, int w, void* stream) {
+    if (!d || !x || !wgt || !saved || !gamma || !beta || !sums || n <= 0 || h <= 0 || w <= 0) return ENDO_E_BADARG;
+    if (blk <= 0) blk = t;
+    if (t <= 0 || t % blk || (blk & 7) || c0 <= 0 || (c0 % 48) || (gc0 & 7) || gc0 < c0 || gc0 + 48 > t || !rot_ok(rot, rot_n, c0)) return ENDO_E_BADARG;
+    if (group_n < 0 || (group_n > 0 && (n % group_n || n > 2 * group_n || gs_saved < 0 || gs_sums < 0))) return ENDO_E_BADARG;
+    if (sums_slot_stride < 0 || (sums_slot_stride > 0 && sums_slot_stride < (group_n > 0 ? gs_sums : 0) + 2 * c0)) return ENDO_E_BADARG;
+    if (static_cast<int64_t>(h) * w * t >= (int64_t{1} << 31)) return ENDO_E_BADARG;          // the kernel indexes a sample with 32 bits
+    DgradBlock16Params p{};
+    p.n = n; p.h = h; p.w = w;
+    p.g = static_cast<const uint16_t*>(d); p.out = static_cast<uint16_t*>(d); p.x = static_cast<const uint16_t*>(x);
+    p.ns = static_cast<int64_t>(h) * w * t; p.blk = blk; p.gc0 = gc0; p.c0 = c0;
+    for (int j = 0; j < kDbLayers; ++j) {
+        if (!wgt[j] || !saved[j] || !gamma[j] || !beta[j] || !sums[j]) return ENDO_E_BADARG;
+        p.wgt[j] = static_cast<const uint16_t*>(wgt[j]); p.saved[j] = saved[j]; p.gamma[j] = gamma[j]; p.beta[j] = beta[j]; p.sums[j] = sums[j];
+    }
+    p.rot = rot; p.rot_n = rot_n; p.group_n = group_n; p.gs_saved = gs_saved; p.gs_sums = gs_sums; p.sums_slot_stride = sums_slot_stride;
+    p.sr_salt = sr_salt;
+    return launch_bf16_dgrad_block(p, static_cast<hipStream_t>(stream));
+}
 
 // ---------------------------------------------------------------------------------------------
 // FCDenseNet57 forward over bf16 level buffers (reference models.py:171-187)

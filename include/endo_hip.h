@@ -946,6 +946,88 @@ int endo_net16h_bwd(endo_net16* net, const float* params, const void* tape, cons
                     void* stream);
 int endo_f16_pack_nhwc(const float* x, void* out, int n, int c, int h, int w, int t, int blk, int oc0, void* stream);
 int endo_f16_unpack_nhwc(const void* in, float* x, int n, int c, int h, int w, int t, int blk, int ic0, void* stream);
+/* the forward brick over half storage: endo_bf16_conv_weight_elems / _conv_weights / _conv with the other element type */
+int64_t endo_f16_conv_weight_elems(int cout, int cin, int ks);
+int endo_f16_conv_weights(const float* w, int cout, int cin, int ks, void* out, void* stream);
+int endo_f16_conv(const void* in, int in_t, int in_blk, int ic0, int cin, const float* bn, const void* wgt, const float* bias, void* out,
+                  int out_t, int out_blk, int oc0, int cout, double* out_sums, int n, int h, int w, int ks, int ups, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * BACKWARD BRICKS of the 16-bit-storage family: each entry is ONE launch of endo_net16_bwd / endo_net16h_bwd (the network's own
+ * parameter struct, launcher and template arguments), so that a test can hold a single kernel to fp64.  endo_bf16_* over bf16,
+ * endo_f16_* over half; buffers are [n][t / blk][h][w][blk] (blk 0 = t).  All are asynchronous on `stream` and return ENDO_E_BADARG
+ * before any device work for null pointers, sizes <= 0, channel ranges outside their buffer and the alignments named below.
+ * Additive: the version stays 7.  Not covered by a brick: bf16_prep_dy_kernel, the two bn_finalize kernels, bf16_final_bwd_kernel.
+ *
+ * endo_bf16_dgrad_weights: W[cout][cin][ks][ks] fp32 -> the DATA-GRADIENT layout (rows = the layer's input channels in groups of 48,
+ *   k = its output channels, taps flipped; endo_bf16_dgrad_weight_elems elements), one layer through the kernel that converts all of
+ *   them.  rot / rot_n: row r < rot_n holds input channel (r + rot) % rot_n (0, 0 = none).  base / koff: rows below `base` (a
+ *   multiple of 48; ks = 3, koff + cout <= 32) are stored as the dense-block kernel's LDS image -- output channel co at k = koff + co,
+ *   16-byte slot k / 8 at position (k / 8) XOR (row >> 1) & 3; rows from `base` on have co at k = co.
+ *
+ * endo_bf16_wgrad: dw[co][(ci + rot) % rot_n][ky][kx] += sum over pixels of G[co][y][x] * a[ci][y + ky - 1][x + kx - 1] (ks = 1: no taps),
+ *   dw fp32 [cout][cin_w][ks][ks], ACCUMULATED into; nothing outside it is written.  a: channels [ac0, ac0 + cin) of the forward
+ *   buffer (a_t channels; the last 8-channel unit is read whole: ac0 + cin rounded up to 8 <= a_t), on the (h / 2) x (w / 2) grid
+ *   if ups (nearest x2).  saved non-null: a = relu(x * sc + sh) rounded to the storage type, sc = gamma[pc] * saved[2 pc + 1],
+ *   sh = fma(-saved[2 pc], sc, beta[pc]), pc = (ci + rot) % rot_n for ci < rot_n; sample n uses the table gs_saved floats further on
+ *   if n >= group_n > 0 (n <= 2 group_n).  g: channels [gc0, gc0 + cout) of the prepared gradient (g_t channels) on the h x w grid,
+ *   or -- g_idx non-null, ks = 1 -- on the pooled (h / 2) x (w / 2) grid with g_idx [n][h / 2][w / 2][cout] bytes naming the window
+ *   position 2 dy + dx that receives the value.  cin_w: input channels of dw (0 = cin).  gscale: {S, 1 / S} or null: dw receives the
+ *   sum times 1 / S.  partial: scratch of partial_cap floats, at least endo_bf16_wgrad_partial_floats(n, h, w, cin, cout, ks) (a
+ *   shorter one is ENDO_E_BADARG; contents on entry ignored).  cin, cout % 4, ac0 % 8, a_blk % 8, gc0 % 4, g_blk % 4; ks = 1: cout,
+ *   gc0, g_blk % 8; h, w even with ups or g_idx; cin_w <= cin; rot < rot_n <= cin.
+ *
+ * endo_bf16_dgrad_bn: the data gradient of BN -> ReLU -> conv with respect to input channels [co_off, co_off + cout) of a layer with
+ *   layer_cin inputs and gcount outputs: dz = conv(g[gc0 : gc0 + gcount], wgt) with wgt from endo_bf16_dgrad_weights(gcount outputs,
+ *   layer_cin inputs), da = [x * sc + sh > 0] * dz (sc, sh as above at (ci + rot) % rot_n), out[ci] += sc * da (read-modify-write,
+ *   stored with stochastic rounding keyed by position and sr_salt: the same inputs give the same bits), out_sums[2 ci] += sum da,
+ *   out_sums[2 ci + 1] += sum da * x (fp64, ACCUMULATED; group 1's gs_out_sums doubles later; out_sums_slot_stride > 0: eight copies
+ *   that many doubles apart, a block adds to one of them and the reader adds them up).  out and x: out_t channels, same positions.
+ *   ks = 3, in_idx null: a dense layer's new-map sub-range (co_off a multiple of 48, gc0 % 4);  ks = 1 with in_idx: the transition
+ *   down (co_off = 0, cout = layer_cin, gcount and gc0 % 8, h and w even, g and in_idx on the (h / 2) x (w / 2) grid, in_idx
+ *   [n][h / 2][w / 2][gcount] bytes).  Any other combination is ENDO_E_BADARG.
+ *
+ * endo_bf16_dgrad_sumpool: transition up: dz = conv3x3(g[gc0 : gc0 + gcount], wgt) on the h x w grid (even), its 2 x 2 sums added
+ *   to channels [oc0, oc0 + cout) of the (h / 2) x (w / 2) buffer `out` (read-modify-write, stochastic rounding); out_sums[2 c] +=
+ *   the pixel sum of what channel c received (fp64 [cout][2], ACCUMULATED).  gc0 % 8, oc0 % 4.
+ *
+ * endo_bf16_dgrad_block: a dense block's four layers with respect to its base channels [0, c0) in one launch: d is the gradient
+ *   buffer (t channels; the layers' prepared gradients at [gc0 + 12 j, + 12), gc0 >= c0, gc0 % 8; base channels read-modify-written),
+ *   x the forward buffer of the same geometry; wgt / saved / gamma / beta / sums: HOST arrays of four device pointers (layer j:
+ *   weights from endo_bf16_dgrad_weights(12, c0 + 12 j, 3, rot, rot_n, c0, {0, 12, 8, 20}[j]), its tables, its fp64 sums as above).
+ *   c0 a multiple of 48.
+ * ------------------------------------------------------------------------------------------- */
+int64_t endo_bf16_dgrad_weight_elems(int cout, int cin, int ks);
+int endo_bf16_dgrad_weights(const float* w, int cout, int cin, int ks, int rot, int rot_n, int base, int koff, void* out, void* stream);
+int64_t endo_bf16_wgrad_partial_floats(int n, int h, int w, int cin, int cout, int ks);
+int endo_bf16_wgrad(const void* a, int a_t, int a_blk, int ac0, int cin, int cin_w, int ups, const float* saved, const float* gamma,
+             const float* beta, int rot, int rot_n, int group_n, int64_t gs_saved, const void* g, int g_t, int g_blk, int gc0, int cout,
+             const void* g_idx, const float* gscale, float* partial, int64_t partial_cap, float* dw, int n, int h, int w, int ks,
+             void* stream);
+int endo_bf16_dgrad_bn(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, int layer_cin, void* out, const void* x, int out_t,
+                int out_blk, int co_off, int cout, const float* saved, const float* gamma, const float* beta, int rot, int rot_n, int group_n,
+                int64_t gs_saved, double* out_sums, int64_t gs_out_sums, int64_t out_sums_slot_stride, unsigned sr_salt, const void* in_idx,
+                int n, int h, int w, int ks, void* stream);
+int endo_bf16_dgrad_sumpool(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, void* out, int out_t, int out_blk, int oc0,
+                     int cout, double* out_sums, unsigned sr_salt, int n, int h, int w, void* stream);
+int endo_bf16_dgrad_block(void* d, const void* x, int t, int blk, int gc0, int c0, const void* const* wgt, const float* const* saved,
+                   const float* const* gamma, const float* const* beta, double* const* sums, int rot, int rot_n, int group_n,
+                   int64_t gs_saved, int64_t gs_sums, int64_t sums_slot_stride, unsigned sr_salt, int n, int h, int w, void* stream);
+int64_t endo_f16_dgrad_weight_elems(int cout, int cin, int ks);
+int endo_f16_dgrad_weights(const float* w, int cout, int cin, int ks, int rot, int rot_n, int base, int koff, void* out, void* stream);
+int64_t endo_f16_wgrad_partial_floats(int n, int h, int w, int cin, int cout, int ks);
+int endo_f16_wgrad(const void* a, int a_t, int a_blk, int ac0, int cin, int cin_w, int ups, const float* saved, const float* gamma,
+             const float* beta, int rot, int rot_n, int group_n, int64_t gs_saved, const void* g, int g_t, int g_blk, int gc0, int cout,
+             const void* g_idx, const float* gscale, float* partial, int64_t partial_cap, float* dw, int n, int h, int w, int ks,
+             void* stream);
+int endo_f16_dgrad_bn(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, int layer_cin, void* out, const void* x, int out_t,
+                int out_blk, int co_off, int cout, const float* saved, const float* gamma, const float* beta, int rot, int rot_n, int group_n,
+                int64_t gs_saved, double* out_sums, int64_t gs_out_sums, int64_t out_sums_slot_stride, unsigned sr_salt, const void* in_idx,
+                int n, int h, int w, int ks, void* stream);
+int endo_f16_dgrad_sumpool(const void* g, int g_t, int g_blk, int gc0, int gcount, const void* wgt, void* out, int out_t, int out_blk, int oc0,
+                     int cout, double* out_sums, unsigned sr_salt, int n, int h, int w, void* stream);
+int endo_f16_dgrad_block(void* d, const void* x, int t, int blk, int gc0, int c0, const void* const* wgt, const float* const* saved,
+                   const float* const* gamma, const float* const* beta, double* const* sums, int rot, int rot_n, int group_n,
+                   int64_t gs_saved, int64_t gs_sums, int64_t sums_slot_stride, unsigned sr_salt, int n, int h, int w, void* stream);
 /* byte offsets into the tape (what 0: final pre-activation fp32; 1: (mean, rstd) of BatchNorm `index` in module order; 2: max-pool
  * codes of transition down `index` ([n][h / 2][w / 2][cout] bytes); 3: level buffer `index`) or the backward workspace (4: gradient
  * buffer of level `index`); 5: channels of level buffer `index`; 7: bytes between two sample groups' (mean, rstd) tables.  Level buffers: [n][t / 32][h][w][32] bf16, channels [0, S) the
