@@ -611,18 +611,13 @@ __global__ void __launch_bounds__(kConvThreads, MINW) conv_dma_kernel(const Conv
                         f32x4 o = dpre[r][q];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float xc = xpre[r][q][e] - mean;
-                            const float z = fmaf(xc, scale, beta);
-                            const float dz = z > 0.f ? acc[r][q][e] : 0.f;
-                            s1 += dz;
-                            s2 += dz * (xc * rstd);
+                            const float dz = bn_relu_bwd_xhat(xpre[r][q][e], acc[r][q][e], scale, beta, mean, rstd, s1, s2);
                             o[e] += scale * dz;
                         }
                         *reinterpret_cast<f32x4*>(p.out + n * p.out_ns + static_cast<int64_t>(co) * p.out_cs + y * p.out_w + px) = o;
                     }
                 }
-                s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-                s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+                bn_rows_sum(s1, s2);
                 if (lk == 0) {
                     s_red[((tid >> 6) * NB + jloc) * 2] = s1;
                     s_red[((tid >> 6) * NB + jloc) * 2 + 1] = s2;
@@ -666,8 +661,7 @@ __global__ void __launch_bounds__(kConvThreads, MINW) conv_dma_kernel(const Conv
                     for (int e = 0; e < 4; ++e) { s1 += lo[e] + hi[e]; s2 += lo[e] * lo[e] + hi[e] * hi[e]; }
                 }
             }
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) {
                 s_red[((tid >> 6) * NB + q * 16 + li) * 2] = s1;
                 s_red[((tid >> 6) * NB + q * 16 + li) * 2 + 1] = s2;

@@ -28,7 +28,7 @@
 // Global->LDS staging is register-prefetched one K-chunk ahead so HBM latency hides under MFMAs.
 #pragma once
 
-#include "common.h"
+#include "bn_device.h"
 
 namespace endo {
 
@@ -233,8 +233,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
                 }
             }
             if (p.out_sums) {
-                s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-                s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+                bn_rows_sum(s1, s2);
                 if (lk == 0) {
                     s_red[(wave * NB + q * 16 + li) * 2] = s1;
                     s_red[(wave * NB + q * 16 + li) * 2 + 1] = s2;
@@ -282,8 +281,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
                     }
                 }
             }
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) {
                 s_red[(wave * NB + q * 16 + li) * 2] = s1;
                 s_red[(wave * NB + q * 16 + li) * 2 + 1] = s2;
@@ -299,6 +297,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
             }
         }
     } else if constexpr (EPI == EPI_DGRAD_BN) {
+        // (bn_relu_bwd_xhat and bn_rows_sum of bn_device.h in place: with either helper three conv_mfma_kernel instantiations are
+        // scheduled differently, one of them in 84 instead of 80 registers)
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const int jloc = q * 16 + li;

@@ -352,11 +352,7 @@ __global__ void __launch_bounds__(kConvThreads) dgrad_block_kernel(const DgradBl
                 } else if (co < p.count && y < p.h && px + 3 < p.w) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float xcen = xc[a][r][e] - mean;
-                        const float z = fmaf(xcen, scale, beta);
-                        const float dz = z > 0.f ? acc[a][r][e] : 0.f;
-                        s1 += dz;
-                        s2 += dz * (xcen * rstd);
+                        const float dz = bn_relu_bwd_xhat(xc[a][r][e], acc[a][r][e], scale, beta, mean, rstd, s1, s2);
                         total[a][r][e] += scale * dz;
                     }
                 }
@@ -366,8 +362,7 @@ __global__ void __launch_bounds__(kConvThreads) dgrad_block_kernel(const DgradBl
                     total[a][r] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (!(EXP & 8) && lk == 0) {
                 float* red = s_red + buf * G::kRed + a * (4 * 16 * 2);
                 red[(wave * 16 + li) * 2] = s1;
@@ -617,8 +612,7 @@ __global__ void __launch_bounds__(512, 4) dgrad_block8_kernel(const DgradBlockPa
             }
             float s1 = s1v[0] + s1v[1];
             float s2 = (s2v[0] + s2v[1]) * rstd;
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) {
                 float* red = s_red + (buf * 2 + half) * G::kRed;
                 red[(w4 * 16 + li) * 2] = s1;

@@ -184,18 +184,13 @@ __global__ void __launch_bounds__(kConvThreads) dgrad_dense_kernel(const ConvPar
                     f32x4 o = dc[r];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float xcen = xc[r][e] - mean;
-                        const float z = fmaf(xcen, scale, beta);
-                        const float dz = z > 0.f ? acc[r][e] : 0.f;
-                        s1 += dz;
-                        s2 += dz * (xcen * rstd);
+                        const float dz = bn_relu_bwd_xhat(xc[r][e], acc[r][e], scale, beta, mean, rstd, s1, s2);
                         o[e] += scale * dz;
                     }
                     *reinterpret_cast<f32x4*>(out_n + static_cast<int64_t>(co) * p.out_cs + y * p.out_w + px) = o;
                 }
             }
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) {
                 float* red = s_red + buf * (4 * 16 * 2);
                 red[(wave * 16 + li) * 2] = s1;

@@ -357,6 +357,7 @@ __global__ void __launch_bounds__(kConvThreads, NewMapGeom<NL>::kBlocksPerCu) dg
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
         double a = ds1[l] + static_cast<double>(fs1[l]), b = ds2[l] + static_cast<double>(fs2[l]);
+        // (bn_rows_sum of bn_device.h in place: with the helper the NL = 1 and NL = 2 kernels are scheduled differently)
         a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
         b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
         if (lk == 0) {

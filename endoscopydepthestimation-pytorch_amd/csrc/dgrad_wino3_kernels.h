@@ -31,7 +31,8 @@
 // LDS: dY tile 66 KB + U 2 workers x 2 buffers x 12 KB + sums 24 KB + BN table 12 KB = 150 KB: one 8-wave block per CU.
 #pragma once
 
-#include "dgrad_wino_kernels.h"
+#include "bn_device.h"
+#include "dgrad_wino3_device.h"
 
 namespace endo {
 
@@ -43,6 +44,7 @@ struct DgradWino3Geom {
     static constexpr int kRows = kTileY + 2, kCols = kTileX + 2;
     static constexpr int kPlane = kRows * kCols;                        // 340
     static constexpr int kCS = 352;                                     // == 32 (mod 64) dwords: the 8-byte patch reads of the 4 maps of a quad hit disjoint banks
+    static constexpr int kPatch0 = 0;                                   // a lane's patches start at window column 2 li
     static constexpr int kU = kWinoDgradSlice;
     static constexpr int kMaxCount = 192;                               // base channels (12 groups: the level-1 up block)
     static constexpr int kMaxSteps = (kMaxCount / 32) * NL;             // per worker
@@ -59,7 +61,6 @@ template <int NL, int EXP = 0>
 __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockParams p, const float* __restrict__ u0, const float* __restrict__ u1,
                                                              const float* __restrict__ u2, const float* __restrict__ u3) {
     using G = DgradWino3Geom<NL>;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int grp = p.group_n > 0 ? blockIdx.z / p.group_n : 0;
     const int n = blockIdx.z - grp * p.group_n;
     const int64_t grp_off = grp * p.gs;
@@ -108,11 +109,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             }
         }
     }
-    for (int i = tid; i < NL * p.count; i += G::kThreads) {
-        const int l = i / p.count, ch = i - l * p.count;
-        const float mean = p.saved[l][grp_off + 2 * ch], rstd = p.saved[l][grp_off + 2 * ch + 1];
-        *reinterpret_cast<f32x4*>(s_bn + 4 * i) = f32x4{p.gamma[l][ch] * rstd, p.beta[l][ch], mean, rstd};
-    }
+    wino3_build_bn<NL, G::kThreads>(p, grp_off, tid, s_bn);
     // this worker's U slice of (group, layer) into weight buffer `buf`: one contiguous 12 KB run, 3 float4 units per thread
     auto issue_weights = [&](int gq, int l, int buf) {
         const float* src = u_layer[l] + static_cast<int64_t>(gq) * G::kU + 4 * th;
@@ -183,44 +180,11 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
     f32x2 av[3][8];
     f32x4 acc[16];
 
-    // ---- T: input transform of the lane's 4x4 patches of layer l's 12 maps: raw patch values into av (24 8-byte reads), transformed in place ----
-    auto load_patches = [&](int l) {
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            // LDS rows 2 w4 .. 2 w4 + 3, columns 2 li .. 2 li + 3 (two aligned pairs): row r's pairs land in av[quad][2 r], av[quad][2 r + 1]
-            const float* a_base = s_g + (l * 12 + quad * 4 + lk) * G::kCS + (2 * w4) * G::kCols + 2 * li;
-#pragma unroll
-            for (int row = 0; row < 4; ++row) {
-                av[quad][2 * row] = *reinterpret_cast<const f32x2*>(a_base + row * G::kCols);
-                av[quad][2 * row + 1] = *reinterpret_cast<const f32x2*>(a_base + row * G::kCols + 2);
-            }
-        }
+    // ---- T: input transform of the lane's 4x4 patches of layer l's 12 maps into av ----
+    auto transform = [&](int l) {
+        wino3_load_patches<G>(s_g, l, w4, lk, li, av);
+        if constexpr ((EXP & 64) == 0) wino3_transform_inplace(av);
     };
-    auto transform_inplace = [&]() {
-        if constexpr ((EXP & 64) != 0) return;
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            // B^T d on the column pairs (c0, c1) | (c2, c3): rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3) -- 8 packed adds
-            // (there is no packed subtract and clang scalarises a - b on ext-vectors: the difference is a packed add with the neg bits set;
-            // operands here come from LDS reads, never straight from an MFMA -- the hazard recogniser does not look into inline assembly)
-            auto sub2 = [](const f32x2 a, const f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; };
-            const f32x2 l0 = av[quad][0], h0 = av[quad][1], l1 = av[quad][2], h1 = av[quad][3];
-            const f32x2 l2 = av[quad][4], h2 = av[quad][5], l3 = av[quad][6], h3 = av[quad][7];
-            const f32x2 tl[4] = {sub2(l0, l2), l1 + l2, sub2(l2, l1), sub2(l1, l3)};
-            const f32x2 th[4] = {sub2(h0, h2), h1 + h2, sub2(h2, h1), sub2(h1, h3)};
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                // (.) B: (v0, v1) = (c0 - c2, c1 + c2), (v2, v3) = (c2 - c1, c1 - c3) -- one packed add each: the operand-select bits pick c2 for
-                // both halves / c1 for both halves, the neg bits the signs (clang turns the same arithmetic on ext-vectors into moves + xor)
-                f32x2 v01, v23;
-                asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(v01) : "v"(tl[a]), "v"(th[a]));
-                asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(v23) : "v"(th[a]), "v"(tl[a]));
-                av[quad][2 * a] = v01;
-                av[quad][2 * a + 1] = v23;
-            }
-        }
-    };
-    auto transform = [&](int l) { load_patches(l); transform_inplace(); };
 
     // ---- M: 16 transform-domain GEMMs over the layer's 12 dY maps: M = this wave's row of 16 tiles, N = the worker's 16 channels ----
     auto mfmas = [&](int buf) {
@@ -230,79 +194,35 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             return;
         }
         const float* ub = s_u + (wk * 2 + buf) * G::kU;
+        if constexpr ((EXP & 32) != 0) {          // diagnostic: the products on the VALU
 #pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            const float* b_base = ub + ((quad * 4 + lk) * 4 * 16 + li) * 4;
+            for (int quad = 0; quad < 3; ++quad) {
+                const float* b_base = ub + ((quad * 4 + lk) * 4 * 16 + li) * 4;
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(b_base + a * 64);
+                for (int a = 0; a < 4; ++a) {
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(b_base + a * 64);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if constexpr ((EXP & 32) != 0) {
+                    for (int i = 0; i < 4; ++i) {
                         if (quad == 0) acc[4 * a + i] = f32x4{av[quad][2 * a + (i >> 1)][i & 1] * b[i], 0.f, 0.f, 0.f};
                         else acc[4 * a + i][quad] += av[quad][2 * a + (i >> 1)][i & 1] * b[i];
-                    } else if (quad == 0) {
-                        acc[4 * a + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[quad][2 * a + (i >> 1)][i & 1], b[i], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    } else {
-                        acc[4 * a + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[quad][2 * a + (i >> 1)][i & 1], b[i], acc[4 * a + i], 0, 0, 0);
                     }
                 }
             }
+            return;
         }
+        wino3_mfmas(ub, lk, li, av, acc, [](int) {});
     };
 
-    // ---- E: output transform A^T M A (tiles 4 lk + e), layer l's ReLU mask + BN backward, accumulated over the layers;
-    //         `slot` = the worker's running step number (its row of the BN-sum table) ----
-    auto read_bn = [&](int gq, int l) { return *reinterpret_cast<const f32x4*>(s_bn + 4 * (l * p.count + gq * 16 + li)); };
-    auto epilogue = [&](int gq, int l, int slot, const f32x4 bn) {
+    // ---- E: wino3_epilogue, then the step's sums join the wave's slot; `slot` = the worker's running step number (its row of the BN-sum table) ----
+    auto epilogue = [&](int slot, const f32x4 bn) {
         if constexpr ((EXP & 64) != 0) {          // diagnostic: no V-phase arithmetic
 #pragma unroll
             for (int i = 0; i < 16; ++i) total[i >> 3][(i >> 2) & 1][i & 3] += acc[i][0];
             return;
         }
-        // On register pairs: the output transform A^T M A runs on the tile pairs (e, e + 1) of the accumulators (adjacent registers of an MFMA
-        // result), BN + ReLU backward on the pixel pairs (k, k + 1) of x / the running total (adjacent registers of a 16-byte load); the
-        // per-pixel select between the two (dz = z > 0 ? d : 0) writes its results where the second layout wants them: the transposition.
-        const f32x2 sb = {bn[0], bn[1]}, mr = {bn[2], bn[3]};          // (scale, beta), (mean, rstd)
-        const float rstd = bn[3];
-        f32x2 s1v = {0.f, 0.f}, s2v = {0.f, 0.f};
-        f32x2 minus1 = {-1.f, -1.f};
-        asm("" : "+v"(minus1));          // opaque: with a visible constant the fma below folds back into a subtraction, which is scalarised
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {          // tiles e = 2 hh, 2 hh + 1 = the lane's column half hh
-            f32x2 u0r[4], u1r[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const f32x2 m0 = {acc[c][2 * hh], acc[c][2 * hh + 1]}, m1 = {acc[4 + c][2 * hh], acc[4 + c][2 * hh + 1]};
-                const f32x2 m2 = {acc[8 + c][2 * hh], acc[8 + c][2 * hh + 1]}, m3 = {acc[12 + c][2 * hh], acc[12 + c][2 * hh + 1]};
-                u0r[c] = m0 + m1 + m2;
-                u1r[c] = __builtin_elementwise_fma(m2 + m3, minus1, m1);          // m1 - m2 - m3 (compiler-made instructions here: they read MFMA results, and the MFMA -> VALU wait states are the compiler's to insert)
-            }
-            // d[r][cx] over the tile pair: pixel k = 2 (e & 1) + cx of the column half
-            const f32x2 d[2][2] = {{u0r[0] + u0r[1] + u0r[2], __builtin_elementwise_fma(u0r[2] + u0r[3], minus1, u0r[1])},
-                                   {u1r[0] + u1r[1] + u1r[2], __builtin_elementwise_fma(u1r[2] + u1r[3], minus1, u1r[1])}};
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                for (int ee = 0; ee < 2; ++ee) {          // pixels k = 2 ee, 2 ee + 1
-                    const f32x2 x2 = {xc[r][hh][2 * ee], xc[r][hh][2 * ee + 1]};
-                    f32x2 xcen, z;
-                    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(xcen) : "v"(x2), "v"(mr));              // x - mean
-                    asm("v_pk_fma_f32 %0, %1, %2, %2 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(z) : "v"(xcen), "v"(sb));                     // xcen * scale + beta
-                    const f32x2 dz = {z[0] > 0.f ? d[r][0][ee] : 0.f, z[1] > 0.f ? d[r][1][ee] : 0.f};
-                    s1v += dz;
-                    s2v = __builtin_elementwise_fma(dz, xcen, s2v);
-                    f32x2 t2 = {total[r][hh][2 * ee], total[r][hh][2 * ee + 1]};
-                    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(t2) : "v"(dz), "v"(sb));                                    // total += dz * scale
-                    total[r][hh][2 * ee] = t2[0];
-                    total[r][hh][2 * ee + 1] = t2[1];
-                }
-            }
-        }
-        float s1 = s1v[0] + s1v[1], s2 = s2v[0] + s2v[1];
-        s2 *= rstd;
-        s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+        float s1, s2;
+        wino3_epilogue(acc, xc, total, bn, s1, s2);
+        bn_rows_sum(s1, s2);
         if (lk == 0) {
             float* red = s_red + ((wk * G::kMaxSteps + slot) * 4 + w4) * 32;
             *reinterpret_cast<f32x2*>(red + 2 * li) = f32x2{s1, s2};
@@ -317,13 +237,6 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto phase_end_m = [&]() {
-        __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0) only: the DMA of the next slice stays in flight across the barrier
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
     const int g_first = wk;                          // p.count >= 32: every worker has at least one whole group
     issue_weights(g_first, 0, 0);
     load_x(g_first * 16 + li, xc);
@@ -348,14 +261,14 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             if (l + 1 < NL) issue_weights(gq, l + 1, (l + 1) & 1);
             else if (has_next) issue_weights(g_next, l_next, 0);
             mfmas(l & 1);
-            phase_end_m();
+            wino3_phase_end_m();
             // ---------------- V: loads, E(gq, l), T(next step) ----------------
             float touched[4] = {0.f, 0.f, 0.f, 0.f};
             if (l == NL - 2) {
                 load_old(co, dc);
                 if (has_next) touch_x(g_next * 16 + li, touched);
             }
-            epilogue(gq, l, slot + l, read_bn(gq, l));
+            epilogue(slot + l, wino3_read_bn(s_bn, p.count, gq, l, li));
             __builtin_amdgcn_sched_barrier(0);          // keep the transform's 24 patch reads (48 registers) behind the epilogue
             if (l + 1 < NL) {
                 transform(l + 1);
@@ -389,9 +302,9 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             if (j == 0 && nfull > 0) store_out((2 * (nfull - 1) + wk) * 16 + li, dc);
             if (j + 1 < NL / 2) issue_weights(gq, l + 1, (j + 1) & 1);
             mfmas(j & 1);
-            phase_end_m();
+            wino3_phase_end_m();
             if (j == 0 && wk == 0) load_old(co, dc);
-            epilogue(gq, l, slot + j, read_bn(gq, l));
+            epilogue(slot + j, wino3_read_bn(s_bn, p.count, gq, l, li));
             __builtin_amdgcn_sched_barrier(0);
             if (j + 1 < NL / 2) transform(l + 1);
             phase_end_v();
@@ -425,19 +338,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3_kernel(const DgradBlockPar
             store_out((ngroups - 1) * 16 + li, dc);
         }
     }
-    if constexpr ((EXP & 4) == 0) {
-        // one fp64 atomic per (worker, step, channel, sum): the 4 waves' partials added in a fixed order
-        for (int i = tid; i < 2 * nsteps * 32; i += G::kThreads) {
-            const int w = i / (nsteps * 32), rem = i - w * nsteps * 32;
-            const int s = rem >> 5, j2 = rem & 31;
-            const float* red = s_red + (w * G::kMaxSteps + s) * G::kRedStep + j2;
-            const double t = static_cast<double>(red[0]) + static_cast<double>(red[32]) + static_cast<double>(red[64]) + static_cast<double>(red[96]);
-            const int gi = s / NL;
-            const int gq = gi < nfull ? 2 * gi + w : ngroups - 1;
-            const int l = gi < nfull ? s - gi * NL : s - nfull * NL + w * (NL / 2);
-            atomicAdd(p.scratch[l] + bn_slot_offset(p.slot_stride) + grp_off / 2 + 2 * (gq * 16) + j2, t);
-        }
-    }
+    if constexpr ((EXP & 4) == 0) wino3_flush_sums<NL, G>(p, grp_off, tid, s_red, nsteps, nfull, ngroups);
 }
 
 inline bool dgrad_wino3_ok(const DgradBlockParams& p) {

@@ -1,7 +1,8 @@
 // Fused data gradient of a dense block's base channels, Winograd F(2x2, 3x3), phase-skewed -- as PERSISTENT blocks (round 6).
 //
-// Same arithmetic, work split and phase structure as dgrad_wino3_kernel (dgrad_wino3_kernels.h: read its header first).  That kernel
-// keeps ONE 8-wave block per CU (150 KB of LDS), so whatever a block does before its first and after its last MFMA is exposed:
+// Same arithmetic, work split and phase structure as dgrad_wino3_kernel (dgrad_wino3_kernels.h: read its header first); the steps of
+// the two are the functions of dgrad_wino3_device.h, and this file holds what differs.  That kernel keeps ONE 8-wave block per CU
+// (150 KB of LDS), so whatever a block does before its first and after its last MFMA is exposed:
 // tools/wino_bench's diagnostic builds priced the 66 KB dY tile load at 81 us of a level-0 launch (20 rounds of blocks per CU), the
 // 1 152 fp64 atomics per block at 22 us, and a build without any global access ran 1040 us per-tile against 860 us persistent
 // (C0 = 144).  Here a block stays on its CU and walks a contiguous run of tiles of ONE group of the batch:
@@ -59,6 +60,7 @@ struct DgradWino3PGeom {
     // 24 ds_read2_b32 and every interval of the kernel 350 cycles longer).  The 16-byte DMA writes to a 4-byte aligned LDS address.
     static constexpr int kMapShift = 1;
     static_assert(kCS >= kPlane + kMapShift && kCS % 64 == 32, "dY map stride");
+    static constexpr int kPatch0 = kMapShift + kLeft - 1;              // window columns 3 + 2 li .. of the shifted map
     static constexpr int kMaxCount = 144;                               // base channels (9 groups: the level-0 up block); wider blocks keep dgrad_wino3_kernel
     static constexpr int kMaxSteps = (kMaxCount / 32) * NL + NL / 2;    // per worker
     static constexpr int kG = NL * 12 * kCS;
@@ -83,7 +85,6 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
                                                               const float* __restrict__ u2, const float* __restrict__ u3, int tiles_xy, int gn, int bpg,
                                                               double* __restrict__ fw_parts) {
     using G = DgradWino3PGeom<NL>;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const int grp = blockIdx.x / bpg;
     const int r0 = blockIdx.x - grp * bpg;
@@ -125,11 +126,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
     };
 
     // ---- once per block: BN table, zeroed sums ----
-    for (int i = tid; i < NL * p.count; i += G::kThreads) {
-        const int l = i / p.count, ch = i - l * p.count;
-        const float mean = p.saved[l][grp_off + 2 * ch], rstd = p.saved[l][grp_off + 2 * ch + 1];
-        *reinterpret_cast<f32x4*>(s_bn + 4 * i) = f32x4{p.gamma[l][ch] * rstd, p.beta[l][ch], mean, rstd};
-    }
+    wino3_build_bn<NL, G::kThreads>(p, grp_off, tid, s_bn);
     for (int i = tid; i < 2 * G::kMaxSteps * G::kRedStep + G::kFw; i += G::kThreads) s_red[i] = 0.f;
     if constexpr (FW) {
         for (int i = tid; i < p.count; i += G::kThreads) { fw_parts[static_cast<int64_t>(blockIdx.x) * p.count + i] = 0.0; s_fw64[i] = 0.0; }
@@ -253,38 +250,8 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
     f32x2 av[3][8];
     f32x4 acc[16];
 
-    // ---- T: input transform of the lane's 4x4 patches of layer l's 12 maps (dgrad_wino3_kernel's, unchanged) ----
-    auto load_patches = [&](int l) {
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            // rows 2 w4 .. 2 w4 + 3, columns x0 - 1 + 2 li .. + 3 = window columns 3 + 2 li ..
-            const float* a_base = s_g + (l * 12 + quad * 4 + lk) * G::kCS + G::kMapShift + (2 * w4) * G::kCols + (G::kLeft - 1) + 2 * li;
-#pragma unroll
-            for (int row = 0; row < 4; ++row) {
-                av[quad][2 * row] = *reinterpret_cast<const f32x2*>(a_base + row * G::kCols);
-                av[quad][2 * row + 1] = *reinterpret_cast<const f32x2*>(a_base + row * G::kCols + 2);
-            }
-        }
-    };
-    auto transform_inplace = [&]() {
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            auto sub2 = [](const f32x2 a, const f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; };
-            const f32x2 l0 = av[quad][0], h0 = av[quad][1], l1 = av[quad][2], h1 = av[quad][3];
-            const f32x2 l2 = av[quad][4], h2 = av[quad][5], l3 = av[quad][6], h3 = av[quad][7];
-            const f32x2 tl[4] = {sub2(l0, l2), l1 + l2, sub2(l2, l1), sub2(l1, l3)};
-            const f32x2 th2[4] = {sub2(h0, h2), h1 + h2, sub2(h2, h1), sub2(h1, h3)};
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                f32x2 v01, v23;
-                asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(v01) : "v"(tl[a]), "v"(th2[a]));
-                asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(v23) : "v"(th2[a]), "v"(tl[a]));
-                av[quad][2 * a] = v01;
-                av[quad][2 * a + 1] = v23;
-            }
-        }
-    };
-    auto transform = [&](int l) { load_patches(l); transform_inplace(); };
+    // ---- T: rows 2 w4 .. 2 w4 + 3, columns x0 - 1 + 2 li .. + 3 of the tile ----
+    auto transform = [&](int l) { wino3_load_patches<G>(s_g, l, w4, lk, li, av); wino3_transform_inplace(av); };
 
     // ---- M: 16 transform-domain GEMMs over the layer's 12 dY maps.  NJ > 0: the wave also issues NJ refill DMAs of the next tile -- both
     //         halves of the NJ / 2 maps from c0 on -- spread over its 48 MFMAs: a 16-byte LDS-DMA instruction costs the CU's address path
@@ -293,28 +260,15 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
     auto mfmas = [&](int buf, auto nj_tag, __amdgpu_buffer_rsrc_t gr, const unsigned (&vo)[2], int c0) {
         constexpr int NJ = decltype(nj_tag)::value;
         static_assert(NJ == 0 || NJ == 6 || NJ == 8, "jobs per M phase");
-        const float* ub = s_u + (wk * 2 + buf) * G::kU;
-#pragma unroll
-        for (int quad = 0; quad < 3; ++quad) {
-            const float* b_base = ub + ((quad * 4 + lk) * 4 * 16 + li) * 4;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(b_base + a * 64);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (quad == 0) acc[4 * a + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[quad][2 * a + (i >> 1)][i & 1], b[i], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    else acc[4 * a + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[quad][2 * a + (i >> 1)][i & 1], b[i], acc[4 * a + i], 0, 0, 0);
-                }
-                if constexpr (NJ > 0) {
-                    const int pair = quad * 4 + a;          // 12 (quad, a) pairs of 4 MFMAs: NJ = 6 -> behind every second, NJ = 8 -> behind two of three
-                    const bool here = NJ == 6 ? (pair & 1) == 1 : (pair % 3) != 1;
-                    if (here) {
-                        const int job = NJ == 6 ? pair / 2 : pair - (pair + 1) / 3;
-                        dma_map_half(gr, vo, c0 + (job >> 1), job & 1);
-                    }
+        wino3_mfmas(s_u + (wk * 2 + buf) * G::kU, lk, li, av, acc, [&](int pair) {
+            if constexpr (NJ > 0) {          // 12 (quad, a) pairs of 4 MFMAs: NJ = 6 -> behind every second, NJ = 8 -> behind two of three
+                const bool here = NJ == 6 ? (pair & 1) == 1 : (pair % 3) != 1;
+                if (here) {
+                    const int job = NJ == 6 ? pair / 2 : pair - (pair + 1) / 3;
+                    dma_map_half(gr, vo, c0 + (job >> 1), job & 1);
                 }
             }
-        }
+        });
     };
     using Tag0 = std::integral_constant<int, 0>;
     using Tag6 = std::integral_constant<int, 6>;
@@ -334,46 +288,10 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
         return c + d;
     };
 
-    // ---- E: output transform, layer l's ReLU mask + BN backward, accumulated over the layers; the step's sums join the wave's slot ----
-    auto read_bn = [&](int gq, int l) { return *reinterpret_cast<const f32x4*>(s_bn + 4 * (l * p.count + gq * 16 + li)); };
+    // ---- E: wino3_epilogue; the step's sums join the wave's slot ----
     auto epilogue = [&](int slot, const f32x4 bn) {
-        const f32x2 sb = {bn[0], bn[1]}, mr = {bn[2], bn[3]};          // (scale, beta), (mean, rstd)
-        const float rstd = bn[3];
-        f32x2 s1v = {0.f, 0.f}, s2v = {0.f, 0.f};
-        f32x2 minus1 = {-1.f, -1.f};
-        asm("" : "+v"(minus1));
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            f32x2 u0r[4], u1r[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const f32x2 m0 = {acc[c][2 * hh], acc[c][2 * hh + 1]}, m1 = {acc[4 + c][2 * hh], acc[4 + c][2 * hh + 1]};
-                const f32x2 m2 = {acc[8 + c][2 * hh], acc[8 + c][2 * hh + 1]}, m3 = {acc[12 + c][2 * hh], acc[12 + c][2 * hh + 1]};
-                u0r[c] = m0 + m1 + m2;
-                u1r[c] = __builtin_elementwise_fma(m2 + m3, minus1, m1);
-            }
-            const f32x2 d[2][2] = {{u0r[0] + u0r[1] + u0r[2], __builtin_elementwise_fma(u0r[2] + u0r[3], minus1, u0r[1])},
-                                   {u1r[0] + u1r[1] + u1r[2], __builtin_elementwise_fma(u1r[2] + u1r[3], minus1, u1r[1])}};
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                for (int ee = 0; ee < 2; ++ee) {
-                    const f32x2 x2 = {xc[r][hh][2 * ee], xc[r][hh][2 * ee + 1]};
-                    f32x2 xcen, z;
-                    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(xcen) : "v"(x2), "v"(mr));
-                    asm("v_pk_fma_f32 %0, %1, %2, %2 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(z) : "v"(xcen), "v"(sb));
-                    const f32x2 dz = {z[0] > 0.f ? d[r][0][ee] : 0.f, z[1] > 0.f ? d[r][1][ee] : 0.f};
-                    s1v += dz;
-                    s2v = __builtin_elementwise_fma(dz, xcen, s2v);
-                    f32x2 t2 = {total[r][hh][2 * ee], total[r][hh][2 * ee + 1]};
-                    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(t2) : "v"(dz), "v"(sb));
-                    total[r][hh][2 * ee] = t2[0];
-                    total[r][hh][2 * ee + 1] = t2[1];
-                }
-            }
-        }
-        float s1 = s1v[0] + s1v[1], s2 = s2v[0] + s2v[1];
-        s2 *= rstd;
+        float s1, s2;
+        wino3_epilogue(acc, xc, total, bn, s1, s2);
         s1 = rows_sum(s1);
         s2 = rows_sum(s2);
         if (lk == 0 && (EXP & 4) == 0) {
@@ -445,13 +363,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
     using V0 = std::integral_constant<int, 0>;
     using V4 = std::integral_constant<int, 4>;
     using V8 = std::integral_constant<int, 8>;
-    auto phase_end_m = [&]() {
-        __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0) only: DMA stays in flight across the barrier
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        stamp();
-    };
+    auto phase_end_m = [&]() { wino3_phase_end_m(); stamp(); };
 
     // ---- first tile: everything from scratch ----
     {
@@ -524,7 +436,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
                 phase_end_m();
                 // ---------------- V: E(gq, l), T(next step), the loads that trail the phase ----------------
                 if (l == 1) load_wf(gq);
-                epilogue(slot + l, read_bn(gq, l));
+                epilogue(slot + l, wino3_read_bn(s_bn, p.count, gq, l, li));
                 __builtin_amdgcn_sched_barrier(0);          // keep the transform's 24 patch reads (48 registers) behind the epilogue
                 if (l + 1 < NL) {
                     transform(l + 1);
@@ -573,7 +485,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
                 else mfmas(j & 1, Tag0{}, gr_next, vo_next, 0);
                 phase_end_m();
                 if (j == 0 && wk == 0) load_wf(gq);
-                epilogue(slot + j, read_bn(gq, l));
+                epilogue(slot + j, wino3_read_bn(s_bn, p.count, gq, l, li));
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + 1 < NL / 2) transform(l + 1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -624,19 +536,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino3p_kernel(const DgradBlockPa
         {
             // every step's epilogue lies behind a block barrier here (the next tile's opening barrier orders these reads before its
             // epilogues' stores).  One fp64 atomic per (worker, step, channel, sum): the 4 waves' partials added in a fixed order
-            if constexpr ((EXP & 4) == 0) {
-                for (int i = tid; i < 2 * nsteps * 32; i += G::kThreads) {
-                    const int w = i / (nsteps * 32), rem = i - w * nsteps * 32;
-                    const int s = rem >> 5, j2 = rem & 31;
-                    float* red = s_red + (w * G::kMaxSteps + s) * G::kRedStep + j2;
-                    const double v = static_cast<double>(red[0]) + static_cast<double>(red[32]) + static_cast<double>(red[64]) + static_cast<double>(red[96]);
-                    const int gi = s / NL;
-                    const int gq = gi < nfull ? 2 * gi + w : ngroups - 1;
-                    const int l = gi < nfull ? s - gi * NL : s - nfull * NL + w * (NL / 2);
-                    double* sc = l == 0 ? p.scratch[0] : l == 1 ? p.scratch[1] : l == 2 ? p.scratch[2] : p.scratch[3];
-                    atomicAdd(sc + bn_slot_offset(p.slot_stride) + grp_off / 2 + 2 * (gq * 16) + j2, v);
-                }
-            }
+            if constexpr ((EXP & 4) == 0) wino3_flush_sums<NL, G>(p, grp_off, tid, s_red, nsteps, nfull, ngroups);
             if (FW && (!has_next_tile || ++since_flush == G::kFlushTiles)) {
                 since_flush = 0;
                 for (int i = tid; i < p.count; i += G::kThreads) {

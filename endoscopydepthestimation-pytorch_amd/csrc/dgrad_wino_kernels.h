@@ -307,8 +307,7 @@ __global__ void __launch_bounds__(512, 2) dgrad_wino8_kernel(const DgradBlockPar
                     }
             }
             s2 *= rstd;
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) {
                 float* red = s_red + (buf * 2 + half) * G::kRed;
                 red[(w4 * 16 + li) * 2] = s1;

@@ -231,11 +231,7 @@ __global__ void __launch_bounds__(512, 2) td_dgrad_kernel(const ConvParams p, in
                     f32x4 o = ov[tt][nt];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float xc = xv[tt][nt][e] - bn[2];
-                        const float z = fmaf(xc, bn[0], bn[1]);
-                        const float dz = z > 0.f ? acc[tt][nt][e] : 0.f;
-                        s1 += dz;
-                        s2 += dz * (xc * bn[3]);
+                        const float dz = bn_relu_bwd_xhat(xv[tt][nt][e], acc[tt][nt][e], bn[0], bn[1], bn[2], bn[3], s1, s2);
                         o[e] = (accumulate ? o[e] : 0.f) + bn[0] * dz;
                     }
                     // (offset all in the vector register: with a scalar offset register the compiler does not insert the wait state a 16-byte
@@ -245,8 +241,7 @@ __global__ void __launch_bounds__(512, 2) td_dgrad_kernel(const ConvParams p, in
                 // over the wave's four 16-lane rows (pixel groups), then the wave's slot.  (__shfl_xor, not the v_permlane swaps of
                 // dgrad_wino3p_kernels.h: inline assembly right behind a 16-byte store is invisible to the compiler's hazard recogniser --
                 // a build with them overwrote the first dword of 0.1 % of the stores; the two LDS round trips are per pass here, not per step)
-                s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-                s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+                bn_rows_sum(s1, s2);
                 if (lk == 0) {          // the wave's slot runs over the block's whole run of tiles (owned: plain read-add-write, fp32; fp64 at the end)
                     typedef float f32x2 __attribute__((ext_vector_type(2)));
                     f32x2* slot = reinterpret_cast<f32x2*>(s_sum + (wave * C + co) * 2);
@@ -409,17 +404,12 @@ __global__ void __launch_bounds__(256) td_dgrad_small_kernel(const ConvParams p)
             f32x4 o = ov[tt][nt];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float xc = xv[tt][nt][e] - mean;
-                const float z = fmaf(xc, scale, beta);
-                const float dz = z > 0.f ? acc[tt][nt][e] : 0.f;
-                s1 += dz;
-                s2 += dz * (xc * rstd);
+                const float dz = bn_relu_bwd_xhat(xv[tt][nt][e], acc[tt][nt][e], scale, beta, mean, rstd, s1, s2);
                 o[e] = (accumulate ? o[e] : 0.f) + scale * dz;
             }
             *reinterpret_cast<f32x4*>(out_n + static_cast<int64_t>(co) * p.out_cs + P0 + (2 * wave + tt) * 16 + 4 * lk) = o;
         }
-        s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+        bn_rows_sum(s1, s2);
         if (lk == 0) { s_sum[wave][nt * 16 + li][0] = s1; s_sum[wave][nt * 16 + li][1] = s2; }
     }
     __syncthreads();

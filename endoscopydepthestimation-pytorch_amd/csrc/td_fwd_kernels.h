@@ -222,8 +222,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) td_fwd_kernel(const ConvParams 
 #pragma unroll
         for (int nt = 0; nt < G::kNT; ++nt) {
             float s1 = st1[nt], s2 = st2[nt];
-            s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+            bn_rows_sum(s1, s2);
             if (lk == 0) { s_sum[(wave * C + nt * 16 + li) * 2] = s1; s_sum[(wave * C + nt * 16 + li) * 2 + 1] = s2; }
         }
         __syncthreads();

@@ -347,8 +347,7 @@ __global__ void __launch_bounds__(kConvThreads, 2) wino4_fwd_kernel(const ConvPa
         }
     }
     if (p.out_sums) {
-        s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+        bn_rows_sum(s1, s2);
         if (lk == 0) {
             s_red[(wave * 16 + li) * 2] = s1;
             s_red[(wave * 16 + li) * 2 + 1] = s2;
