@@ -32,7 +32,7 @@
 
 namespace endo {
 
-enum InMode { IN_PLAIN = 0, IN_BNRELU = 1, IN_UPSAMPLE = 2, IN_UNPOOL = 3, IN_SUBPIX = 4 };
+enum InMode { IN_PLAIN = 0, IN_BNRELU = 1, IN_UPSAMPLE = 2, IN_UNPOOL = 3 };
 enum Epilogue { EPI_FWD = 0, EPI_FWD_POOL = 1, EPI_DGRAD_BN = 2, EPI_DGRAD_SUMPOOL = 3 };
 
 constexpr int kConvThreads = 256;
@@ -95,7 +95,6 @@ struct ConvParams {
     // caller tensors), parameter pointers do not move.  group_n == 0 means "not grouped" (one group of n samples).
     int group_n;
     int64_t gs, in_gs, out_gs;
-    int sub_c;        // IN_SUBPIX: real channels per sub-pixel phase (cin = 4 * sub_c pseudo-channels)
     // ---- the last dense layer of the network (wino4_fwd_kernel<true>): the final 1x1 convolution over the channels this launch streams
     // anyway -- fin_out[sample][pixel] = sum over the launch's input channels of fin_w[c] * x_raw[c][pixel] (no BN, no ReLU: finalConv reads the
     // raw concatenation, reference models.py:167, 186).  fin_out is a tape pointer: it moves with the group like `out`'s tape does (gs).

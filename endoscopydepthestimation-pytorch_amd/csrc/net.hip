@@ -388,58 +388,48 @@ __global__ void bn_bwd_finalize4_kernel(const BnFin4 a, int nl, float* __restric
     }
 }
 
-// Tap-summed weights of the transition-up sub-pixel phases (conv_dma_kernels.h, PH) in the compact layout the kernel
-// DMAs: out[a][ci][400] with, for row tap t in {0,1} and slot in [0,12): slot 0-2 = column tap 0 of the b = 0 tiles,
-// 3-8 = column tap 1 of all six tiles (b = 0 | b = 1), 9-11 = column tap 2 of the b = 1 tiles; 16 channels per tile.
-// Row phase 0 sees input rows (y-1, y): row tap 0 <- ky 0, 1 <- ky 1 + ky 2; row phase 1 sees (y, y+1): 0 <- ky 0 + ky 1,
-// 1 <- ky 2.  Column phases likewise: b = 0 sees (x-1, x), b = 1 sees (x, x+1).
+// Tap-summed weights of the transition-up forward in sub-pixel form (conv_dma_kernels.h, tu_fwd_subpix_kernel) in the layout the kernel
+// DMAs: out[ci][rc = 3 r + c][48] = W'[r][c][co][ci] = sum over ky in rows(r), kx in cols(c) of w[co][ci][ky][kx], with r, c in {-, 0, +}
+// and rows(-) = {0}, rows(0) = {0, 1, 2}, rows(+) = {2} (tu_tap_range); summed in fp32 in (ky, kx) order.  Couts past `cout` are zeros.
+__host__ __device__ inline void tu_tap_range(int r, int& k0, int& k1) { k0 = r == 2 ? 2 : 0; k1 = r == 0 ? 0 : 2; }
+
 __global__ void tu_phase_weights_kernel(const float* __restrict__ w, int cout, int cin, float* __restrict__ out) {
-    constexpr int kPhW = 2 * 12 * 16 + 16;
-    const int total = 2 * cin * 2 * 12 * 16;
+    const int total = cin * kTuW9;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int lane16 = i & 15;
-        const int slot = (i >> 4) % 12;
-        const int t = (i / (16 * 12)) & 1;
-        const int ci = (i / (16 * 12 * 2)) % cin;
-        const int a = i / (16 * 12 * 2 * cin);
-        int ctap, tile;                                     // column tap (0..2 on the low-res grid) and tile (0..5)
-        if (slot < 3) { ctap = 0; tile = slot; } else if (slot < 9) { ctap = 1; tile = slot - 3; } else { ctap = 2; tile = slot - 9 + 3; }
-        const int b = tile / 3, co = (tile % 3) * 16 + lane16;
+        const int co = i % 48;
+        const int rc = (i / 48) % 9;
+        const int ci = i / kTuW9;
         float v = 0.f;
         if (co < cout) {
             const float* src = w + (static_cast<int64_t>(co) * cin + ci) * 9;
-            // original rows / columns that fall on this low-res tap
-            const int ky0 = a == 0 ? (t == 0 ? 0 : 1) : (t == 0 ? 0 : 2), ky1 = a == 0 ? (t == 0 ? 0 : 2) : (t == 0 ? 1 : 2);
-            int kx0, kx1;
-            if (b == 0) { kx0 = ctap == 0 ? 0 : 1; kx1 = ctap == 0 ? 0 : 2; }          // b = 0: tap 0 <- kx 0, tap 1 <- kx 1 + kx 2
-            else { kx0 = ctap == 1 ? 0 : 2; kx1 = ctap == 1 ? 1 : 2; }                  // b = 1: tap 1 <- kx 0 + kx 1, tap 2 <- kx 2
+            int ky0, ky1, kx0, kx1;
+            tu_tap_range(rc / 3, ky0, ky1);
+            tu_tap_range(rc % 3, kx0, kx1);
             for (int ky = ky0; ky <= ky1; ++ky)
                 for (int kx = kx0; kx <= kx1; ++kx) v += src[ky * 3 + kx];
         }
-        out[(static_cast<int64_t>(a) * cin + ci) * kPhW + (t * 12 + slot) * 16 + lane16] = v;
+        out[i] = v;
     }
 }
 
-// Tap-summed weights of the transition-up DATA gradient in sub-pixel form (conv_dma_kernels.h, IN_SUBPIX):
-// out[pseudo = (alpha, beta, co)][208] = [(tyi, txi)][ci] (+ pad).  With u = a + 1 - ky the row offset of dY seen from low-res
-// row y:  alpha = 0: tyi 0 (row y) <- ky 1 + ky 2, tyi 1 (row y+1) <- ky 0;  alpha = 1: tyi 0 (row y-1) <- ky 2,
-// tyi 1 (row y) <- ky 0 + ky 1.  Columns likewise.
+// The same nine matrices for the transition-up DATA gradient (conv_dma_kernels.h, tu_dgrad_subpix_kernel), transposed:
+// out[co][rc = 3 r + c][48] = W'[r][c][co][ci].  Cins past `cin` are zeros.
 __global__ void tu_subpix_dgrad_weights_kernel(const float* __restrict__ w, int cout, int cin, float* __restrict__ out) {
-    const int pitch = 4 * cin + 16;
-    const int total = 4 * cout * 4 * cin;
+    const int total = cout * kTuW9;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int ci = i % cin;
-        const int tap = (i / cin) & 3;
-        const int co = (i / (4 * cin)) % cout;
-        const int ph = i / (4 * cin * cout);
-        const int alpha = ph >> 1, beta = ph & 1, tyi = tap >> 1, txi = tap & 1;
-        const int ky0 = alpha == 0 ? (tyi == 0 ? 1 : 0) : (tyi == 0 ? 2 : 0), ky1 = alpha == 0 ? (tyi == 0 ? 2 : 0) : (tyi == 0 ? 2 : 1);
-        const int kx0 = beta == 0 ? (txi == 0 ? 1 : 0) : (txi == 0 ? 2 : 0), kx1 = beta == 0 ? (txi == 0 ? 2 : 0) : (txi == 0 ? 2 : 1);
-        const float* src = w + (static_cast<int64_t>(co) * cin + ci) * 9;
+        const int ci = i % 48;
+        const int rc = (i / 48) % 9;
+        const int co = i / kTuW9;
         float v = 0.f;
-        for (int ky = ky0; ky <= ky1; ++ky)
-            for (int kx = kx0; kx <= kx1; ++kx) v += src[ky * 3 + kx];
-        out[static_cast<int64_t>(ph * cout + co) * pitch + tap * cin + ci] = v;
+        if (ci < cin) {
+            const float* src = w + (static_cast<int64_t>(co) * cin + ci) * 9;
+            int ky0, ky1, kx0, kx1;
+            tu_tap_range(rc / 3, ky0, ky1);
+            tu_tap_range(rc % 3, kx0, kx1);
+            for (int ky = ky0; ky <= ky1; ++ky)
+                for (int kx = kx0; kx <= kx1; ++kx) v += src[ky * 3 + kx];
+        }
+        out[i] = v;
     }
 }
 
@@ -911,20 +901,19 @@ static int tu_fwd(const Ctx& c, int level, int src_level, int src_c0, const Conv
     ProfScope prof(kProfConv3x3Up, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3),
                    4.0 * c.nt() * c.net->lv[level].plane * (cv.cin / 4.0 + cv.cout));
     if (c.fwd->tu_subpix[level]) {
-        // sub-pixel form: the two row phases on the low-resolution grid, 4/9 of the MACs.  The tap-summed weights
+        // sub-pixel form: nine products per low-resolution pixel, 1/4 of the direct MACs.  The tap-summed weights
         // go to the (idle) split-K scratch of group 0's tape; they are shared by all groups.
         float* w3 = c.tape + c.net->partial_off;
-        tu_phase_weights_kernel<<<(2 * cv.cin * 384 + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, w3);
+        tu_phase_weights_kernel<<<(cv.cin * kTuW9 + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, w3);
         ENDO_LAUNCH_CHECK();
-        // ONE launch for both row phases (gridDim.y = 2, conv_dma_kernel<.., PH = 2>)
         ConvParams p{};
         fill_grid(c, p, src_level);                     // the launch runs over the low-resolution pixels
         fill_in(c, p, c.act(src_level), src_level, src_c0, cv.cin);
-        p.wgt = w3; p.w_cout = 2 * cv.cout; p.w_cin = cv.cin;
+        p.wgt = w3; p.w_cout = cv.cout; p.w_cin = cv.cin;
         p.bias = c.params + cv.b;
         fill_out(c, p, c.act(level), level, 0, cv.cout);
         p.out_sums = c.out_sums(level, 0);
-        return launch_conv_dma_vec<3, 4, 6, IN_PLAIN, EPI_FWD, 2, 4, 2, 1, 4, 0, 0, 2>(p, c.stream);
+        return launch_tu_fwd_subpix(p, c.stream);
     }
     ConvParams p{};
     fill_grid(c, p, level);
@@ -1419,20 +1408,19 @@ static int tu_bwd(const Ctx& c, int level, int src_level, int src_c0, const Conv
         fill_out(c, p, c.gbuf(src_level), src_level, src_c0, cv.cin);
         return launch_conv_dma_auto<3, 4, 3, IN_PLAIN, EPI_DGRAD_SUMPOOL, 4>(p, c.stream);
     }
-    // sub-pixel form on the low-resolution grid: the four stride-2 phases of dY are 4 x 48 pseudo input channels of a
-    // 3x3 convolution that uses 2x2 of its taps per phase (4/9 of the MACs); the weights have their own scratch (the n-split scratch belongs to the side stream)
+    // sub-pixel form on the low-resolution grid: the four stride-2 phases of dY, transformed at read time into 9 x 48 pseudo input
+    // channels (1/4 of the MACs); the weights have their own scratch (the n-split scratch belongs to the side stream)
     float* wd = c.gradws + c.net->tuw_scratch_off;
-    tu_subpix_dgrad_weights_kernel<<<(16 * cv.cout * cv.cin + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, wd);
+    tu_subpix_dgrad_weights_kernel<<<(cv.cout * kTuW9 + 255) / 256, 256, 0, c.stream>>>(c.params + cv.w, cv.cout, cv.cin, wd);
     ENDO_LAUNCH_CHECK();
     ConvParams p{};
     fill_grid(c, p, src_level);
-    fill_in(c, p, c.gbuf(level), level, 0, 4 * cv.cout);      // strides of the full-resolution gradient buffer
-    p.sub_c = cv.cout;
-    p.wgt = wd; p.w_cout = cv.cin; p.w_cin = 4 * cv.cout;
+    fill_in(c, p, c.gbuf(level), level, 0, cv.cout);          // strides of the full-resolution gradient buffer
+    p.wgt = wd; p.w_cout = cv.cin; p.w_cin = cv.cout;
     fill_out(c, p, c.gbuf(src_level), src_level, src_c0, cv.cin);
-    if (form == TuDgrad::Subpix32x8) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 2, 4, 2, 1, 1>(p, c.stream);
-    if (form == TuDgrad::Subpix16x8) return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 2, 2, 1, 1>(p, c.stream);
-    return launch_conv_dma_vec<3, 8, 3, IN_SUBPIX, EPI_FWD, 1, 1, 2, 1, 1>(p, c.stream);
+    if (form == TuDgrad::Subpix32x8) return launch_tu_dgrad_subpix<2, 4>(p, c.stream);
+    if (form == TuDgrad::Subpix16x8) return launch_tu_dgrad_subpix<1, 2>(p, c.stream);
+    return launch_tu_dgrad_subpix<1, 1>(p, c.stream);
 }
 
 static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -1488,7 +1476,7 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     net->scratch_bytes = net->slot_stride * 8 * kBnSlots;
     net->wg_scratch_off = (net->scratch_off + align_up(net->scratch_bytes, 256)) / 4;
     net->tuw_scratch_off = net->wg_scratch_off + std::max(std::max(kNsScratchFloats, kSpScratchFloats), 4 * kF34ScratchFloats);          // four slices: the layers of a dense block reduce in one launch
-    net->wd_off = align_up(net->tuw_scratch_off + 4 * kNew * (4 * kNew + 16), 64);
+    net->wd_off = align_up(net->tuw_scratch_off + kNew * kTuW9, 64);
     net->gplane_off = align_up(net->wd_off + tb.wino_dgrad_floats, 64);
     net->bias_parts_off = net->gplane_off + align_up(static_cast<int64_t>(n) * h * w, 64);
     net->bias_parts_floats = static_cast<int64_t>(kBiasPartChannels) * n * groups * 32;
