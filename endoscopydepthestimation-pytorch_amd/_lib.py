@@ -144,6 +144,12 @@ SIGNATURES = {
     "endo_prof_read": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_L),
                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "endo_prof_family_name": (ctypes.c_char_p, [_I]),
+    "endo_registration_tile": (_I, [_I]),
+    "endo_registration_prepared_bytes": (_L, [_L]),
+    "endo_registration_workspace_bytes": (_L, [_L, _L]),
+    "endo_registration_prepare": (_I, [_P, _L, _L, _P, _P, _L, _P]),
+    "endo_registration_match": (_I, [_P, _L, _L, _P, _P, _P, _L, _L, _P, ctypes.c_double, _P, _P, _P, _P, _L, _P]),
+    "endo_similarity_apply": (_I, [_P, _L, _L, _P, _P, _P]),
 }
 
 # the backward bricks of the 16-bit-storage family (one launch of endo_net16_bwd each), over bf16 and over half

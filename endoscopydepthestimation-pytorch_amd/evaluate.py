@@ -23,6 +23,11 @@ pairs (dataset.TrainingBatches(transform=None, shuffle=False): the reference's S
 
 The reference cannot run this phase as written: it unpacks 17 items from the loader's 18 (evaluate.py:167-171) and needs cv2,
 torchvision, plyfile and tensorboardX.
+
+What the reference leaves to another tool (its README, step 4: register the predicted point clouds to the CT model with a similarity
+transformation "to calculate residual errors") is registration_errors over the points / offsets any of the outputs above return, and
+run_registration_phase: the posed test outputs per batch, each frame's cloud registered to a registration.TargetModel from the tracker's
+pose as its start, ``registration_errors.csv`` and the registered clouds.
 """
 
 import os
@@ -32,7 +37,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, display, models, utils
+from . import _lib, display, models, registration, utils
 from .train_step import mask_mul
 
 
@@ -398,3 +403,108 @@ def run_validation_phase(model, batches, out_dir, write_png=True, write_ply=True
         if finite[:, side].any():
             means[side] = metrics[finite[:, side], side].astype(np.float64).mean(axis=0)
     return {"pairs": int(metrics.shape[0]), "metrics": metrics, "mean_metrics": means, "non_finite": int((~finite).sum())}
+
+
+def _initial_transform(initial):
+    """(scale, rotation, translation) of a start given as None (the identity), a registration.Registration, a 4 x 4 matrix whose upper
+    left block is scale * R, or a (scale, rotation, translation) tuple."""
+    if initial is None:
+        return 1.0, np.eye(3), np.zeros(3)
+    if isinstance(initial, registration.Registration):
+        return initial.scale, initial.rotation, initial.translation
+    if isinstance(initial, (tuple, list)) and len(initial) == 3:
+        return float(initial[0]), np.asarray(initial[1], np.float64).reshape(3, 3), np.asarray(initial[2], np.float64).reshape(3)
+    matrix = np.asarray(initial, np.float64)
+    if matrix.shape != (4, 4):
+        raise ValueError("initial is None, a Registration, a 4 x 4 matrix or (scale, rotation, translation)")
+    det = float(np.linalg.det(matrix[:3, :3]))
+    if not det > 0.0:
+        raise ValueError("initial's 3 x 3 block must be scale * rotation with a positive determinant")
+    scale = det ** (1.0 / 3.0)
+    return scale, matrix[:3, :3] / scale, matrix[:3, 3].copy()
+
+
+def registration_errors(points, offsets, target, initial=None, merged=False, **register_kwargs):
+    """The residual errors of point clouds against a model (the reference's README, step 4): ``points`` / ``offsets`` as test_outputs,
+    posed_test_outputs and validation_outputs return them (rows of x, y, z, r, g, b on the device; the host list of row offsets), target
+    a registration.TargetModel (or rows to make one of, prepared once here), initial the start of every frame (_initial_transform;
+    None: the identity), register_kwargs those of registration.register.  Returns a list with one registration.Registration per frame,
+    None for a frame without points; merged=True: one Registration of all rows together.  A frame whose matches do not determine a
+    similarity raises registration.register's ValueError."""
+    if not isinstance(target, registration.TargetModel):
+        target = registration.TargetModel(target)
+    scale, rotation, translation = _initial_transform(initial)
+    offsets = [int(v) for v in offsets]
+    if merged:
+        if offsets[-1] == offsets[0]:
+            return None
+        return registration.register(points[offsets[0]:offsets[-1]], target, scale, rotation, translation, **register_kwargs)
+    return [registration.register(points[a:b], target, scale, rotation, translation, **register_kwargs) if b > a else None
+            for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+REGISTRATION_COLUMNS = ("name", "points", "inliers", "scale", "mean", "rms", "max", "iterations", "converged")
+
+
+def _write_registered(ready, path, rows, ply_text):
+    ready.synchronize()
+    utils.write_point_cloud(path, rows.numpy(), text=ply_text)
+
+
+def run_registration_phase(model, frames, translation_dict, rotation_dict, target, out_dir, initial=None, write_ply=True, ply_text=True,
+                           point_cloud_downsampling=1, min_threshold=None, max_threshold=None, writers=4, **register_kwargs):
+    """The posed test outputs of a sequence (posed_test_outputs per batch, as run_posed_test_phase runs them: clouds in the tracker's
+    frame), then every frame's cloud registered to ``target`` (a registration.TargetModel, e.g. TargetModel.from_ply of the CT model)
+    from ``initial`` (the tracker-to-model start, _initial_transform) with registration.register(**register_kwargs).  Writes
+    ``registration_errors.csv`` in ``out_dir``: one line per frame of name, points, inliers (the rows within the last distance cap),
+    scale, mean, rms and max of their distances, iterations, converged; a frame without kept pixels, with non-finite coordinates (equal
+    kept depths) or whose matches do not determine a similarity has points and empty fields.  write_ply: ``registered_<name>.ply``, the
+    frame's cloud under its registration (endo_similarity_apply; colours kept), on run_test_phase's writer pool.
+    Returns a dictionary: frames, registered (their number), failed (the names of the other frames), rows (the table's rows) and rms
+    (the root mean square of the inliers' distances over all registered frames; NaN without one)."""
+    names_ahead = getattr(frames, "image_file_names", None)
+    if names_ahead is not None:
+        for name in names_ahead:
+            key = os.path.basename(str(name))[-12:-4]
+            translation_dict[key], rotation_dict[key]          # KeyError before anything runs
+    if not isinstance(target, registration.TargetModel):
+        target = registration.TargetModel(target)
+    scale, rotation, translation = _initial_transform(initial)
+    out_dir = str(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    rows, failed = [], []
+    count, squares, inliers = 0, 0.0, 0
+    with _WriterPool(writers) as pool:
+        for batch in frames:
+            names = list(batch["names"])
+            out = posed_test_outputs(model, batch, [rotation_dict[name] for name in names], [translation_dict[name] for name in names],
+                                     is_hsv=getattr(frames, "is_hsv", False), point_cloud_downsampling=point_cloud_downsampling,
+                                     min_threshold=min_threshold, max_threshold=max_threshold)
+            count += len(names)
+            offsets, ranges = out["offsets"], out["ranges"]
+            for f, name in enumerate(names):
+                cloud = out["points"][offsets[f]:offsets[f + 1]]
+                result = None
+                if ranges[f, 0] < ranges[f, 1]:          # neither empty nor of equal kept depths (non-finite coordinates)
+                    try:
+                        result = registration.register(cloud, target, scale, rotation, translation, **register_kwargs)
+                    except ValueError:
+                        result = None
+                if result is None:
+                    failed.append(name)
+                    rows.append((name, int(cloud.shape[0]), "", "", "", "", "", "", ""))
+                    continue
+                rows.append((name, int(cloud.shape[0]), result.count, repr(result.scale), repr(result.mean), repr(result.rms),
+                             repr(result.max), result.iterations, int(result.converged)))
+                squares += result.rms * result.rms * result.count
+                inliers += result.count
+                if write_ply:
+                    moved = registration.similarity_apply(cloud, result.scale, result.rotation, result.translation)
+                    pool.submit(_write_registered, os.path.join(out_dir, "registered_{}.ply".format(name)),
+                                moved.to("cpu", non_blocking=True), ply_text)
+    with open(os.path.join(out_dir, "registration_errors.csv"), "w") as f:
+        f.write(",".join(REGISTRATION_COLUMNS) + "\n")
+        for row in rows:
+            f.write(",".join(str(v) for v in row) + "\n")
+    return {"frames": count, "registered": count - len(failed), "failed": failed, "rows": rows,
+            "rms": float(np.sqrt(squares / inliers)) if inliers else float("nan")}

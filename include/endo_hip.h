@@ -1036,6 +1036,45 @@ int64_t endo_net16_offset(const endo_net16* net, int what, int index);
 int endo_net16_bwd(endo_net16* net, const float* params, const void* tape, const float* grad_out, float* grads, void* ws, int training,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Similarity registration by iterative closest point (csrc/registration.hip) -- the reference's README, step 4: after evaluate.py,
+ * "apply a registration algorithm that is able to estimate a similarity transformation to register the predicted point clouds to the
+ * corresponding CT model to calculate residual errors".  The reference has no code for it.  The per-point work is here; the 3 x 3
+ * similarity estimate is the host's, in fp64, from the 20 sums (registration.py).  An additive part of ABI 7.
+ *
+ * Point rows are fp32 x, y, z at a row stride in floats (>= 3: (P, 6) clouds and plain (K, 3) arrays alike), on the device.
+ * `transform` (13 doubles: scale, the rotation row-major, the translation; a row becomes scale * R row + t), `centre` and
+ * `source_centre` (3 doubles) are HOST arrays, read during the call; all must be finite.
+ *
+ * endo_registration_tile(which): 0 = source rows per block of the search, 1 = target rows per LDS stage (the two macros below).
+ * endo_registration_prepared_bytes(k): size of the prepared copy of a k-row target, 1 <= k <= 2^31 - 1 (-1 outside).
+ * endo_registration_prepare: writes the whole prepared copy: the centre, then per row the centred coordinates (fp64 difference, rounded
+ *   to fp32) as the search's operand (-2 x, -2 y, -2 z, |.|^2), padded to a multiple of the target tile with rows that never win.
+ *   STATE: read by every later endo_registration_match on it.
+ * endo_registration_match: one ICP iteration.  Each of the m source rows is moved by `transform` in fp64, taken relative to the target
+ *   centre and rounded to fp32; index[i] (int32) is the row of `target` nearest to it by the score |t|^2 - 2 x.t in fp32 (exact brute
+ *   force over all k rows; of equal scores the lowest index; the target's coordinates must be finite and their squares within fp32); distance[i] (fp32) is the distance from the moved point to that row,
+ *   formed in fp64 by direct differences against `target` (the caller's rows, the ones `prepared` was made from) and rounded once.
+ *   sums (20 doubles, device), over the rows whose fp64 distance is <= cap (+inf keeps all; NaN is ENDO_E_BADARG):
+ *   [0] n, [1] sum d, [2] sum d^2, [3] max d (0 when n = 0), [4..6] sum s, [7..9] sum t, [10] sum |s|^2, [11 + 3 i + j] sum t_i s_j,
+ *   s = the UNMOVED source row - source_centre, t = the matched target row - the target centre, all in fp64.  Per-block partials in the
+ *   workspace are added in a fixed order, without floating-point atomics: equal inputs give equal bytes.
+ *   workspace: endo_registration_workspace_bytes(m, k) bytes, SCRATCH.
+ * endo_similarity_apply: out row = scale * R row + t in fp64, rounded to fp32; columns 3 .. stride - 1 are copied.  out has the
+ *   stride of rows and may be rows itself.
+ * ------------------------------------------------------------------------------------------- */
+#define ENDO_REGISTRATION_SOURCE_TILE 64
+#define ENDO_REGISTRATION_TARGET_TILE 1024
+int endo_registration_tile(int which);
+int64_t endo_registration_prepared_bytes(int64_t k);
+int64_t endo_registration_workspace_bytes(int64_t m, int64_t k);
+int endo_registration_prepare(const float* target, int64_t target_stride, int64_t k, const double* centre, void* prepared,
+                              int64_t prepared_bytes, void* stream);
+int endo_registration_match(const float* source, int64_t source_stride, int64_t m, const double* transform, const void* prepared,
+                            const float* target, int64_t target_stride, int64_t k, const double* source_centre, double cap,
+                            int32_t* index, float* distance, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int endo_similarity_apply(const float* rows, int64_t stride, int64_t m, const double* transform, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
