@@ -185,6 +185,41 @@ inline hipError_t launch_dyn(void (*kernel)(Params...), dim3 grid, dim3 block, s
     return hipGetLastError();
 }
 
+// A stream of the handle's own beside the caller's ("main") stream -- both network families run their weight gradients on one.  Work issued
+// on it after fork_after(main) follows everything issued on main so far; after join_into(main), main follows everything issued on it.
+// A pass joins on EVERY exit path once it may have forked (its forking part runs in a lambda, the join behind it): an error return never
+// leaves the side stream running against the caller's buffers.
+struct SideStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+
+    // on first use, on the caller's device: the stream and both events, or (an error) none of them
+    hipError_t create() {
+        if (stream) return hipSuccess;
+        SideStream s;
+        hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming);
+        if (e == hipSuccess) *this = s;
+        else s.destroy();
+        return e;
+    }
+    hipError_t fork_after(hipStream_t main) const {
+        const hipError_t e = hipEventRecord(ev_fork, main);
+        return e != hipSuccess ? e : hipStreamWaitEvent(stream, ev_fork, 0);
+    }
+    hipError_t join_into(hipStream_t main) const {
+        const hipError_t e = hipEventRecord(ev_join, stream);
+        return e != hipSuccess ? e : hipStreamWaitEvent(main, ev_join, 0);
+    }
+    void destroy() {
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (stream) (void)hipStreamDestroy(stream);
+        *this = SideStream();
+    }
+};
+
 }  // namespace endo
 
 // geometry.hip / losses.hip, used by head.hip: the public entry points with their reduction tables' memset optional (zero = 0: the caller has

@@ -31,7 +31,7 @@
 #include "wino4_fwd_kernels.h"
 #include "dgrad_wino_kernels.h"
 #include "dgrad_wino3_kernels.h"
-
+#include "net_arch.h"
 
 namespace endo {
 
@@ -39,25 +39,13 @@ int run_dgrad_wino3_nl4(const DgradBlockParams& p, const float* const* u, hipStr
 bool dgrad_wino3p_applies(const DgradBlockParams& p);
 int run_dgrad_wino3p_nl4(const DgradBlockParams& p, const float* const* u, int blocks, double* fw_parts, int* blocks_used, hipStream_t stream);
 
-constexpr int kGrowth = 12;
-constexpr int kLayers = 4;
-constexpr int kFirst = 48;
-constexpr int kLevels = 5;
-constexpr int kNew = kGrowth * kLayers;   // 48
-constexpr float kBnEps = 1.0e-5f;
-constexpr float kBnMomentum = 0.1f;
 constexpr int kSideStreamFromLevel = 0;      // weight gradients of levels >= this run on the side stream (in-job A/B: 0 -> -4.7 %, 1 -> -3 %, 2 -> -1.8 % step time)
 
-struct ConvP { int64_t w, b; int cout, cin, ks; int64_t u; int64_t ud; };      // u / ud: offsets of the layer's Winograd-domain forward / data-gradient weights (dense layers), floats
-struct BnP { int64_t g, b; int c; int64_t run; int64_t saved; };   // run: offset in bn_running; saved: offset (pairs) in saved/scratch
+// what this family adds to the network's modules (net_arch.h)
+struct ConvP : ConvDesc { int64_t u = -1, ud = -1; };      // u / ud: offsets of the layer's Winograd-domain forward / data-gradient weights (dense layers), floats
+using BnP = BnDesc;                              // saved statistics and backward scratch: pairs from `before`
 
-struct Table {
-    ConvP first, final_;
-    ConvP down_conv[kLevels][kLayers], td_conv[kLevels], bott_conv[kLayers], tu_conv[kLevels], up_conv[kLevels][kLayers];
-    BnP down_bn[kLevels][kLayers], td_bn[kLevels], bott_bn[kLayers], up_bn[kLevels][kLayers];
-    std::vector<int64_t> param_offsets;   // 210 tensors in .parameters() order
-    std::vector<BnP*> bn_order;           // 49 BN layers in module order
-    int64_t param_floats = 0, bn_floats = 0, bn_width_total = 0;
+struct Table : ModuleTable<ConvP> {
     WinoWeightTable wino;                 // the 44 dense layers' forward weights in Winograd form (wino_fwd_kernels.h)
     WinoWeightTable wino4;                // the same layers in F(4x4, 3x3) form (wino4_fwd_kernels.h): u_off in floats of ITS buffer
     int64_t wino4_floats = 0;
@@ -66,77 +54,33 @@ struct Table {
     int64_t wino_dgrad_floats = 0;
 };
 
-inline int down_in(int level) { return kFirst + kNew * level; }          // C_L
-inline int level_channels(int level) { return level < kLevels ? 144 + down_in(level) : 288 + kNew; }
+inline int level_channels(int level) { return level < kLevels ? 144 + down_in(level) : kBottIn + kNew; }
 
 static const Table& table() {
     static Table* t = [] {
         Table* tb = new Table();
-        int64_t off = 0;
-        auto conv = [&](ConvP& c, int cout, int cin, int ks) {
-            c.cout = cout; c.cin = cin; c.ks = ks; c.u = -1; c.ud = -1;
-            c.w = off; tb->param_offsets.push_back(off); off += static_cast<int64_t>(cout) * cin * ks * ks;
-            c.b = off; tb->param_offsets.push_back(off); off += cout;
-        };
-        int64_t run = 0, saved = 0;
-        auto bn = [&](BnP& b, int c) {
-            b.c = c;
-            b.g = off; tb->param_offsets.push_back(off); off += c;
-            b.b = off; tb->param_offsets.push_back(off); off += c;
-            b.run = run; run += 2 * c;
-            b.saved = saved; saved += c;
-            tb->bn_order.push_back(&b);
-        };
-        conv(tb->first, kFirst, 3, 3);
-        for (int l = 0; l < kLevels; ++l)
-            for (int j = 0; j < kLayers; ++j) { bn(tb->down_bn[l][j], down_in(l) + kGrowth * j); conv(tb->down_conv[l][j], kGrowth, down_in(l) + kGrowth * j, 3); }
-        for (int l = 0; l < kLevels; ++l) { bn(tb->td_bn[l], down_in(l) + kNew); conv(tb->td_conv[l], down_in(l) + kNew, down_in(l) + kNew, 1); }
-        for (int j = 0; j < kLayers; ++j) { bn(tb->bott_bn[j], 288 + kGrowth * j); conv(tb->bott_conv[j], kGrowth, 288 + kGrowth * j, 3); }
-        for (int i = 0; i < kLevels; ++i) conv(tb->tu_conv[i], kNew, kNew, 3);
-        for (int i = 0; i < kLevels; ++i) {
-            const int l = kLevels - 1 - i;
-            for (int j = 0; j < kLayers; ++j) { const int cin = 96 + down_in(l) + kGrowth * j; bn(tb->up_bn[i][j], cin); conv(tb->up_conv[i][j], kGrowth, cin, 3); }
+        // Winograd-domain weights of the dense layers, layer after layer in module order -- forward: kWinoUStride floats per input channel;
+        // data gradient: per dense block, the 16-channel groups of its base channels, for each of its layers
+        WinoWeightTable& wt = tb->wino;
+        WinoDgradTable& wd = tb->wino_dgrad;
+        wt.layers = 0; wt.start[0] = 0;
+        wd.layers = 0; wd.start[0] = 0;
+        for (const ConvDesc& m : arch().convs) {
+            if (!is_dense(m.role)) continue;
+            ConvP& c = tb->conv(m);
+            const int l = wt.layers++;
+            c.u = tb->wino_floats;
+            wt.cin[l] = c.cin; wt.cout[l] = c.cout; wt.w_off[l] = c.w; wt.u_off[l] = c.u;
+            wt.start[l + 1] = wt.start[l] + c.cin * 16;
+            tb->wino_floats += static_cast<int64_t>(c.cin) * kWinoUStride;
+            wd.layers++;
+            c.ud = tb->wino_dgrad_floats;
+            wd.cin[l] = c.cin; wd.groups[l] = dense_base(m) / 16; wd.w_off[l] = c.w; wd.u_off[l] = c.ud;
+            wd.start[l + 1] = wd.start[l] + 16 * wd.groups[l] * 12;
+            tb->wino_dgrad_floats += static_cast<int64_t>(wd.groups[l]) * kWinoDgradSlice;
         }
-        conv(tb->final_, 1, 192, 1);
-        tb->param_floats = off;
-        tb->bn_floats = run;
-        tb->bn_width_total = saved;
-        {   // Winograd-domain weights of the dense layers: kWinoUStride floats per input channel, layer after layer
-            WinoWeightTable& wt = tb->wino;
-            wt.layers = 0; wt.start[0] = 0;
-            int64_t uoff = 0;
-            auto add = [&](ConvP& c) {
-                const int l = wt.layers++;
-                c.u = uoff;
-                wt.cin[l] = c.cin; wt.cout[l] = c.cout; wt.w_off[l] = c.w; wt.u_off[l] = uoff;
-                wt.start[l + 1] = wt.start[l] + c.cin * 16;
-                uoff += static_cast<int64_t>(c.cin) * kWinoUStride;
-            };
-            for (int l = 0; l < kLevels; ++l) for (int j = 0; j < kLayers; ++j) add(tb->down_conv[l][j]);
-            for (int j = 0; j < kLayers; ++j) add(tb->bott_conv[j]);
-            for (int i = 0; i < kLevels; ++i) for (int j = 0; j < kLayers; ++j) add(tb->up_conv[i][j]);
-            tb->wino_floats = uoff;
-            tb->wino4 = wt;
-            int64_t u4 = 0;
-            for (int l = 0; l < wt.layers; ++l) { tb->wino4.u_off[l] = u4; u4 += static_cast<int64_t>(wt.cin[l]) * kW4UStride; }
-            tb->wino4_floats = u4;
-        }
-        {   // data-gradient weights in Winograd form: per dense block, the 16-channel groups of its base channels, for each of its layers
-            WinoDgradTable& wd = tb->wino_dgrad;
-            wd.layers = 0; wd.start[0] = 0;
-            int64_t uoff = 0;
-            auto add = [&](ConvP& c, int base) {
-                const int l = wd.layers++;
-                c.ud = uoff;
-                wd.cin[l] = c.cin; wd.groups[l] = base / 16; wd.w_off[l] = c.w; wd.u_off[l] = uoff;
-                wd.start[l + 1] = wd.start[l] + 16 * wd.groups[l] * 12;
-                uoff += static_cast<int64_t>(wd.groups[l]) * kWinoDgradSlice;
-            };
-            for (int l = 0; l < kLevels; ++l) for (int j = 0; j < kLayers; ++j) add(tb->down_conv[l][j], down_in(l));
-            for (int j = 0; j < kLayers; ++j) add(tb->bott_conv[j], 288);
-            for (int i = 0; i < kLevels; ++i) for (int j = 0; j < kLayers; ++j) add(tb->up_conv[i][j], 96 + down_in(kLevels - 1 - i));
-            tb->wino_dgrad_floats = uoff;
-        }
+        tb->wino4 = wt;
+        for (int l = 0; l < wt.layers; ++l) { tb->wino4.u_off[l] = tb->wino4_floats; tb->wino4_floats += static_cast<int64_t>(wt.cin[l]) * kW4UStride; }
         return tb;
     }();
     return *t;
@@ -178,8 +122,7 @@ struct endo_net {
     // Weight gradients run on a side stream: a layer's wgrad depends only on its prepared dY and the forward tape, nothing on the
     // backward chain depends on it (it only adds into the flat gradient), so it overlaps the data-gradient chain -- which at the
     // coarse levels is a string of launches too small to fill the chip.  Forked after every prep_dy, joined once at the end.
-    hipStream_t wstream;
-    hipEvent_t ev_fork, ev_join;
+    SideStream side;
     // kernel-form / precision options of THIS network (endo_net_set_option): two networks in one process never change each
     // other's arithmetic, and a thread stepping one model is not affected by another thread configuring a second one
     int opt[ENDO_OPT_COUNT];
@@ -646,10 +589,9 @@ struct Ctx {
     // context of the weight-gradient side stream, ordered after everything issued so far on the main stream
     int fork_wgrad(Ctx& side, int level) const {
         side = *this;
-        if (!net->wstream || !bwd->overlap || level < kSideStreamFromLevel) return 0;          // run in line
-        ENDO_CHECK(hipEventRecord(net->ev_fork, stream));
-        ENDO_CHECK(hipStreamWaitEvent(net->wstream, net->ev_fork, 0));
-        side.stream = net->wstream;
+        if (!net->side.stream || !bwd->overlap || level < kSideStreamFromLevel) return 0;          // run in line
+        ENDO_CHECK(net->side.fork_after(stream));
+        side.stream = net->side.stream;
         return 0;
     }
     float* act(int level) const { return tape + net->lv[level].act; }
@@ -658,8 +600,8 @@ struct Ctx {
     // where a kernel accumulates the per-channel sum / sum^2 of what it stores: nowhere in inference mode (running statistics are
     // used, reference evaluate.py:317-345), which drops the reductions and their atomics from every epilogue
     double* out_sums(int level, int channel) const { return training ? sums(level) + 2 * channel : nullptr; }
-    float* saved(const BnP& b) const { return tape + net->saved_off + 2 * b.saved; }
-    double* scratch(const BnP& b) const { return reinterpret_cast<double*>(reinterpret_cast<char*>(gradws) + net->scratch_off) + 2 * b.saved; }
+    float* saved(const BnP& b) const { return tape + net->saved_off + 2 * b.before; }
+    double* scratch(const BnP& b) const { return reinterpret_cast<double*>(reinterpret_cast<char*>(gradws) + net->scratch_off) + 2 * b.before; }
     float* pq_p(int level) const { return gradws + net->pq_off + 2 * net->lv[level].pq; }
     float* pq_q(int level) const { return pq_p(level) + net->lv[level].t; }
     uint8_t* idx(int level) const { return reinterpret_cast<uint8_t*>(tape) + net->idx_off[level]; }
@@ -733,9 +675,9 @@ struct DenseBlock { int level, ic0, c0; const BnP* bn; const ConvP* cv; bool bas
 static DenseBlock dense_block(int b) {
     const Table& tb = table();
     if (b < kLevels) return {b, 48, down_in(b), tb.down_bn[b], tb.down_conv[b], false};
-    if (b == kLevels) return {kLevels, 0, 288, tb.bott_bn, tb.bott_conv, true};
+    if (b == kLevels) return {kLevels, 0, kBottIn, tb.bott_bn, tb.bott_conv, true};
     const int i = b - kLevels - 1, l = kLevels - 1 - i;
-    return {l, 0, 96 + down_in(l), tb.up_bn[i], tb.up_conv[i], l > 0};
+    return {l, 0, up_in(l), tb.up_bn[i], tb.up_conv[i], l > 0};
 }
 static long tile_count(const Ctx& c, int level, int tx, int ty) {          // tx x ty pixel tiles of a launch over the level, partial ones included
     const auto& lv = c.net->lv[level];
@@ -1079,7 +1021,7 @@ static ConvParams td_dgrad_params(const Ctx& c, int level) {
 // weight gradient of the transition up that wrote channels [0, 48) of `level`; subpix: as the sub-pixel form takes it (it walks the low-resolution grid)
 static WgradParams tu_wgrad_params(const Ctx& c, int level, bool subpix) {
     const ConvP& cv = table().tu_conv[kLevels - 1 - level];
-    const int src_level = level + 1, src_c0 = src_level == kLevels ? 288 : 96 + down_in(src_level);
+    const int src_level = level + 1, src_c0 = src_level == kLevels ? kBottIn : up_in(src_level);
     const auto& lv = c.net->lv[level];
     const auto& sv = c.net->lv[src_level];
     WgradParams p{};
@@ -1438,7 +1380,6 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     endo_net* net = new (std::nothrow) endo_net();
     if (!net) return ENDO_E_BADARG;
     net->n = n; net->h = h; net->w = w; net->groups = groups;
-    net->wstream = nullptr; net->ev_fork = nullptr; net->ev_join = nullptr;
     net->last_fwd = nullptr; net->last_bwd = nullptr;
     default_options(net->opt);
     int64_t off = 0, sums = 0, pq = 0;
@@ -1453,7 +1394,7 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     }
     const int64_t acts = off;
     net->pre_off = off; off += align_up(static_cast<int64_t>(n) * h * w, 64);
-    net->saved_off = off; off += align_up(2 * tb.bn_width_total, 64);
+    net->saved_off = off; off += align_up(2 * arch().bn_width, 64);
     int64_t byte_off = off * 4;
     for (int l = 0; l < kLevels; ++l) {
         net->idx_off[l] = byte_off;
@@ -1472,7 +1413,7 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     net->pq_off = acts;
     net->pq_floats = 2 * pq;
     net->scratch_off = align_up((acts + net->pq_floats) * 4, 256);
-    net->slot_stride = align_up(tb.bn_width_total * 2, 32);
+    net->slot_stride = align_up(arch().bn_width * 2, 32);
     net->scratch_bytes = net->slot_stride * 8 * kBnSlots;
     net->wg_scratch_off = (net->scratch_off + align_up(net->scratch_bytes, 256)) / 4;
     net->tuw_scratch_off = net->wg_scratch_off + std::max(std::max(kNsScratchFloats, kSpScratchFloats), 4 * kF34ScratchFloats);          // four slices: the layers of a dense block reduce in one launch
@@ -1481,16 +1422,13 @@ extern "C" int endo_net_create_grouped(endo_net** out, int n, int h, int w, int 
     net->bias_parts_off = net->gplane_off + align_up(static_cast<int64_t>(n) * h * w, 64);
     net->bias_parts_floats = static_cast<int64_t>(kBiasPartChannels) * n * groups * 32;
     {   // the BiasParts limits against THIS network's table: one prep_dy launch per convolution with a bias, its output channels in all
-        int launches = 1, channels = tb.first.cout;
-        for (int l = 0; l < kLevels; ++l) {
-            for (int j = 0; j < kLayers; ++j) { launches += 2; channels += tb.down_conv[l][j].cout + tb.up_conv[l][j].cout; }
-            launches += 2; channels += tb.td_conv[l].cout + tb.tu_conv[l].cout;
-        }
-        for (int j = 0; j < kLayers; ++j) { ++launches; channels += tb.bott_conv[j].cout; }
+        int launches = 0, channels = 0;
+        for (const ConvDesc& m : arch().convs)
+            if (m.role != Role::Final) { ++launches; channels += m.cout; }
         if (launches > kBiasPartLaunches || channels > kBiasPartChannels) { delete net; return ENDO_E_UNSUPPORTED; }
     }
     net->fw_parts_off = net->bias_parts_off + align_up(net->bias_parts_floats, 64);
-    net->gradws_floats = net->fw_parts_off + 2 * static_cast<int64_t>(kFwPartBlocks) * 192;
+    net->gradws_floats = net->fw_parts_off + 2 * static_cast<int64_t>(kFwPartBlocks) * kFinalIn;
     // one stride for both buffers keeps the kernels' group arithmetic to a single number; the caller allocates
     // groups * gs floats for each when groups > 1 (the two sizes differ by a few per cent)
     net->gs = align_up(net->tape_floats > net->gradws_floats ? net->tape_floats : net->gradws_floats, 64);
@@ -1516,40 +1454,35 @@ extern "C" int endo_net_get_option(const endo_net* net, int option_id) {
 
 extern "C" void endo_net_destroy(endo_net* net) {
     if (!net) return;
-    if (net->ev_fork) (void)hipEventDestroy(net->ev_fork);
-    if (net->ev_join) (void)hipEventDestroy(net->ev_join);
-    if (net->wstream) (void)hipStreamDestroy(net->wstream);
+    net->side.destroy();
     delete net->last_fwd;
     delete net->last_bwd;
     delete net;
 }
-extern "C" int64_t endo_net_param_floats(void) { return table().param_floats; }
-extern "C" int64_t endo_net_bn_floats(void) { return table().bn_floats; }
+extern "C" int64_t endo_net_param_floats(void) { return arch().param_floats; }
+extern "C" int64_t endo_net_bn_floats(void) { return arch().bn_floats; }
 extern "C" int64_t endo_net_tape_floats(const endo_net* net) { return !net ? 0 : (net->groups > 1 ? net->groups * net->gs : net->tape_floats); }
 extern "C" int64_t endo_net_gradws_floats(const endo_net* net) { return !net ? 0 : (net->groups > 1 ? net->groups * net->gs : net->gradws_floats); }
 extern "C" int endo_net_groups(const endo_net* net) { return net ? net->groups : 0; }
 extern "C" int64_t endo_net_group_stride(const endo_net* net) { return net ? net->gs : 0; }
 extern "C" int64_t endo_net_param_offset(int index) {
-    const Table& tb = table();
-    if (index < 0 || index >= static_cast<int>(tb.param_offsets.size())) return -1;
-    return tb.param_offsets[index];
+    if (index < 0 || index >= static_cast<int>(arch().param_offsets.size())) return -1;
+    return arch().param_offsets[index];
 }
 extern "C" int64_t endo_net_bn_offset(int bn_index, int which) {
-    const Table& tb = table();
-    if (bn_index < 0 || bn_index >= static_cast<int>(tb.bn_order.size()) || which < 0 || which > 1) return -1;
-    return tb.bn_order[bn_index]->run + which * tb.bn_order[bn_index]->c;
+    if (bn_index < 0 || bn_index >= static_cast<int>(arch().bns.size()) || which < 0 || which > 1) return -1;
+    return arch().bns[bn_index].run + which * arch().bns[bn_index].c;
 }
 extern "C" int endo_net_level_channels(int level) { return (level < 0 || level > kLevels) ? -1 : level_channels(level); }
 extern "C" int64_t endo_net_act_offset(const endo_net* net, int level) { return (!net || level < 0 || level > kLevels) ? -1 : net->lv[level].act; }
 
 extern "C" int64_t endo_net_tape_offset(const endo_net* net, int what, int index) {
     if (!net) return -1;
-    const Table& tb = table();
     switch (what) {
         case ENDO_TAPE_PRE: return net->pre_off;
         case ENDO_TAPE_BN_SAVED:
-            if (index < 0 || index >= static_cast<int>(tb.bn_order.size())) return -1;
-            return net->saved_off + 2 * tb.bn_order[index]->saved;
+            if (index < 0 || index >= static_cast<int>(arch().bns.size())) return -1;
+            return net->saved_off + 2 * arch().bns[index].before;
         case ENDO_TAPE_POOL:
             if (index < 0 || index >= kLevels) return -1;
             return net->idx_off[index];
@@ -1593,7 +1526,7 @@ extern "C" int endo_net_fwd(endo_net* net, const float* params, float* bn_runnin
     for (int b = 0; b < kBlocks; ++b) {          // down path: block, transition down; bottleneck; up path: transition up, block
         if (b > kLevels) {
             const int i = b - kLevels - 1, l = kLevels - 1 - i;
-            rc = tu_fwd(c, l, l + 1, (i == 0) ? 288 : 96 + down_in(l + 1), tb.tu_conv[i]);
+            rc = tu_fwd(c, l, l + 1, (i == 0) ? kBottIn : up_in(l + 1), tb.tu_conv[i]);
             if (rc) return rc;
         }
         for (int j = 0; j < kLayers; ++j) {
@@ -1607,11 +1540,11 @@ extern "C" int endo_net_fwd(endo_net* net, const float* params, float* bn_runnin
     }
     {
         const auto& lv = net->lv[0];
-        const int c_first = plan.fuse_final ? 96 + down_in(0) + kGrowth * (kLayers - 1) : 0;          // 180: the last layer's launch has summed channels [0, 180) into `pre`
-        ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * 192, 4.0 * c.nt() * lv.plane * (194 - c_first));
+        const int c_first = plan.fuse_final ? up_in(0) + kGrowth * (kLayers - 1) : 0;          // 180: the last layer's launch has summed channels [0, 180) into `pre`
+        ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * kFinalIn, 4.0 * c.nt() * lv.plane * (kFinalIn + 2 - c_first));
         int bx = static_cast<int>((lv.plane / 4 + 255) / 256);
         bx = bx < 1 ? 1 : bx;
-        final_fwd_kernel<<<dim3(bx, c.nt()), 256, 0, c.stream>>>(c.act(0), lv.t * lv.plane, static_cast<int>(lv.plane), 192,
+        final_fwd_kernel<<<dim3(bx, c.nt()), 256, 0, c.stream>>>(c.act(0), lv.t * lv.plane, static_cast<int>(lv.plane), kFinalIn,
                                                                  params + tb.final_.w, params + tb.final_.b, tape + net->pre_off, out,
                                                                  net->n, net->gs, c_first);
         ENDO_LAUNCH_CHECK();
@@ -1631,11 +1564,7 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
     if (net->last_bwd) *net->last_bwd = plan;
     BiasParts bias_parts{};
     c.bias_parts = &bias_parts;
-    if (!net->wstream) {          // side stream of the weight gradients (see endo_net), created on first use on the caller's device
-        ENDO_CHECK(hipStreamCreateWithFlags(&net->wstream, hipStreamNonBlocking));
-        ENDO_CHECK(hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming));
-        ENDO_CHECK(hipEventCreateWithFlags(&net->ev_join, hipEventDisableTiming));
-    }
+    ENDO_CHECK(net->side.create());          // side stream of the weight gradients (see endo_net), created on first use on the caller's device
     // zero the deferred-term tables and the BN reduction scratch
     for (int g = 0; g < net->groups; ++g)
         ENDO_CHECK(hipMemsetAsync(gradws + g * net->gs + net->pq_off, 0,
@@ -1647,6 +1576,7 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         dgrad_wino_weights_kernel<<<(tb.wino_dgrad.start[tb.wino_dgrad.layers] + 255) / 256, 256, 0, c.stream>>>(tb.wino_dgrad, params, gradws + net->wd_off, layout1_blocks);
         ENDO_LAUNCH_CHECK();
     }
+    auto body = [&]() -> int {          // everything that may fork the side stream: the join below is reached on every exit path (SideStream)
     int rc;
     const FinalVirt virt{gradws + net->gplane_off, params + tb.final_.w, grads + tb.final_.w};
     {   // final convolution (what the last up block forms itself: BwdPlan::use_virt)
@@ -1659,13 +1589,13 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
             const int c_first = plan.c_first;          // (the channels below it are the persistent base pass's)
             int by = static_cast<int>((lv.plane + 256 * 16 - 1) / (256 * 16));       // 16 pixels per thread
             by = by < 1 ? 1 : (by > 16 ? 16 : by);
-            ProfScope prof(kProfConvFinal, cw.stream, 2.0 * c.nt() * lv.plane * (192 - c_first), 4.0 * c.nt() * lv.plane * (192 - c_first + 2));
-            final_bwd_weight_kernel<<<dim3(192 - c_first + 1, by, c.nt()), 256, 0, cw.stream>>>(grad_out, tape + net->pre_off, c.act(0), lv.t * lv.plane,
-                                                                         static_cast<int>(lv.plane), 192, net->n, net->gs, grads + tb.final_.w,
+            ProfScope prof(kProfConvFinal, cw.stream, 2.0 * c.nt() * lv.plane * (kFinalIn - c_first), 4.0 * c.nt() * lv.plane * (kFinalIn - c_first + 2));
+            final_bwd_weight_kernel<<<dim3(kFinalIn - c_first + 1, by, c.nt()), 256, 0, cw.stream>>>(grad_out, tape + net->pre_off, c.act(0), lv.t * lv.plane,
+                                                                         static_cast<int>(lv.plane), kFinalIn, net->n, net->gs, grads + tb.final_.w,
                                                                          grads + tb.final_.b, c_first);
             ENDO_LAUNCH_CHECK();
         }
-        ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * 192, 4.0 * c.nt() * lv.plane * (materialise + 2));
+        ProfScope prof(kProfConvFinal, c.stream, 2.0 * c.nt() * lv.plane * kFinalIn, 4.0 * c.nt() * lv.plane * (materialise + 2));
         if (plan.use_virt) {
             int bx = static_cast<int>((lv.plane + 1023) / 1024);
             final_g_kernel<<<dim3(bx, c.nt()), 256, 0, c.stream>>>(grad_out, tape + net->pre_off, gradws + net->gplane_off, static_cast<int>(lv.plane), net->n, net->gs);
@@ -1687,7 +1617,7 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         if (rc) return rc;
         if (b > kLevels) {
             const int i = b - kLevels - 1, l = kLevels - 1 - i;
-            rc = tu_bwd(c, l, l + 1, (i == 0) ? 288 : 96 + down_in(l + 1), tb.tu_conv[i]);
+            rc = tu_bwd(c, l, l + 1, (i == 0) ? kBottIn : up_in(l + 1), tb.tu_conv[i]);
             if (rc) return rc;
         }
     }
@@ -1721,11 +1651,11 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         bias_reduce_kernel<<<dim3(bias_parts.table.n, 8), 256, 0, c.stream>>>(bias_parts.table);
         ENDO_LAUNCH_CHECK();
     }
-    if (net->wstream) {          // join: the caller's stream continues only after every weight gradient has landed
-        ENDO_CHECK(hipEventRecord(net->ev_join, net->wstream));
-        ENDO_CHECK(hipStreamWaitEvent(c.stream, net->ev_join, 0));
-    }
     return 0;
+    };
+    const int rc_body = body();
+    ENDO_CHECK(net->side.join_into(c.stream));          // the caller's stream continues only after every weight gradient has landed
+    return rc_body;
 }
 
 // ---- the plan, readable (include/endo_hip.h: endo_net_last_plan / endo_net_plan_query / endo_net_plan_name) ----

@@ -2,15 +2,15 @@
 // drive, and on top of them FCDenseNet57 (reference models.py:171-187) over bf16 level buffers in 32-channel blocks: endo_net16_fwd
 // (training mode: batch statistics + running-statistics update; inference) and endo_net16_bwd (parameter gradients into the fp32
 // family's flat gradient buffer).  One or two sample groups per call (a training pair's two frames, each with its own statistics).
-// A separate network implementation next to the fp32 one (net.hip): same parameters, same tensors at the boundary.
+// A second schedule of the network next to the fp32 one (net.hip), with its own kernels and its own level-buffer layout: same parameters,
+// same tensors at the boundary.  What the two must agree on they share: the modules, their widths and their places in the flat parameter
+// and BatchNorm tensors (net_arch.h), and the side stream of the weight gradients (common.h).
 #include <vector>
 
 #include "bf16_conv_kernels.h"
 #include "bf16_bwd_kernels.h"
 #include "bf16_dgrad_block_kernels.h"
-
-extern "C" int64_t endo_net_param_offset(int index);
-extern "C" int64_t endo_net_bn_offset(int bn_index, int which);
+#include "net_arch.h"
 
 // the half-storage build (net16h.hip) exports the network entry points as endo_net16h_* and the single-kernel bricks as endo_f16_* (B16() below)
 #ifdef ENDO16_HALF
@@ -22,91 +22,64 @@ extern "C" int64_t endo_net_bn_offset(int bn_index, int which);
 namespace endo {
 inline namespace ENDO16_NS {
 
-constexpr int k16Levels = 5, k16Layers = 4, k16Growth = 12, k16First = 48, k16New = 48;
-inline int c16_down_in(int level) { return k16First + k16New * level; }
-constexpr int k16Blk = 32;                                                    // channels per block of a level buffer (bf16_conv_kernels.h)
-inline int c16_skip(int level) { return c16_down_in(level) + k16New; }        // channels a level hands to the up path (models.py:176-177)
+constexpr int k16Blk = 32;                                              // channels per block of a level buffer (bf16_conv_kernels.h)
+inline int c16_skip(int level) { return down_in(level) + kNew; }        // channels a level hands to the up path (models.py:176-177)
 // Level buffer, l < 5: [0, S) the down path (dense-block input, then its 48 new maps: the skip), [S, S + 48) the transition-up output,
 // [S + 48, S + 96) the up block's new maps, S = c16_skip(l); every dense layer reads a run that starts at channel 0.  The reference
 // concatenates [transition-up output, skip] (models.py:183): the up layers' parameters are indexed through (rot = 48, rot_n = S + 48).
 // Bottleneck: [0, 288) input, [288, 336) new.  Padded to whole blocks.
 inline int c16_level_channels(int level) {
-    const int c = level < k16Levels ? 96 + c16_skip(level) : 288 + k16New;
+    const int c = level < kLevels ? 96 + c16_skip(level) : kBottIn + kNew;
     return (c + k16Blk - 1) / k16Blk * k16Blk;
 }
 
 // w16 / w16d: element offsets of the forward / data-gradient (transposed, flipped; -1 = none) bf16 weights
 // base / koff: a dense layer's data-gradient weights below row `base` (the block's base channels) sit at k = koff + co -- the K window
 // of bf16_dgrad_block_kernel -- and at k = co from there on
-struct Conv16 { int64_t w, b; int cout, cin, ks, nt; int64_t w16; int rot, rot_n; int64_t w16d; int base, koff; };      // w16: element offset of the converted weights
-struct Bn16 { int64_t g, b; int c; int64_t run_mean, run_var; int64_t saved; };
+struct Conv16 : ConvDesc { int nt; int64_t w16; int rot, rot_n; int64_t w16d; int base, koff; };      // w16: element offset of the converted weights
+using Bn16 = BnDesc;          // (mean, rstd) and the backward sums: 2 * before
 
-// the reference's module order (models.py:100-170, the order of .parameters()): offsets come from the fp32 family's own table
-struct Table16 {
-    Conv16 first, final_;
-    Conv16 down_conv[k16Levels][k16Layers], td_conv[k16Levels], bott_conv[k16Layers], tu_conv[k16Levels], up_conv[k16Levels][k16Layers];
-    Bn16 down_bn[k16Levels][k16Layers], td_bn[k16Levels], bott_bn[k16Layers], up_bn[k16Levels][k16Layers];
-    std::vector<Conv16*> convs;
+// elements of a convolution's weights W[cout][cin][ks][ks] in the kernels' layout -- forward: output channels in groups of nt x 16
+inline int w16_nt(int cout) { return cout <= 16 ? 1 : 3; }
+inline int64_t w16_fwd_elems(int cout, int cin, int ks) {
+    const int nt = w16_nt(cout);
+    const int64_t groups = (cout + nt * 16 - 1) / (nt * 16), chunks = (cin + kBfKC - 1) / kBfKC;
+    return chunks * groups * ks * ks * nt * 16 * 32;
+}
+// data gradient: a convolution over the gradient, cout' = cin (48-wide groups), K = cout
+inline int64_t w16_dgrad_elems(int cout, int cin, int ks) {
+    const int64_t groups = (cin + 47) / 48, chunks = (cout + kBfKC - 1) / kBfKC;
+    return chunks * groups * ks * ks * 3 * 16 * 32;
+}
+inline int w16_cin_k(int cin) { return cin < 4 ? 4 : cin; }          // the first convolution's 3 input channels travel as 4 (+ 4 zero) of an 8-channel record
+
+struct Table16 : ModuleTable<Conv16> {
+    std::vector<Conv16*> convs;           // the MFMA convolutions (all but the final one)
     int64_t w16_elems = 0, w16d_elems = 0, saved_floats = 0;
-    std::vector<Conv16*> dconvs;          // the convolutions with a data gradient (all but the first)
-    std::vector<Bn16*> bns;               // module order
+    std::vector<Conv16*> dconvs;          // those with a data gradient (all but the first)
 };
 
 static const Table16& table16() {
     static Table16* t = [] {
         Table16* tb = new Table16();
-        int pi = 0, bi = 0;
-        int64_t saved = 0;
-        auto conv = [&](Conv16& c, int cout, int cin, int ks, bool mfma) {
-            c.cout = cout; c.cin = cin; c.ks = ks; c.nt = cout <= 16 ? 1 : 3;
-            c.w = endo_net_param_offset(pi++); c.b = endo_net_param_offset(pi++);
-            c.w16 = -1; c.rot = 0; c.rot_n = 0; c.w16d = -1; c.base = 0; c.koff = 0;
-            if (mfma && cin >= 4) {          // as a convolution over the gradient: cout' = cin (48-wide groups), K = cout
+        const int koffs[kLayers] = {0, 12, 8, 20};          // 12 j - 8 u0_j, u0 = {0, 0, 2, 2} (bf16_dgrad_block_kernels.h)
+        for (const ConvDesc& m : arch().convs) {
+            Conv16& c = tb->conv(m);
+            c.nt = w16_nt(m.cout); c.w16 = -1; c.rot = 0; c.rot_n = 0; c.w16d = -1; c.base = 0; c.koff = 0;
+            // the up path reads [transition-up output, skip] from a buffer that holds the skip first (c16_level_channels)
+            if (m.role == Role::Up || m.role == Role::Final) { c.rot = kNew; c.rot_n = c16_skip(m.level) + kNew; }
+            if (is_dense(m.role)) { c.base = dense_base(m); c.koff = koffs[m.j]; }
+            if (m.role == Role::Final) continue;          // not an MFMA convolution
+            if (m.cin >= 4) {
                 c.w16d = tb->w16d_elems;
-                const int64_t groups = (cin + 47) / 48, chunks = (cout + kBfKC - 1) / kBfKC;
-                tb->w16d_elems += chunks * groups * ks * ks * 3 * 16 * 32;
+                tb->w16d_elems += w16_dgrad_elems(m.cout, m.cin, m.ks);
                 tb->dconvs.push_back(&c);
             }
-            if (mfma) {
-                const int cin_k = cin < 4 ? 4 : cin;          // the first convolution's 3 input channels travel as 4 (+ 4 zero) of an 8-channel record
-                c.w16 = tb->w16_elems;
-                const int64_t groups = (cout + c.nt * 16 - 1) / (c.nt * 16), chunks = (cin_k + kBfKC - 1) / kBfKC;
-                tb->w16_elems += chunks * groups * ks * ks * c.nt * 16 * 32;
-                tb->convs.push_back(&c);
-            }
-        };
-        auto bn = [&](Bn16& b, int c) {
-            b.c = c;
-            b.g = endo_net_param_offset(pi++); b.b = endo_net_param_offset(pi++);
-            b.run_mean = endo_net_bn_offset(bi, 0); b.run_var = endo_net_bn_offset(bi, 1); ++bi;
-            b.saved = saved; saved += 2 * c;
-            tb->bns.push_back(&b);
-        };
-        const int koffs[k16Layers] = {0, 12, 8, 20};          // 12 j - 8 u0_j, u0 = {0, 0, 2, 2} (bf16_dgrad_block_kernels.h)
-        conv(tb->first, k16First, 3, 3, true);
-        for (int l = 0; l < k16Levels; ++l)
-            for (int j = 0; j < k16Layers; ++j) {
-                bn(tb->down_bn[l][j], c16_down_in(l) + k16Growth * j); conv(tb->down_conv[l][j], k16Growth, c16_down_in(l) + k16Growth * j, 3, true);
-                tb->down_conv[l][j].base = c16_down_in(l); tb->down_conv[l][j].koff = koffs[j];
-            }
-        for (int l = 0; l < k16Levels; ++l) { bn(tb->td_bn[l], c16_down_in(l) + k16New); conv(tb->td_conv[l], c16_down_in(l) + k16New, c16_down_in(l) + k16New, 1, true); }
-        for (int j = 0; j < k16Layers; ++j) {
-            bn(tb->bott_bn[j], 288 + k16Growth * j); conv(tb->bott_conv[j], k16Growth, 288 + k16Growth * j, 3, true);
-            tb->bott_conv[j].base = 288; tb->bott_conv[j].koff = koffs[j];
+            c.w16 = tb->w16_elems;
+            tb->w16_elems += w16_fwd_elems(m.cout, w16_cin_k(m.cin), m.ks);
+            tb->convs.push_back(&c);
         }
-        for (int i = 0; i < k16Levels; ++i) conv(tb->tu_conv[i], k16New, k16New, 3, true);
-        for (int i = 0; i < k16Levels; ++i) {
-            const int l = k16Levels - 1 - i;
-            for (int j = 0; j < k16Layers; ++j) {
-                const int cin = 96 + c16_down_in(l) + k16Growth * j;
-                bn(tb->up_bn[i][j], cin); conv(tb->up_conv[i][j], k16Growth, cin, 3, true);
-                tb->up_conv[i][j].rot = k16New; tb->up_conv[i][j].rot_n = c16_skip(l) + k16New;
-                tb->up_conv[i][j].base = c16_skip(l) + k16New; tb->up_conv[i][j].koff = koffs[j];
-            }
-        }
-        conv(tb->final_, 1, 192, 1, false);
-        tb->final_.rot = k16New; tb->final_.rot_n = c16_skip(0) + k16New;
-        tb->saved_floats = saved;
+        tb->saved_floats = 2 * arch().bn_width;
         return tb;
     }();
     return *t;
@@ -120,6 +93,19 @@ struct W16Table {
     int cout[63], cin[63], cin_k[63], ks[63], nt[63], rot[63], rot_n[63], base[63], koff[63];
     int dgrad;          // 1: data-gradient form: row = input channel of the layer, k = its cout, taps flipped
 };
+
+// appends a layer's forward weights, or (t.dgrad) its data-gradient weights, where the table's sizes put them (cv.w16 / cv.w16d); t starts zeroed
+static void w16_append(W16Table& t, const Conv16& cv) {
+    const int l = t.layers++;
+    t.w[l] = cv.w; t.ks[l] = cv.ks; t.rot[l] = cv.rot; t.rot_n[l] = cv.rot_n;
+    if (t.dgrad) {
+        t.out[l] = cv.w16d; t.cout[l] = cv.cin; t.cin[l] = cv.cout; t.cin_k[l] = cv.cout; t.nt[l] = 3; t.base[l] = cv.base; t.koff[l] = cv.koff;
+        t.start[l + 1] = t.start[l] + w16_dgrad_elems(cv.cout, cv.cin, cv.ks);
+    } else {
+        t.out[l] = cv.w16; t.cout[l] = cv.cout; t.cin[l] = cv.cin; t.cin_k[l] = w16_cin_k(cv.cin); t.nt[l] = cv.nt;
+        t.start[l + 1] = t.start[l] + w16_fwd_elems(cv.cout, t.cin_k[l], cv.ks);
+    }
+}
 
 __global__ void __launch_bounds__(256) bf16_all_weights_kernel(const W16Table t, const float* __restrict__ params, uint16_t* __restrict__ w16) {
     const int64_t total = t.start[t.layers];
@@ -249,15 +235,12 @@ extern "C" int B16(unpack_nhwc)(const void* in, float* x, int n, int c, int h, i
 }
 extern "C" int64_t B16(conv_weight_elems)(int cout, int cin, int ks) {
     if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3)) return -1;
-    const int nt = cout <= 16 ? 1 : 3;
-    const int64_t groups = (cout + nt * 16 - 1) / (nt * 16), chunks = (cin + kBfKC - 1) / kBfKC;
-    return chunks * groups * ks * ks * nt * 16 * 32;
+    return w16_fwd_elems(cout, cin, ks);
 }
 
 extern "C" int B16(conv_weights)(const float* w, int cout, int cin, int ks, void* out, void* stream) {
     if (!w || !out || B16(conv_weight_elems)(cout, cin, ks) < 0) return ENDO_E_BADARG;
-    const int nt = cout <= 16 ? 1 : 3;
-    bf16_conv_weights_kernel<<<256, 256, 0, static_cast<hipStream_t>(stream)>>>(w, cout, cin, ks, nt, static_cast<uint16_t*>(out), 0, 0);
+    bf16_conv_weights_kernel<<<256, 256, 0, static_cast<hipStream_t>(stream)>>>(w, cout, cin, ks, w16_nt(cout), static_cast<uint16_t*>(out), 0, 0);
     ENDO_LAUNCH_CHECK();
     return 0;
 }
@@ -296,19 +279,18 @@ int up8(int v) { return (v + 7) & ~7; }
 // data-gradient weights of a layer W[cout][cin][ks][ks]: the convolution over the gradient has cin output rows in groups of 48 and K = cout
 extern "C" int64_t B16(dgrad_weight_elems)(int cout, int cin, int ks) {
     if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3)) return -1;
-    const int64_t groups = (cin + 47) / 48, chunks = (cout + kBfKC - 1) / kBfKC;
-    return chunks * groups * ks * ks * 3 * 16 * 32;
+    return w16_dgrad_elems(cout, cin, ks);
 }
 
 extern "C" int B16(dgrad_weights)(const float* w, int cout, int cin, int ks, int rot, int rot_n, int base, int koff, void* out, void* stream) {
     if (!w || !out || B16(dgrad_weight_elems)(cout, cin, ks) < 0 || !rot_ok(rot, rot_n, cin)) return ENDO_E_BADARG;
     // rows below `base` are stored as bf16_dgrad_block_kernel's LDS image: one K-chunk, the layer's couts at k = koff + co
     if (base < 0 || base > cin || koff < 0 || (base > 0 && (ks != 3 || (base % 48) || koff + cout > kBfKC))) return ENDO_E_BADARG;
+    Conv16 cv{};          // the layer alone: weights at w, converted to out
+    cv.cout = cout; cv.cin = cin; cv.ks = ks; cv.rot = rot; cv.rot_n = rot_n; cv.base = base; cv.koff = koff;
     W16Table t{};
-    t.layers = 1; t.dgrad = 1;
-    t.start[0] = 0; t.start[1] = B16(dgrad_weight_elems)(cout, cin, ks);
-    t.w[0] = 0; t.out[0] = 0; t.cout[0] = cin; t.cin[0] = cout; t.cin_k[0] = cout; t.ks[0] = ks; t.nt[0] = 3;
-    t.rot[0] = rot; t.rot_n[0] = rot_n; t.base[0] = base; t.koff[0] = koff;
+    t.dgrad = 1;
+    w16_append(t, cv);
     bf16_all_weights_kernel<<<1024, 256, 0, static_cast<hipStream_t>(stream)>>>(t, w, static_cast<uint16_t*>(out));
     ENDO_LAUNCH_CHECK();
     return 0;
@@ -442,9 +424,9 @@ struct endo_net16 {
     int n, h, w;               // n: all samples of a call = groups x gn
     int gn, groups;            // sample groups: each has its own BatchNorm batch statistics (bf16_conv_kernels.h)
     int64_t gs_saved, gs_sums; // floats / doubles between the groups' (mean, rstd) tables and forward sums (the backward sums: gs_saved doubles)
-    struct Level { int h, w, t; int64_t plane; int64_t act; int64_t sums; } lv[k16Levels + 1];      // act: bytes, sums: doubles (from sums_off)
+    struct Level { int h, w, t; int64_t plane; int64_t act; int64_t sums; } lv[kLevels + 1];      // act: bytes, sums: doubles (from sums_off)
     int64_t in_off;            // bytes: the packed input [n][h][w][8] bf16
-    int64_t idx_off[k16Levels];
+    int64_t idx_off[kLevels];
     int64_t pre_off;           // bytes: final pre-activation fp32
     int64_t saved_off;         // bytes: BN (mean, rstd) fp32
     int64_t sums_off, sums_bytes;
@@ -452,11 +434,11 @@ struct endo_net16 {
     int64_t tape_bytes;
     // backward workspace (endo_net16_bwd): gradient buffers with the geometry of the level buffers, the deferred BatchNorm terms P, Q
     // per level channel, the BatchNorm backward sums per layer, the data-gradient weights, the weight-gradient partials
-    int64_t ws_d[k16Levels + 1];          // bytes
-    int64_t ws_pq[k16Levels + 1];         // bytes: floats [2][t]
+    int64_t ws_d[kLevels + 1];          // bytes
+    int64_t ws_pq[kLevels + 1];         // bytes: floats [2][t]
     int64_t ws_bnsums;                    // bytes: doubles, layer at its `saved` offset; kBnSlots copies, bn_slot_stride doubles apart
     int64_t bn_slot_stride;
-    int64_t ws_gsum[k16Levels + 1];       // bytes: doubles [t][2], pixel sums of the total gradient per level channel (bf16_prep_dy_kernel)
+    int64_t ws_gsum[kLevels + 1];       // bytes: doubles [t][2], pixel sums of the total gradient per level channel (bf16_prep_dy_kernel)
     int64_t ws_zero_begin, ws_zero_end;   // everything but the level-0 gradient buffer starts at zero
     int64_t ws_w16d;                      // bytes
     int64_t ws_partial;                   // bytes
@@ -465,8 +447,7 @@ struct endo_net16 {
     int64_t ws_bytes;
     // the weight gradients read only finished tensors (forward activations, a prepared gradient range) and nothing waits for them but
     // the optimizer: they run on a side stream, forked after every prep_dy and joined once at the end (as in the fp32 family)
-    hipStream_t wstream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    SideStream side;
     int use_wstream = 1;
 };
 
@@ -479,14 +460,14 @@ extern "C" int N16(create)(endo_net16** out, int n_per_group, int h, int w, int 
     net->n = n; net->h = h; net->w = w; net->gn = n_per_group; net->groups = groups;
     auto align = [](int64_t v) { return (v + 255) / 256 * 256; };
     int64_t off = 0, sums = 0;
-    for (int l = 0; l <= k16Levels; ++l) {
+    for (int l = 0; l <= kLevels; ++l) {
         auto& lv = net->lv[l];
         lv.h = h >> l; lv.w = w >> l; lv.t = c16_level_channels(l); lv.plane = static_cast<int64_t>(lv.h) * lv.w;
         lv.act = off; off += align(static_cast<int64_t>(n) * lv.plane * lv.t * 2);
         lv.sums = sums; sums += 2 * lv.t;
     }
     net->in_off = off; off += align(static_cast<int64_t>(n) * net->lv[0].plane * 16);
-    for (int l = 0; l < k16Levels; ++l) { net->idx_off[l] = off; off += align(static_cast<int64_t>(n) * net->lv[l + 1].plane * (c16_down_in(l) + k16New)); }
+    for (int l = 0; l < kLevels; ++l) { net->idx_off[l] = off; off += align(static_cast<int64_t>(n) * net->lv[l + 1].plane * (down_in(l) + kNew)); }
     net->pre_off = off; off += align(static_cast<int64_t>(n) * net->lv[0].plane * 4);
     net->gs_saved = tb.saved_floats; net->gs_sums = sums;
     net->saved_off = off; off += align(tb.saved_floats * 4 * groups);
@@ -497,32 +478,22 @@ extern "C" int N16(create)(endo_net16** out, int n_per_group, int h, int w, int 
         int64_t o = 0;
         net->ws_d[0] = o; o += align(static_cast<int64_t>(n) * net->lv[0].plane * net->lv[0].t * 2);
         net->ws_zero_begin = o;
-        for (int l = 1; l <= k16Levels; ++l) { net->ws_d[l] = o; o += align(static_cast<int64_t>(n) * net->lv[l].plane * net->lv[l].t * 2); }
-        for (int l = 0; l <= k16Levels; ++l) { net->ws_pq[l] = o; o += align(static_cast<int64_t>(net->lv[l].t) * 2 * 4 * groups); }
+        for (int l = 1; l <= kLevels; ++l) { net->ws_d[l] = o; o += align(static_cast<int64_t>(n) * net->lv[l].plane * net->lv[l].t * 2); }
+        for (int l = 0; l <= kLevels; ++l) { net->ws_pq[l] = o; o += align(static_cast<int64_t>(net->lv[l].t) * 2 * 4 * groups); }
         net->bn_slot_stride = tb.saved_floats * groups;          // kBnSlots copies of the BatchNorm-backward sums (common.h), this many doubles apart
         net->ws_bnsums = o; o += align(tb.saved_floats * 8 * groups * kBnSlots);
-        for (int l = 0; l <= k16Levels; ++l) { net->ws_gsum[l] = o; o += align(static_cast<int64_t>(net->lv[l].t) * 2 * 8); }
+        for (int l = 0; l <= kLevels; ++l) { net->ws_gsum[l] = o; o += align(static_cast<int64_t>(net->lv[l].t) * 2 * 8); }
         net->ws_zero_end = o;
         net->ws_w16d = o; o += align(tb.w16d_elems * 2);
         int64_t need = 0;
-        auto wg = [&](int level, int cin, int cout, int ks) {
-            Wgrad16Params q{};
-            q.n = n; q.h = net->lv[level].h; q.w = net->lv[level].w; q.cin = cin; q.cout = cout;
-            const int64_t f = bf16_wgrad_partial_floats(cin, cout, ks, bf16_wgrad_blocks(q, ks));
-            need = f > need ? f : need;
-        };
         // EVERY weight-gradient launch of the backward pass: blocks x co_groups x 144 x ci_pad is not monotonic in cin (the block count
         // drops when cin crosses a multiple of 64), so the widest layer of a level is not its largest partial buffer
-        wg(0, 4, k16First, 3);
-        for (int l = 0; l < k16Levels; ++l) {
-            for (int j = 0; j < k16Layers; ++j) {
-                wg(l, tb.down_conv[l][j].cin, k16Growth, 3);
-                wg(l, tb.up_conv[k16Levels - 1 - l][j].cin, k16Growth, 3);
-            }
-            wg(l, tb.td_conv[l].cin, tb.td_conv[l].cout, 1);                 // transition down
-            wg(l, k16New, k16New, 3);                                        // transition up (output grid of level l)
+        for (const Conv16* cv : tb.convs) {
+            Wgrad16Params q{};
+            q.n = n; q.h = net->lv[cv->level].h; q.w = net->lv[cv->level].w; q.cin = w16_cin_k(cv->cin); q.cout = cv->cout;
+            const int64_t f = bf16_wgrad_partial_floats(q.cin, q.cout, cv->ks, bf16_wgrad_blocks(q, cv->ks));
+            need = f > need ? f : need;
         }
-        for (int j = 0; j < k16Layers; ++j) wg(k16Levels, tb.bott_conv[j].cin, k16Growth, 3);
         net->ws_partial_floats = need;
         net->ws_partial = o; o += align(need * 4);
         net->ws_gscale = o; o += 256;
@@ -533,9 +504,7 @@ extern "C" int N16(create)(endo_net16** out, int n_per_group, int h, int w, int 
 }
 extern "C" void N16(destroy)(endo_net16* net) {
     if (!net) return;
-    if (net->ev_fork) (void)hipEventDestroy(net->ev_fork);
-    if (net->ev_join) (void)hipEventDestroy(net->ev_join);
-    if (net->wstream) (void)hipStreamDestroy(net->wstream);
+    net->side.destroy();
     delete net;
 }
 // 1 (default): endo_net16_bwd issues the weight gradients on a side stream it owns (forked after every prep_dy, joined before it returns);
@@ -553,15 +522,14 @@ extern "C" int64_t N16(bwd_workspace_bytes)(const endo_net16* net) { return net 
 // buffer `index` (not an offset); 7: bytes between two sample groups' (mean, rstd) tables.  -1 for anything else.
 extern "C" int64_t N16(offset)(const endo_net16* net, int what, int index) {
     if (!net || index < 0) return -1;
-    const Table16& tb = table16();
     switch (what) {
         case 0: return net->pre_off;
-        case 1: return index < static_cast<int>(tb.bns.size()) ? net->saved_off + tb.bns[index]->saved * 4 : -1;
-        case 2: return index < k16Levels ? net->idx_off[index] : -1;
-        case 3: return index <= k16Levels ? net->lv[index].act : -1;
-        case 4: return index <= k16Levels ? net->ws_d[index] : -1;
-        case 5: return index <= k16Levels ? net->lv[index].t : -1;
-        case 6: return index <= k16Levels ? net->ws_pq[index] : -1;          // workspace: deferred BatchNorm terms of the level, fp32 [P[t]][Q[t]] per group
+        case 1: return index < static_cast<int>(arch().bns.size()) ? net->saved_off + 2 * arch().bns[index].before * 4 : -1;
+        case 2: return index < kLevels ? net->idx_off[index] : -1;
+        case 3: return index <= kLevels ? net->lv[index].act : -1;
+        case 4: return index <= kLevels ? net->ws_d[index] : -1;
+        case 5: return index <= kLevels ? net->lv[index].t : -1;
+        case 6: return index <= kLevels ? net->ws_pq[index] : -1;          // workspace: deferred BatchNorm terms of the level, fp32 [P[t]][Q[t]] per group
         case 7: return net->gs_saved * 4;          // not an offset: bytes from one sample group's saved (mean, rstd) table to the next
         default: return -1;
     }
@@ -582,7 +550,7 @@ struct Ctx16 {
     float* pq_p(int level) const { return reinterpret_cast<float*>(ws + net->ws_pq[level]); }
     float* pq_q(int level) const { return pq_p(level) + net->lv[level].t; }
     double* gsum(int level) const { return reinterpret_cast<double*>(ws + net->ws_gsum[level]); }
-    double* bnsums(const Bn16& b) const { return reinterpret_cast<double*>(ws + net->ws_bnsums) + b.saved; }
+    double* bnsums(const Bn16& b) const { return reinterpret_cast<double*>(ws + net->ws_bnsums) + 2 * b.before; }
     const uint16_t* w16d(const Conv16& c) const { return reinterpret_cast<const uint16_t*>(ws + net->ws_w16d) + c.w16d; }
     float* partial() const { return reinterpret_cast<float*>(ws + net->ws_partial); }
 #ifdef ENDO16_HALF
@@ -592,18 +560,15 @@ struct Ctx16 {
 #endif
     // the side stream, after everything issued on `stream` so far
     int fork_wgrad(hipStream_t& side) const {
-        const bool on = net->wstream && net->use_wstream;
-        side = on ? net->wstream : stream;
-        if (on) {
-            ENDO_CHECK(hipEventRecord(net->ev_fork, stream));
-            ENDO_CHECK(hipStreamWaitEvent(net->wstream, net->ev_fork, 0));
-        }
+        const bool on = net->side.stream && net->use_wstream;
+        side = on ? net->side.stream : stream;
+        if (on) ENDO_CHECK(net->side.fork_after(stream));
         return 0;
     }
     uint16_t* act(int level) const { return reinterpret_cast<uint16_t*>(tape + net->lv[level].act); }
     double* sums(int level) const { return reinterpret_cast<double*>(tape + net->sums_off) + net->lv[level].sums; }
     const uint16_t* w16(const Conv16& c) const { return reinterpret_cast<const uint16_t*>(tape + net->w16_off) + c.w16; }
-    float* saved(const Bn16& b) const { return reinterpret_cast<float*>(tape + net->saved_off) + b.saved; }
+    float* saved(const Bn16& b) const { return reinterpret_cast<float*>(tape + net->saved_off) + 2 * b.before; }
 };
 
 void fill_io(const Ctx16& c, Conv16Params& p, int in_level, int ic0, int cin, int out_level, int oc0, const Conv16& cv) {
@@ -622,10 +587,10 @@ void fill_bn(const Ctx16& c, Conv16Params& p, const Bn16& b, int level, int ic0)
     p.use_stats = 1;
     p.in_sums = c.sums(level) + 2 * ic0;
     p.gamma = c.params + b.g; p.beta = c.params + b.b;
-    p.running_mean = c.bn_running + b.run_mean; p.running_var = c.bn_running + b.run_var;
+    p.running_mean = c.bn_running + b.run; p.running_var = c.bn_running + b.run + b.c;
     p.saved = c.saved(b);
     p.count = static_cast<double>(c.net->gn) * lv.plane;
-    p.eps = 1.0e-5f; p.momentum = 0.1f; p.training = c.training;
+    p.eps = kBnEps; p.momentum = kBnMomentum; p.training = c.training;
 }
 
 // dense layer: BN -> ReLU -> conv3x3 -> +12 channels (models.py:19-28, 44-52)
@@ -677,17 +642,8 @@ extern "C" int N16(fwd)(endo_net16* net, const float* params, float* bn_running,
     ENDO_CHECK(hipMemsetAsync(c.tape + net->sums_off, 0, net->sums_bytes, stream));
     {   // weights of all 56 MFMA convolutions -> bf16
         W16Table t{};
-        t.layers = static_cast<int>(tb.convs.size());
-        if (t.layers > 63) return ENDO_E_BADARG;
-        int64_t start = 0;
-        for (int l = 0; l < t.layers; ++l) {
-            const Conv16& cv = *tb.convs[l];
-            const int cin_k = cv.cin < 4 ? 4 : cv.cin;
-            const int64_t groups = (cv.cout + cv.nt * 16 - 1) / (cv.nt * 16), chunks = (cin_k + kBfKC - 1) / kBfKC;
-            t.start[l] = start; t.w[l] = cv.w; t.out[l] = cv.w16; t.cout[l] = cv.cout; t.cin[l] = cv.cin; t.cin_k[l] = cin_k; t.ks[l] = cv.ks; t.nt[l] = cv.nt; t.rot[l] = cv.rot; t.rot_n[l] = cv.rot_n;
-            start += chunks * groups * cv.ks * cv.ks * cv.nt * 16 * 32;
-        }
-        t.start[t.layers] = start;
+        if (tb.convs.size() > 63) return ENDO_E_BADARG;
+        for (const Conv16* cv : tb.convs) w16_append(t, *cv);
         bf16_all_weights_kernel<<<1024, 256, 0, stream>>>(t, params, reinterpret_cast<uint16_t*>(c.tape + net->w16_off));
         ENDO_LAUNCH_CHECK();
     }
@@ -700,31 +656,31 @@ extern "C" int N16(fwd)(endo_net16* net, const float* params, float* bn_running,
         p.n = net->n; p.h = net->h; p.w = net->w;
         p.in = xin; p.in_t = 8; p.in_h = net->h; p.in_w = net->w; p.in_ns = net->lv[0].plane * 8; p.ic0 = 0; p.cin = 4;
         p.wgt = c.w16(tb.first); p.bias = params + tb.first.b;
-        p.out = c.act(0); p.out_t = net->lv[0].t; p.out_blk = k16Blk; p.out_ns = net->lv[0].plane * net->lv[0].t; p.oc0 = 0; p.cout = k16First;
+        p.out = c.act(0); p.out_t = net->lv[0].t; p.out_blk = k16Blk; p.out_ns = net->lv[0].plane * net->lv[0].t; p.oc0 = 0; p.cout = kFirst;
         p.out_sums = training ? c.sums(0) : nullptr;
         p.group_n = net->groups > 1 ? net->gn : 0; p.gs_out_sums = net->gs_sums;
         rc = launch_bf16_conv<3, 3, 0, 8, 2>(p, stream);
         if (rc) return rc;
     }
-    for (int l = 0; l < k16Levels; ++l) {
-        for (int j = 0; j < k16Layers; ++j) {
-            rc = dense16(c, l, 0, c16_down_in(l) + k16Growth * j, tb.down_bn[l][j], tb.down_conv[l][j]);
+    for (int l = 0; l < kLevels; ++l) {
+        for (int j = 0; j < kLayers; ++j) {
+            rc = dense16(c, l, 0, down_in(l) + kGrowth * j, tb.down_bn[l][j], tb.down_conv[l][j]);
             if (rc) return rc;
         }
         rc = td16(c, l, tb.td_bn[l], tb.td_conv[l]);
         if (rc) return rc;
     }
-    for (int j = 0; j < k16Layers; ++j) {
-        rc = dense16(c, k16Levels, 0, 288 + k16Growth * j, tb.bott_bn[j], tb.bott_conv[j]);
+    for (int j = 0; j < kLayers; ++j) {
+        rc = dense16(c, kLevels, 0, kBottIn + kGrowth * j, tb.bott_bn[j], tb.bott_conv[j]);
         if (rc) return rc;
     }
-    for (int i = 0; i < k16Levels; ++i) {
-        const int l = k16Levels - 1 - i, src = l + 1;
-        const int src_c0 = (i == 0) ? 288 : c16_skip(src) + k16New;
+    for (int i = 0; i < kLevels; ++i) {
+        const int l = kLevels - 1 - i, src = l + 1;
+        const int src_c0 = (i == 0) ? kBottIn : c16_skip(src) + kNew;
         rc = tu16(c, l, src, src_c0, tb.tu_conv[i]);
         if (rc) return rc;
-        for (int j = 0; j < k16Layers; ++j) {
-            rc = dense16(c, l, 0, c16_skip(l) + k16New + k16Growth * j, tb.up_bn[i][j], tb.up_conv[i][j]);
+        for (int j = 0; j < kLayers; ++j) {
+            rc = dense16(c, l, 0, c16_skip(l) + kNew + kGrowth * j, tb.up_bn[i][j], tb.up_conv[i][j]);
             if (rc) return rc;
         }
     }
@@ -798,7 +754,7 @@ void fill_dgrad(const Ctx16& c, Conv16Params& p, int g_level, int gc0, int level
 // dependency); the base channels of all four layers follow in one pass (dense_block_bwd16)
 int dense_wgrad16(const Ctx16& c, int level, int c0, int j, const Bn16& b, const Conv16& cv, hipStream_t side) {
     const auto& lv = c.net->lv[level];
-    const int oc0 = c0 + k16Growth * j;
+    const int oc0 = c0 + kGrowth * j;
     const double px = static_cast<double>(c.net->n) * lv.plane;
     Wgrad16Params p{};
     p.n = c.net->n; p.h = lv.h; p.w = lv.w;
@@ -810,7 +766,7 @@ int dense_wgrad16(const Ctx16& c, int level, int c0, int j, const Bn16& b, const
 
 int dense_bwd16(const Ctx16& c, int level, int c0, int j, const Bn16& b, const Conv16& cv, bool with_wgrad = true) {
     const auto& lv = c.net->lv[level];
-    const int oc0 = c0 + k16Growth * j;
+    const int oc0 = c0 + kGrowth * j;
     int rc = prep_dy16(c, level, oc0, cv.cout, c.grads + cv.b);
     if (rc) return rc;
     const double px = static_cast<double>(c.net->n) * lv.plane;
@@ -824,19 +780,19 @@ int dense_bwd16(const Ctx16& c, int level, int c0, int j, const Bn16& b, const C
     if (j == 0) return 0;
     Conv16Params p{};
     fill_dgrad(c, p, level, oc0, level, b, cv);
-    p.oc0 = c0; p.cout = k16Growth * j; p.co_off = c0; p.grp0 = c0 / 48; p.wgroups = (cv.cin + 47) / 48;
+    p.oc0 = c0; p.cout = kGrowth * j; p.co_off = c0; p.grp0 = c0 / 48; p.wgroups = (cv.cin + 47) / 48;
     {
         ProfScope prof(kProfDgradDense, c.stream, 2.0 * px * p.cout * cv.cout * 9, px * (6.0 * p.cout + 2.0 * cv.cout));
         rc = launch_bf16_conv<3, 3, kEpiDgradBn, 4, 1, 0, 0, 8>(p, c.stream);          // 4-wave blocks over 8-row tiles: one fits a CU beside a weight-gradient block
     }
     if (rc) return rc;
-    return bn_finalize16(c, b, cv, level, c0, k16Growth * j);
+    return bn_finalize16(c, b, cv, level, c0, kGrowth * j);
 }
 
 // a dense block with c0 base channels [0, c0) and its four layers' maps at [c0, c0 + 48)
 int dense_block_bwd16(const Ctx16& c, int level, int c0, const Bn16* bn, const Conv16* cv) {
-    const bool defer = c.net->wstream && c.net->use_wstream == 2;          // one fork per block: nothing rewrites a prepared G before the join
-    for (int j = k16Layers - 1; j >= 0; --j) {
+    const bool defer = c.net->side.stream && c.net->use_wstream == 2;          // one fork per block: nothing rewrites a prepared G before the join
+    for (int j = kLayers - 1; j >= 0; --j) {
         const int rc = dense_bwd16(c, level, c0, j, bn[j], cv[j], !defer);
         if (rc) return rc;
     }
@@ -844,7 +800,7 @@ int dense_block_bwd16(const Ctx16& c, int level, int c0, const Bn16* bn, const C
         hipStream_t side;
         int rc = c.fork_wgrad(side);
         if (rc) return rc;
-        for (int j = k16Layers - 1; j >= 0; --j) {
+        for (int j = kLayers - 1; j >= 0; --j) {
             rc = dense_wgrad16(c, level, c0, j, bn[j], cv[j], side);
             if (rc) return rc;
         }
@@ -853,7 +809,7 @@ int dense_block_bwd16(const Ctx16& c, int level, int c0, const Bn16* bn, const C
     DgradBlock16Params p{};
     p.n = c.net->n; p.h = lv.h; p.w = lv.w;
     p.g = c.dbuf(level); p.out = c.dbuf(level); p.x = c.act(level); p.ns = lv.plane * lv.t; p.blk = k16Blk; p.gc0 = c0; p.c0 = c0;
-    for (int j = 0; j < k16Layers; ++j) {
+    for (int j = 0; j < kLayers; ++j) {
         p.wgt[j] = c.w16d(cv[j]); p.saved[j] = c.saved(bn[j]); p.gamma[j] = c.params + bn[j].g; p.beta[j] = c.params + bn[j].b;
         p.sums[j] = c.bnsums(bn[j]);
     }
@@ -863,13 +819,13 @@ int dense_block_bwd16(const Ctx16& c, int level, int c0, const Bn16* bn, const C
     {
         // per base channel and pixel: forward value 2 B, gradient read + written 4 B; the 48 gradient maps 2 B each
         const double px = static_cast<double>(c.net->n) * lv.plane;
-        ProfScope prof(kProfDgradDense, c.stream, 2.0 * px * c0 * k16New * 9, px * (6.0 * c0 + 2.0 * k16New));
+        ProfScope prof(kProfDgradDense, c.stream, 2.0 * px * c0 * kNew * 9, px * (6.0 * c0 + 2.0 * kNew));
         const int rc = launch_bf16_dgrad_block(p, c.stream);
         if (rc) return rc;
     }
-    static_assert(k16Layers == 4, "bf16_bn_finalize4_kernel");
+    static_assert(kLayers == 4, "bf16_bn_finalize4_kernel");
     BnFin16x4 fin{};
-    for (int j = 0; j < k16Layers; ++j) {
+    for (int j = 0; j < kLayers; ++j) {
         fin.sums[j] = c.bnsums(bn[j]); fin.saved[j] = c.saved(bn[j]); fin.gamma[j] = c.params + bn[j].g;
         fin.ggamma[j] = c.grads + bn[j].g; fin.gbeta[j] = c.grads + bn[j].b; fin.rot[j] = cv[j].rot; fin.rot_n[j] = cv[j].rot_n;
     }
@@ -950,32 +906,17 @@ extern "C" int N16(bwd)(endo_net16* net, const float* params, const void* tape_,
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Ctx16 c{net, params, nullptr, const_cast<char*>(static_cast<const char*>(tape_)), training, stream};
     c.grads = grads; c.ws = static_cast<char*>(ws_);
-    if (!net->wstream && net->use_wstream) {
-        ENDO_CHECK(hipStreamCreateWithFlags(&net->wstream, hipStreamNonBlocking));
-        ENDO_CHECK(hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming));
-        ENDO_CHECK(hipEventCreateWithFlags(&net->ev_join, hipEventDisableTiming));
-    }
+    if (net->use_wstream) ENDO_CHECK(net->side.create());
     ENDO_CHECK(hipMemsetAsync(c.ws + net->ws_zero_begin, 0, static_cast<size_t>(net->ws_zero_end - net->ws_zero_begin), stream));
     {   // data-gradient weights of the 54 convolutions that have one
         W16Table t{};
-        t.layers = static_cast<int>(tb.dconvs.size());
         t.dgrad = 1;
-        if (t.layers > 63) return ENDO_E_BADARG;
-        int64_t start = 0;
-        for (int l = 0; l < t.layers; ++l) {
-            const Conv16& cv = *tb.dconvs[l];
-            const int64_t groups = (cv.cin + 47) / 48, chunks = (cv.cout + kBfKC - 1) / kBfKC;
-            t.start[l] = start; t.w[l] = cv.w; t.out[l] = cv.w16d; t.cout[l] = cv.cin; t.cin[l] = cv.cout; t.cin_k[l] = cv.cout; t.ks[l] = cv.ks; t.nt[l] = 3;
-            t.rot[l] = cv.rot; t.rot_n[l] = cv.rot_n; t.base[l] = cv.base; t.koff[l] = cv.koff;
-            start += chunks * groups * cv.ks * cv.ks * 3 * 16 * 32;
-        }
-        t.start[t.layers] = start;
+        if (tb.dconvs.size() > 63) return ENDO_E_BADARG;
+        for (const Conv16* cv : tb.dconvs) w16_append(t, *cv);
         bf16_all_weights_kernel<<<1024, 256, 0, stream>>>(t, params, reinterpret_cast<uint16_t*>(c.ws + net->ws_w16d));
         ENDO_LAUNCH_CHECK();
     }
-    // everything that may fork the side stream runs inside `body`: the join below is reached on every exit path, so an error return never
-    // leaves the side stream un-joined with the caller's
-    auto body = [&]() -> int {
+    auto body = [&]() -> int {          // everything that may fork the side stream: the join below is reached on every exit path (SideStream)
     int rc;
 #ifdef ENDO16_HALF
     ENDO_CHECK(hipMemsetAsync(c.ws + net->ws_gscale, 0, 16, stream));
@@ -997,30 +938,30 @@ extern "C" int N16(bwd)(endo_net16* net, const float* params, const void* tape_,
                                                                     tb.final_.rot_n, grads + tb.final_.w, grads + tb.final_.b, c.gsum(0), c.gscale());
         ENDO_LAUNCH_CHECK();
     }
-    for (int i = k16Levels - 1; i >= 0; --i) {
-        const int l = k16Levels - 1 - i, src = l + 1;
-        rc = dense_block_bwd16(c, l, c16_skip(l) + k16New, tb.up_bn[i], tb.up_conv[i]);
+    for (int i = kLevels - 1; i >= 0; --i) {
+        const int l = kLevels - 1 - i, src = l + 1;
+        rc = dense_block_bwd16(c, l, c16_skip(l) + kNew, tb.up_bn[i], tb.up_conv[i]);
         if (rc) return rc;
-        rc = tu_bwd16(c, l, src, (i == 0) ? 288 : c16_skip(src) + k16New, tb.tu_conv[i]);
+        rc = tu_bwd16(c, l, src, (i == 0) ? kBottIn : c16_skip(src) + kNew, tb.tu_conv[i]);
         if (rc) return rc;
     }
-    rc = dense_block_bwd16(c, k16Levels, 288, tb.bott_bn, tb.bott_conv);
+    rc = dense_block_bwd16(c, kLevels, kBottIn, tb.bott_bn, tb.bott_conv);
     if (rc) return rc;
-    for (int l = k16Levels - 1; l >= 0; --l) {
+    for (int l = kLevels - 1; l >= 0; --l) {
         rc = td_bwd16(c, l, tb.td_bn[l], tb.td_conv[l]);
         if (rc) return rc;
-        rc = dense_block_bwd16(c, l, c16_down_in(l), tb.down_bn[l], tb.down_conv[l]);
+        rc = dense_block_bwd16(c, l, down_in(l), tb.down_bn[l], tb.down_conv[l]);
         if (rc) return rc;
     }
     {   // first convolution: bias and weight gradient (the image needs none)
-        rc = prep_dy16(c, 0, 0, k16First, grads + tb.first.b);
+        rc = prep_dy16(c, 0, 0, kFirst, grads + tb.first.b);
         if (rc) return rc;
         const auto& lv = net->lv[0];
         Wgrad16Params p{};
         p.n = net->n; p.h = lv.h; p.w = lv.w;
         p.a = reinterpret_cast<const uint16_t*>(c.tape + net->in_off); p.a_ns = lv.plane * 8; p.a_blk = 8; p.a_h = lv.h; p.a_w = lv.w; p.ac0 = 0; p.cin = 4;
         p.cin_w = 3;
-        p.g = c.dbuf(0); p.g_ns = lv.plane * lv.t; p.g_blk = k16Blk; p.gc0 = 0; p.cout = k16First;
+        p.g = c.dbuf(0); p.g_ns = lv.plane * lv.t; p.g_blk = k16Blk; p.gc0 = 0; p.cout = kFirst;
         p.partial = c.partial(); p.partial_cap = c.net->ws_partial_floats; p.gscale = c.gscale();
         hipStream_t side;
         rc = c.fork_wgrad(side);
@@ -1031,9 +972,6 @@ extern "C" int N16(bwd)(endo_net16* net, const float* params, const void* tape_,
     return 0;
     };
     const int rc_body = body();
-    if (net->wstream && net->use_wstream) {          // join: the caller's stream continues only after every weight gradient has landed
-        ENDO_CHECK(hipEventRecord(net->ev_join, net->wstream));
-        ENDO_CHECK(hipStreamWaitEvent(stream, net->ev_join, 0));
-    }
+    if (net->side.stream && net->use_wstream) ENDO_CHECK(net->side.join_into(stream));          // the caller's stream continues only after every weight gradient has landed
     return rc_body;
 }

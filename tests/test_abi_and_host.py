@@ -64,6 +64,29 @@ def test_module_tree_matches_reference_state_dict():
         bn_off += 2 * m.num_features
 
 
+def test_both_families_place_batchnorms_by_one_table():
+    """The saved (mean, rstd) pairs of BatchNorm i lie where the same table puts them in the fp32 tape (float offsets) and in the bf16 and
+    half tapes (byte offsets), each from its handle's own start; index 49 is past the table for all three."""
+    lib = ea._lib.load()
+    hnd = ctypes.c_void_p()
+    assert lib.endo_net_create(ctypes.byref(hnd), 2, 64, 96) == 0
+    try:
+        saved = [lib.endo_net_tape_offset(hnd, 1, i) for i in range(50)]          # ENDO_TAPE_BN_SAVED
+        assert saved[49] == -1 and min(saved[:49]) >= 0
+        for family in ("endo_net16", "endo_net16h"):
+            h16 = ctypes.c_void_p()
+            assert getattr(lib, family + "_create")(ctypes.byref(h16), 2, 64, 96, 1) == 0
+            try:
+                saved16 = [getattr(lib, family + "_offset")(h16, 1, i) for i in range(50)]
+                assert saved16[49] == -1 and min(saved16[:49]) >= 0
+                for i in range(49):
+                    assert saved16[i] - saved16[0] == 4 * (saved[i] - saved[0]), (family, i)
+            finally:
+                getattr(lib, family + "_destroy")(h16)
+    finally:
+        lib.endo_net_destroy(hnd)
+
+
 def test_flat_buffers_and_checkpoint_roundtrip(tmp_path):
     state = onet.perturb_affine(onet.synthetic_state(3), 4)
     model = ea.FCDenseNet57(1)
