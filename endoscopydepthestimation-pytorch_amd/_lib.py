@@ -150,6 +150,13 @@ SIGNATURES = {
     "endo_registration_prepare": (_I, [_P, _L, _L, _P, _P, _L, _P]),
     "endo_registration_match": (_I, [_P, _L, _L, _P, _P, _P, _L, _L, _P, ctypes.c_double, _P, _P, _P, _P, _L, _P]),
     "endo_similarity_apply": (_I, [_P, _L, _L, _P, _P, _P]),
+    "endo_fusion_tile": (_I, [_I]),
+    "endo_fusion_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_fusion_clear": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "endo_fusion_integrate": (_I, [_P] * 7 + [_I, _I, _I, _P, ctypes.c_double, ctypes.c_double, _F, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "endo_fusion_extract_workspace_bytes": (_L, [_I, _I, _I]),
+    "endo_fusion_count": (_I, [_P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _F, _P, _P, _L, _P]),
+    "endo_fusion_extract": (_I, [_P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _F, _P, _L, _P, _P, _L, _P]),
 }
 
 # the backward bricks of the 16-bit-storage family (one launch of endo_net16_bwd each), over bf16 and over half

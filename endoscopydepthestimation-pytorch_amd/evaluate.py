@@ -28,6 +28,10 @@ What the reference leaves to another tool (its README, step 4: register the pred
 transformation "to calculate residual errors") is registration_errors over the points / offsets any of the outputs above return, and
 run_registration_phase: the posed test outputs per batch, each frame's cloud registered to a registration.TargetModel from the tracker's
 pose as its start, ``registration_errors.csv`` and the registered clouds.
+
+run_fusion_phase makes one model of the sequence before that step: the posed outputs per batch, their depth maps fused into a
+fusion.TSDFVolume around the posed clouds' bounding box (csrc/fusion.hip), the surface written as ``fused_surface.ply`` and, with a
+target, registered once.
 """
 
 import os
@@ -37,7 +41,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, display, models, registration, utils
+from . import _lib, display, fusion, models, registration, utils
 from .train_step import mask_mul
 
 
@@ -508,3 +512,88 @@ def run_registration_phase(model, frames, translation_dict, rotation_dict, targe
             f.write(",".join(str(v) for v in row) + "\n")
     return {"frames": count, "registered": count - len(failed), "failed": failed, "rows": rows,
             "rms": float(np.sqrt(squares / inliers)) if inliers else float("nan")}
+
+
+def _write_fused(ready, path, rows, ply_text):
+    ready.synchronize()
+    utils.write_point_cloud(path, rows.numpy(), text=ply_text)
+
+
+def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, voxel_size=None, resolution=256, truncation_voxels=4,
+                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, **register_kwargs):
+    """One model of a sequence: every batch of ``frames`` (a dataset.TestFrames) through posed_test_outputs with the poses
+    ``translation_dict[name]`` / ``rotation_dict[name]`` (the network's forward runs once); each batch's depth, colour images,
+    boundaries, intrinsics and poses stay on the device, with the bounding box of its posed rows.  Then a fusion.TSDFVolume around
+    that box (its longest side in ``resolution`` voxels, or voxels of ``voxel_size``; truncation ``truncation_voxels`` voxels), the
+    batches integrated in order, the surface extracted at ``min_weight`` and written as ``fused_surface.ply`` in ``out_dir`` on
+    run_test_phase's writer pool.  Frames without kept pixels or with equal kept depths take no part, neither in the box nor in the
+    volume; their names are reported.  A frame whose name is missing from either dictionary raises KeyError before anything runs.
+    With ``target`` (a registration.TargetModel, or rows to make one of): the fused rows registered once with
+    registration.register(**register_kwargs) from ``initial`` (_initial_transform), ``fused_registered.ply`` (the rows under that
+    registration, colours kept) and a one-row ``fused_registration.csv`` with REGISTRATION_COLUMNS.
+    Returns a dictionary: frames (their number), empty and zero_range (names), voxel_size, dims and origin of the volume (None when no
+    frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None)."""
+    names_ahead = getattr(frames, "image_file_names", None)
+    if names_ahead is not None:
+        for name in names_ahead:
+            key = os.path.basename(str(name))[-12:-4]
+            translation_dict[key], rotation_dict[key]          # KeyError before anything runs
+    out_dir = str(out_dir)
+    count = 0
+    empty, zero_range, kept, boxes = [], [], [], []
+    for batch in frames:
+        names = list(batch["names"])
+        rotations = [rotation_dict[name] for name in names]
+        translations = [translation_dict[name] for name in names]
+        out = posed_test_outputs(model, batch, rotations, translations, is_hsv=getattr(frames, "is_hsv", False))
+        count += len(names)
+        offsets, ranges = out["offsets"], out["ranges"]
+        good = []
+        for f, name in enumerate(names):
+            if ranges[f, 0] > ranges[f, 1]:
+                empty.append(name)
+            elif ranges[f, 0] == ranges[f, 1]:
+                zero_range.append(name)
+            else:
+                good.append(f)
+        for f in good:
+            rows = out["points"][offsets[f]:offsets[f + 1], :3]
+            if rows.shape[0]:
+                boxes.append(torch.stack([rows.amin(dim=0), rows.amax(dim=0)]))
+        if good:
+            dev = out["depth"].device
+            rot, tr = _poses_f64(rotations, translations, len(names), dev)
+            pick = torch.tensor(good, dtype=torch.int64, device=dev)
+            kept.append((out["depth"][pick], batch["boundaries"].to(dev)[pick], out["color_images"][pick], batch["intrinsics"].to(dev)[pick],
+                         rot[pick], tr[pick]))
+    os.makedirs(out_dir, exist_ok=True)
+    result = {"frames": count, "empty": empty, "zero_range": zero_range, "voxel_size": None, "dims": None, "origin": None, "points": 0,
+              "observed_voxels": 0, "registration": None}
+    with _WriterPool(1) as pool:
+        if boxes:
+            both = torch.stack(boxes).to(torch.float64)
+            bounds = torch.stack([both[:, 0].amin(dim=0), both[:, 1].amax(dim=0)]).cpu().numpy()          # the box's one read
+            volume = fusion.TSDFVolume.around_bounds(bounds[0], bounds[1], voxel_size, resolution, device=kept[0][0].device,
+                                                     truncation_voxels=truncation_voxels, max_weight=max_weight)
+            for depth, boundaries, colors, intrinsics, rot, tr in kept:
+                volume.integrate(depth, boundaries, colors, intrinsics, rot, tr)
+            surface = volume.extract(min_weight)
+            result.update({"voxel_size": volume.voxel_size, "dims": volume.dims, "origin": volume.origin.copy(),
+                           "observed_voxels": volume.observed_voxels()})
+        else:
+            surface = torch.zeros((0, 6), dtype=torch.float32)
+        result["points"] = int(surface.shape[0])
+        pool.submit(_write_fused, os.path.join(out_dir, "fused_surface.ply"), surface.to("cpu", non_blocking=True), ply_text)
+        if target is not None:
+            if not isinstance(target, registration.TargetModel):
+                target = registration.TargetModel(target)
+            scale, rotation, translation = _initial_transform(initial)
+            fit = registration.register(surface, target, scale, rotation, translation, **register_kwargs)
+            moved = registration.similarity_apply(surface, fit.scale, fit.rotation, fit.translation)
+            pool.submit(_write_fused, os.path.join(out_dir, "fused_registered.ply"), moved.to("cpu", non_blocking=True), ply_text)
+            with open(os.path.join(out_dir, "fused_registration.csv"), "w") as f:
+                f.write(",".join(REGISTRATION_COLUMNS) + "\n")
+                f.write(",".join(str(v) for v in ("fused", int(surface.shape[0]), fit.count, repr(fit.scale), repr(fit.mean), repr(fit.rms),
+                                                  repr(fit.max), fit.iterations, int(fit.converged))) + "\n")
+            result["registration"] = fit
+    return result

@@ -1,0 +1,216 @@
+"""Volumetric fusion of a sequence's posed depth maps into one surface: a truncated signed distance function (TSDF) on a voxel grid,
+averaged over the frames that saw a voxel, with its zero crossings as one coloured cloud.  evaluate.run_posed_test_phase ends at one
+cloud per frame, every surface patch once per frame that saw it; what a user registers, measures and looks at is one model.  The
+reference has no code for this step; tests/fusion_restate.py is the numpy float32 statement of what is computed here, bit for bit.
+
+    per volume   TSDFVolume: five fp32 planes of nz x ny x nx voxels on the device (tsdf, weight, colour x 3), cleared once
+    per batch    volume.integrate (csrc/fusion.hip, two launches whatever the batch size): the per-frame table, then every voxel
+                 against every frame of the batch in order; a wave whose box of voxels no frame can see loads and stores nothing;
+                 one read of the per-frame flags
+    at the end   volume.extract (three launches): the surface points on the grid's edges as (P, 6) rows of x, y, z, r, g, b, which
+                 registration.register and utils.write_point_cloud take as they are; one 8-byte read of the count in between
+
+Depth maps, masks, colour images, intrinsics and poses are the ones evaluate.posed_outputs_from_predictions takes and returns: a pose
+maps scaled camera coordinates to the tracker's frame, ``x = R (s x_cam) + t``, and without explicit scales ``s`` is the posed
+output's own 20 / (z_max - z_min), so the fused surface lies on the posed clouds.
+"""
+
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FLAGS = ("ok", "empty", "zero_range", "bad_scale")          # ENDO_FUSION_FRAME_* of include/endo_hip.h
+NO_CULL = 1                                                 # ENDO_FUSION_NO_CULL
+
+
+def __getattr__(name):
+    # the box of voxels one wave of the integrate kernel owns, asked of the library itself (tests take their edge sizes from here)
+    if name == "WAVE_BOX":
+        lib = _lib.load()
+        return tuple(int(lib.endo_fusion_tile(which)) for which in range(3))
+    raise AttributeError(name)
+
+
+def _host_doubles(values):
+    values = [float(v) for v in values]
+    return (ctypes.c_double * len(values))(*values)
+
+
+def _device_tensor(t, dtype, shape, name):
+    if not torch.is_tensor(t):
+        raise ValueError("%s must be a device tensor of shape %s" % (name, tuple(shape)))
+    if not t.is_cuda:
+        raise RuntimeError("%s must live on the GPU: the MI355X path has no CPU fallback" % name)
+    if t.dtype != dtype or int(t.numel()) != int(np.prod(shape)):
+        raise ValueError("%s must be a %s tensor of shape %s, not %s of %s" % (
+            name, str(dtype).replace("torch.", ""), tuple(shape), str(t.dtype).replace("torch.", ""), tuple(t.shape)))
+    return t.contiguous()
+
+
+def _poses(rotations, translations, n, dev):
+    from . import evaluate          # (evaluate imports this module)
+    return evaluate._poses_f64(rotations, translations, n, dev)
+
+
+class TSDFVolume(object):
+    """A voxel grid in the tracker's frame.  origin: the corner of voxel (0, 0, 0) (its centre is half a voxel further on every
+    axis); voxel_size: the edge of a voxel; dims: (nx, ny, nz) with nx a multiple of 4; truncation: the distance at which the signed
+    distance saturates (None: 4 voxels); max_weight: the cap of a voxel's frame count, after which the average becomes a moving one.
+    The planes are ``tsdf`` and ``weight`` (nz, ny, nx) and ``color`` (3, nz, ny, nx), fp32 on ``device``: tsdf 1, weight 0, colour 0
+    until a frame sees the voxel."""
+
+    def __init__(self, origin, voxel_size, dims, truncation=None, max_weight=64.0, device=None):
+        origin = np.asarray(origin, np.float64).reshape(-1)
+        if origin.shape[0] != 3 or not np.all(np.isfinite(origin)) or not np.all(np.isfinite(origin.astype(np.float32))):
+            raise ValueError("origin must be three finite coordinates, not %r" % (origin.tolist(),))
+        voxel_size = float(voxel_size)
+        if not (voxel_size > 0.0 and math.isfinite(voxel_size) and float(np.float32(voxel_size)) > 0.0 and np.isfinite(np.float32(voxel_size))):
+            raise ValueError("voxel_size must be positive and finite, not %r" % voxel_size)
+        try:
+            nx, ny, nz = (int(v) for v in dims)
+        except (TypeError, ValueError):
+            raise ValueError("dims must be (nx, ny, nz), not %r" % (dims,))
+        if nx <= 0 or ny <= 0 or nz <= 0:
+            raise ValueError("dims must be positive, not %r" % ((nx, ny, nz),))
+        if nx % 4:
+            raise ValueError("nx must be a multiple of 4 (a thread owns 4 consecutive x voxels), not %d" % nx)
+        truncation = 4.0 * voxel_size if truncation is None else float(truncation)
+        if not (truncation > 0.0 and math.isfinite(truncation)):
+            raise ValueError("truncation must be positive and finite, not %r" % truncation)
+        max_weight = float(max_weight)
+        if not (max_weight >= 1.0 and math.isfinite(max_weight)):
+            raise ValueError("max_weight must be finite and at least 1, not %r" % max_weight)
+        lib = _lib.load()
+        self._extract_bytes = int(lib.endo_fusion_extract_workspace_bytes(nx, ny, nz))
+        if self._extract_bytes < 0:
+            raise ValueError("a volume of %d x %d x %d voxels is outside endo_fusion_integrate's sizes" % (nx, ny, nz))
+        self.origin, self.voxel_size, self.dims = origin, voxel_size, (nx, ny, nz)
+        self.truncation, self.max_weight = truncation, max_weight
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise RuntimeError("a TSDFVolume lives on the GPU: the MI355X path has no CPU fallback")
+        with torch.cuda.device(self.device):
+            self._planes = torch.empty((5, nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.tsdf, self.weight, self.color = self._planes[0], self._planes[1], self._planes[2:5]
+        self.device = self._planes.device
+        self.clear()
+
+    @classmethod
+    def around(cls, points, voxel_size=None, resolution=256, margin_voxels=8, **kw):
+        """A volume around the bounding box of (P, >= 3) device rows of x, y, z, ...: the box's longest side divided into ``resolution``
+        voxels (or voxels of ``voxel_size``), ``margin_voxels`` more on every side, nx rounded up to a multiple of 4.  One read of the
+        six bounds."""
+        if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] < 3:
+            raise ValueError("points must be (P, C) device rows of x, y, z, ... with C >= 3")
+        if not points.is_cuda:
+            raise RuntimeError("points must live on the GPU: the MI355X path has no CPU fallback")
+        if points.shape[0] == 0:
+            raise ValueError("points is empty: there is no bounding box")
+        xyz = points[:, :3].float()
+        bounds = torch.stack([xyz.amin(dim=0), xyz.amax(dim=0)]).to(torch.float64).cpu().numpy()
+        return cls.around_bounds(bounds[0], bounds[1], voxel_size, resolution, margin_voxels, device=points.device, **kw)
+
+    @classmethod
+    def around_bounds(cls, low, high, voxel_size=None, resolution=256, margin_voxels=8, truncation_voxels=None, **kw):
+        """around() from the box's corners as host numbers.  truncation_voxels: the truncation in voxels of the size found here."""
+        low, high = np.asarray(low, np.float64).reshape(3), np.asarray(high, np.float64).reshape(3)
+        if not (np.all(np.isfinite(low)) and np.all(np.isfinite(high))) or np.any(high < low):
+            raise ValueError("the bounding box %r .. %r is not finite" % (low.tolist(), high.tolist()))
+        margin = int(margin_voxels)
+        if margin < 0:
+            raise ValueError("margin_voxels must not be negative")
+        if voxel_size is None:
+            if int(resolution) <= 0:
+                raise ValueError("resolution must be positive, not %r" % resolution)
+            voxel_size = float((high - low).max()) / int(resolution)
+            if not voxel_size > 0.0:
+                raise ValueError("the bounding box has no extent: give voxel_size")
+        voxel_size = float(voxel_size)
+        if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+            raise ValueError("voxel_size must be positive and finite, not %r" % voxel_size)
+        dims = [int(math.ceil(float(side) / voxel_size)) + 1 + 2 * margin for side in (high - low)]
+        dims[0] = (dims[0] + 3) // 4 * 4
+        if truncation_voxels is not None:
+            kw["truncation"] = float(truncation_voxels) * voxel_size
+        return cls(low - margin * voxel_size, voxel_size, dims, **kw)
+
+    def clear(self):
+        """tsdf 1, weight 0, colour 0 (endo_fusion_clear)."""
+        nx, ny, nz = self.dims
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().endo_fusion_clear(nx, ny, nz, _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color),
+                                                     _lib.stream()), "endo_fusion_clear")
+
+    def integrate(self, depth, boundaries, colors_u8, intrinsics, rotations, translations, scales=None, cull=True):
+        """endo_fusion_integrate on a batch of N frames, in order: depth and boundaries (N, 1, H, W) or (N, H, W) fp32, colors_u8
+        (N, H, W, 3) uint8, intrinsics (N, 3, 3) fp32, as evaluate.posed_outputs_from_predictions takes and returns them (its
+        ``depth``, its ``boundaries`` argument, its ``color_images``); rotations (N, 3, 3) and translations (N, 3) as it takes them.
+        scales: N per-frame scales (a tensor or an array), or None for the posed output's own 20 / (z_max - z_min).  cull=False
+        integrates without the per-wave visibility test: same bytes, more traffic.  Returns the host list of N flags -- "ok",
+        "empty" (no pixel inside the mask), "zero_range" (equal kept depths under the default scale), "bad_scale" (a scale that is
+        not finite and positive) -- the call's one read back; only "ok" frames touch the volume."""
+        if not torch.is_tensor(depth) or depth.dim() not in (3, 4):
+            raise ValueError("depth must be an (N, 1, H, W) or (N, H, W) device tensor")
+        n, height, width = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
+        depth = _device_tensor(depth, torch.float32, (n, height, width), "depth")
+        boundaries = _device_tensor(boundaries, torch.float32, (n, height, width), "boundaries")
+        colors_u8 = _device_tensor(colors_u8, torch.uint8, (n, height, width, 3), "colors_u8")
+        intrinsics = _device_tensor(intrinsics, torch.float32, (n, 3, 3), "intrinsics")
+        for name, t in (("depth", depth), ("boundaries", boundaries), ("colors_u8", colors_u8), ("intrinsics", intrinsics)):
+            if t.device != self.device:
+                raise ValueError("%s lives on %s, the volume on %s" % (name, t.device, self.device))
+        lib = _lib.load()
+        need = int(lib.endo_fusion_workspace_bytes(n, height, width))
+        if need < 0:
+            raise ValueError("a batch of %d frames of %d x %d is outside endo_fusion_integrate's sizes" % (n, height, width))
+        rotations, translations = _poses(rotations, translations, n, self.device)
+        if scales is not None:
+            if not torch.is_tensor(scales):
+                scales = torch.from_numpy(np.ascontiguousarray(np.asarray(scales, np.float32).reshape(-1)))
+            if int(scales.numel()) != n:
+                raise ValueError("scales must hold one value per frame: %d, not %d" % (n, int(scales.numel())))
+            scales = scales.detach().to(device=self.device, dtype=torch.float32).reshape(n).contiguous()
+        nx, ny, nz = self.dims
+        with torch.cuda.device(self.device):
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            flags = torch.empty(n, dtype=torch.int32, device=self.device)
+            _lib.check(lib.endo_fusion_integrate(_lib.ptr(depth), _lib.ptr(boundaries), _lib.ptr(colors_u8), _lib.ptr(intrinsics),
+                                                 _lib.ptr(rotations), _lib.ptr(translations), _lib.ptr(scales), n, height, width,
+                                                 _host_doubles(self.origin), self.voxel_size, self.truncation, self.max_weight, nx, ny,
+                                                 nz, _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color), _lib.ptr(flags),
+                                                 0 if cull else NO_CULL, _lib.ptr(workspace), need, _lib.stream()),
+                       "endo_fusion_integrate")
+            host = flags.cpu().tolist()          # the call's one read back (it waits for the stream)
+        return [FLAGS[v] for v in host]
+
+    def extract(self, min_weight=1.0):
+        """The surface as a (P, 6) fp32 device tensor of x, y, z, r, g, b: one row per grid edge whose two voxels both have
+        weight >= min_weight and signed distances of different sign, at the linear zero crossing, coloured by the same interpolation;
+        voxels in (k, j, i) order, the edges +x, +y, +z inside a voxel.  P = 0 is a valid result."""
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError("min_weight is NaN")
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        origin = _host_doubles(self.origin)
+        with torch.cuda.device(self.device):
+            workspace = torch.empty(self._extract_bytes, dtype=torch.uint8, device=self.device)
+            total = torch.empty(2, dtype=torch.int64, device=self.device)
+            _lib.check(lib.endo_fusion_count(origin, self.voxel_size, nx, ny, nz, _lib.ptr(self.tsdf), _lib.ptr(self.weight),
+                                             _lib.ptr(self.color), min_weight, _lib.ptr(total), _lib.ptr(workspace), self._extract_bytes,
+                                             _lib.stream()), "endo_fusion_count")
+            count = int(total[1:].cpu()[0])          # the one 8-byte read between the scan and the write pass
+            rows = torch.empty((count, 6), dtype=torch.float32, device=self.device)
+            _lib.check(lib.endo_fusion_extract(origin, self.voxel_size, nx, ny, nz, _lib.ptr(self.tsdf), _lib.ptr(self.weight),
+                                               _lib.ptr(self.color), min_weight, _lib.ptr(rows) if count else None, count,
+                                               _lib.ptr(total), _lib.ptr(workspace), self._extract_bytes, _lib.stream()),
+                       "endo_fusion_extract")
+        return rows
+
+    def observed_voxels(self):
+        """The number of voxels at least one frame has seen (one read)."""
+        return int(torch.count_nonzero(self.weight))

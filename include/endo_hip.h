@@ -1075,6 +1075,59 @@ int endo_registration_match(const float* source, int64_t source_stride, int64_t 
                             int32_t* index, float* distance, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 int endo_similarity_apply(const float* rows, int64_t stride, int64_t m, const double* transform, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Volumetric fusion of posed depth maps (csrc/fusion.hip): a truncated signed distance function on a voxel grid, averaged over the
+ * frames that saw a voxel, and its zero crossings as coloured points.  The reference has no code for it; tests/fusion_restate.py is
+ * the numpy float32 statement of the arithmetic, which the planes and rows match bit for bit.  An additive part of ABI 7.
+ *
+ * A volume is five fp32 planes of nz x ny x nx voxels, x fastest, on the device and 16-byte aligned: tsdf, weight and color
+ * ([3][nz][ny][nx]).  They are STATE: endo_fusion_clear initialises them (tsdf 1, weight 0, colour 0), endo_fusion_integrate updates
+ * them.  nx % 4 == 0; ny, nz <= 65535; nx ny nz <= 2^40.  Voxel (i, j, k) has its centre at origin + (index + 0.5) * voxel_size, in
+ * fp32 from `origin` (3 HOST doubles, finite) and voxel_size rounded to fp32.
+ *
+ * endo_fusion_tile(which): the box of voxels one wave of the integrate kernel owns, 0 = x, 1 = y, 2 = z.
+ * endo_fusion_workspace_bytes(n, h, w): endo_fusion_integrate's workspace for n frames of h x w (-1 outside endo_evaluate_posed's sizes).
+ * endo_fusion_integrate: n frames in order, two launches.  depth and boundaries [n][h][w] fp32 (endo_evaluate_posed's depth and its
+ *   mask), colors [n][h][w][3] uint8 (its colour images), intrinsics [n][3][3] fp32, rotations [n][3][3] and translations [n][3] fp64
+ *   (a pose maps scaled camera coordinates to the volume's frame, x = R (s x_cam) + t), scales [n] fp32 or NULL: all on the device.
+ *   Per voxel centre c and frame, in fp32 with every operation rounded: d = c - t; p = Rt d; u = rint(fx p_x / p_z + cx), v likewise;
+ *   the sample counts when p_z > 0, 0 <= u <= w - 1, 0 <= v <= h - 1, boundaries[v][u] > 0.5, z = depth[v][u] finite and > 0 and
+ *   sdf = s z - p_z >= -truncation; then tsdf <- (tsdf weight + min(1, sdf / truncation)) / (weight + 1), each colour plane
+ *   likewise with the pixel's byte (plane c from byte c), weight <- min(weight + 1, max_weight).
+ *   scales NULL: s = 20.0f / (z_max - z_min) over the frame's pixels with boundaries > 0.5 of boundaries * depth, endo_evaluate_posed's
+ *   own scale.  flags [n] int32, device, written for every frame: ENDO_FUSION_FRAME_OK; _EMPTY (no such pixel); _ZERO_RANGE (z_max ==
+ *   z_min with scales NULL); _BAD_SCALE (a scale that is not finite and positive).  Only OK frames touch the volume.
+ *   options: ENDO_FUSION_NO_CULL integrates without the per-wave visibility test; the planes' bytes are the same either way.
+ *   truncation > 0, max_weight >= 1.  workspace: SCRATCH (the per-frame table).
+ * endo_fusion_extract_workspace_bytes(nx, ny, nz): the workspace of the next two entries (-1 for sizes outside the above).
+ * endo_fusion_count: two launches.  An edge from a voxel to its +x, +y or +z neighbour holds a surface point when both weights are
+ *   >= min_weight and exactly one of the two tsdf values is negative.  total (2 int64, device) receives 0 and the number of such edges;
+ *   the workspace receives every (k, j) row's offset and is read by endo_fusion_extract (STATE between the two calls).
+ * endo_fusion_extract: one launch after endo_fusion_count with the same arguments: rows (capacity x 6 fp32) receives, in (k, j, i)
+ *   order and +x, +y, +z inside a voxel, x, y, z (the voxel's centre with the edge's coordinate advanced by lambda * voxel_size,
+ *   lambda = t_a / (t_a - t_b)) and r, g, b = rint(col_a + lambda (col_b - col_a)) of colour planes 2, 1, 0.  Rows at or past
+ *   `capacity` are not written.  capacity 0 is valid.
+ * ------------------------------------------------------------------------------------------- */
+#define ENDO_FUSION_NO_CULL 1
+#define ENDO_FUSION_FRAME_OK 0
+#define ENDO_FUSION_FRAME_EMPTY 1
+#define ENDO_FUSION_FRAME_ZERO_RANGE 2
+#define ENDO_FUSION_FRAME_BAD_SCALE 3
+int endo_fusion_tile(int which);
+int64_t endo_fusion_workspace_bytes(int frames, int height, int width);
+int endo_fusion_clear(int nx, int ny, int nz, float* tsdf, float* weight, float* color, void* stream);
+int endo_fusion_integrate(const float* depth, const float* boundaries, const uint8_t* colors, const float* intrinsics,
+                          const double* rotations, const double* translations, const float* scales, int frames, int height, int width,
+                          const double* origin, double voxel_size, double truncation, float max_weight, int nx, int ny, int nz,
+                          float* tsdf, float* weight, float* color, int32_t* flags, int options, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int64_t endo_fusion_extract_workspace_bytes(int nx, int ny, int nz);
+int endo_fusion_count(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
+                      const float* color, float min_weight, int64_t* total, void* workspace, int64_t workspace_bytes, void* stream);
+int endo_fusion_extract(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
+                        const float* color, float min_weight, float* rows, int64_t capacity, int64_t* total, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
