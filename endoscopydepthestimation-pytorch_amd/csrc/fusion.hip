@@ -23,6 +23,7 @@
 //              exclusive scan of the nz * ny counts; the total is left for the caller's one 8-byte read
 //   extract    one block per row: rows (x, y, z, r, g, b) at the row's offset, voxels in i order and per voxel the edges +x, +y, +z,
 //              ranked inside a chunk of 256 voxels by the three ballots
+//   The volume, the edge test, the ranks and the row pass are in fusion_device.h: fusion_mesh.hip makes a triangle mesh of the same rows.
 //
 // numpy rounds every float32 operation on its own.  The file is compiled with -ffp-contract=off, as display.hip is, and the arithmetic
 // the restatement shares is written with explicit-rounding intrinsics besides: a contracted multiply-add anywhere in the update would
@@ -31,6 +32,7 @@
 
 #include "cloud_device.h"
 #include "common.h"
+#include "fusion_device.h"
 
 namespace endo {
 
@@ -40,7 +42,6 @@ constexpr int kBlockX = kBoxX * (kFusionThreads / kWave);
 constexpr int kFrameFloats = 32;                         // a row of the frame table
 // half the diagonal between the box's outermost voxel centres, (7.5, 1.5, 1.5) voxels, plus one voxel
 constexpr float kCullRadius = 8.8f;
-constexpr int64_t kMaxVoxels = static_cast<int64_t>(1) << 40;
 
 static_assert(kBoxX * kBoxY * kBoxZ == 4 * kWave, "a lane owns four voxels");
 
@@ -54,18 +55,6 @@ enum FrameSlot {
     kZNorm = 26,        // the norm of the rotation's third column (p_z's gradient)
     kActive = 27,       // 1.0f: the frame contributes
 };
-
-struct FusionVolume {
-    float* tsdf;
-    float* weight;
-    float* color;          // [3][nz][ny][nx]
-    int nx, ny, nz;
-    float ox, oy, oz, vs;
-};
-
-__device__ __forceinline__ float voxel_centre(float o, int idx, float vs) {
-    return __fadd_rn(o, __fmul_rn(__fadd_rn(static_cast<float>(idx), 0.5f), vs));
-}
 
 // p_r = (Rt[r][0] d_x + Rt[r][1] d_y) + Rt[r][2] d_z
 __device__ __forceinline__ float camera_coordinate(const float* rt, float dx, float dy, float dz) {
@@ -294,29 +283,6 @@ __global__ void __launch_bounds__(kFusionThreads) fusion_integrate_kernel(const 
     for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(g.color + c * voxels + idx) = make_float4(col[c][0], col[c][1], col[c][2], col[c][3]);
 }
 
-struct ExtractParams {
-    FusionVolume vol;
-    float min_weight;
-    int64_t* offsets;          // [nz * ny] counts after the count kernel, exclusive offsets after the scan
-    int64_t* total;            // [2]: 0, the total (cloud_scan_block's offsets of one group)
-    float* rows;               // [capacity][6]
-    int64_t capacity;
-};
-
-// bit e of the result: the edge from voxel (i, j, k) to its +x (0), +y (1), +z (2) neighbour holds a surface point
-__device__ __forceinline__ int surface_edges(const ExtractParams& q, int i, int j, int k, int64_t idx, float& ta) {
-    const FusionVolume& g = q.vol;
-    ta = g.tsdf[idx];
-    if (!(g.weight[idx] >= q.min_weight)) return 0;
-    const int64_t step[3] = {1, g.nx, static_cast<int64_t>(g.nx) * g.ny};
-    const bool has[3] = {i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
-    int edges = 0;
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-        if (has[e] && g.weight[idx + step[e]] >= q.min_weight && (ta < 0.0f) != (g.tsdf[idx + step[e]] < 0.0f)) edges |= 1 << e;
-    return edges;
-}
-
 __global__ void __launch_bounds__(kCloudThreads) fusion_count_kernel(const ExtractParams q) {
     const int j = blockIdx.x, k = blockIdx.y;
     const int64_t row = static_cast<int64_t>(k) * q.vol.ny + j;
@@ -334,80 +300,7 @@ __global__ void __launch_bounds__(kScanThreads) fusion_scan_kernel(const Extract
     cloud_scan_block(q.offsets, 1, q.vol.ny * q.vol.nz, q.total);
 }
 
-// cloud_chunk_rank for up to three rows per thread: the rank of this thread's first row among the rows of a chunk of kCloudThreads
-// voxels, voxel by voxel and +x, +y, +z inside a voxel, and the chunk's number of rows.  Every thread of the block calls.
-__device__ __forceinline__ int edge_chunk_rank(int edges, int& total) {
-    __shared__ int s_wave[kCloudThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bx = __ballot(edges & 1), by = __ballot(edges & 2), bz = __ballot(edges & 4);
-    if (lane == 0) s_wave[wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
-    __syncthreads();
-    const unsigned long long lower = (1ull << lane) - 1ull;
-    int rank = __popcll(bx & lower) + __popcll(by & lower) + __popcll(bz & lower);
-    for (int i = 0; i < wave; ++i) rank += s_wave[i];
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return rank;
-}
-
-__global__ void __launch_bounds__(kCloudThreads) fusion_write_kernel(const ExtractParams q) {
-    const FusionVolume& g = q.vol;
-    const int j = blockIdx.x, k = blockIdx.y;
-    const int64_t row = static_cast<int64_t>(k) * g.ny + j;
-    const int64_t voxels = static_cast<int64_t>(g.nx) * g.ny * g.nz;
-    const int64_t step[3] = {1, g.nx, static_cast<int64_t>(g.nx) * g.ny};
-    int64_t at = q.offsets[row];
-    for (int i0 = 0; i0 < g.nx; i0 += kCloudThreads) {
-        const int i = i0 + threadIdx.x;
-        const int64_t idx = row * g.nx + i;
-        float ta = 0.0f;
-        const int edges = i < g.nx ? surface_edges(q, i, j, k, idx, ta) : 0;
-        int total;
-        int rank = edge_chunk_rank(edges, total);
-        if (edges) {
-            const float c[3] = {voxel_centre(g.ox, i, g.vs), voxel_centre(g.oy, j, g.vs), voxel_centre(g.oz, k, g.vs)};
-            const float ca[3] = {g.color[idx], g.color[voxels + idx], g.color[2 * voxels + idx]};
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                if (!(edges & (1 << e))) continue;
-                const int64_t nb = idx + step[e];
-                const float lambda = __fdiv_rn(ta, __fsub_rn(ta, g.tsdf[nb]));
-                const int64_t dst = at + rank;
-                ++rank;
-                if (dst >= q.capacity) continue;          // (a caller that allocated fewer rows than the count: nothing outside them)
-                float* o = q.rows + dst * 6;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) o[a] = a == e ? __fadd_rn(c[a], __fmul_rn(lambda, g.vs)) : c[a];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {          // r, g, b = channels 2, 1, 0, as the posed writer reads them
-                    const float cb = g.color[(2 - ch) * voxels + nb];
-                    o[3 + ch] = rintf(__fadd_rn(ca[2 - ch], __fmul_rn(lambda, __fsub_rn(cb, ca[2 - ch]))));
-                }
-            }
-        }
-        at += total;
-    }
-}
-
-static bool volume_sizes_ok(int nx, int ny, int nz) {
-    if (nx <= 0 || ny <= 0 || nz <= 0 || nx % 4 != 0) return false;
-    if (ny > 65535 || nz > 65535) return false;          // the (y, z) grid of the row kernels
-    return static_cast<int64_t>(nx) * ny * nz <= kMaxVoxels;
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-static bool make_volume(const double* origin, double voxel_size, int nx, int ny, int nz, float* tsdf, float* weight, float* color,
-                        FusionVolume& g) {
-    if (!origin || !tsdf || !weight || !color || !volume_sizes_ok(nx, ny, nz)) return false;
-    if (!aligned16(tsdf) || !aligned16(weight) || !aligned16(color)) return false;
-    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return false;
-    const float vs = static_cast<float>(voxel_size);
-    if (!(vs > 0.0f) || !std::isfinite(vs)) return false;
-    g = FusionVolume{tsdf, weight, color, nx, ny, nz, static_cast<float>(origin[0]), static_cast<float>(origin[1]),
-                     static_cast<float>(origin[2]), vs};
-    return std::isfinite(g.ox) && std::isfinite(g.oy) && std::isfinite(g.oz);
-}
+__global__ void __launch_bounds__(kCloudThreads) fusion_write_kernel(const ExtractParams q) { fusion_write_rows<false>(q); }
 
 }  // namespace endo
 
@@ -469,26 +362,12 @@ extern "C" int endo_fusion_integrate(const float* depth, const float* boundaries
     return 0;
 }
 
-static int extract_params(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
-                          const float* color, float min_weight, int64_t* total, void* workspace, int64_t workspace_bytes,
-                          ExtractParams& q) {
-    if (!total || !workspace || std::isnan(min_weight)) return ENDO_E_BADARG;
-    if (!make_volume(origin, voxel_size, nx, ny, nz, const_cast<float*>(tsdf), const_cast<float*>(weight), const_cast<float*>(color), q.vol))
-        return ENDO_E_BADARG;
-    if (workspace_bytes < endo_fusion_extract_workspace_bytes(nx, ny, nz)) return ENDO_E_BADARG;
-    q.min_weight = min_weight;
-    q.offsets = static_cast<int64_t*>(workspace);
-    q.total = total;
-    q.rows = nullptr;
-    q.capacity = 0;
-    return 0;
-}
-
 extern "C" int endo_fusion_count(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
                                  const float* color, float min_weight, int64_t* total, void* workspace, int64_t workspace_bytes,
                                  void* stream_) {
     ExtractParams q;
-    const int err = extract_params(origin, voxel_size, nx, ny, nz, tsdf, weight, color, min_weight, total, workspace, workspace_bytes, q);
+    const int err = extract_params(origin, voxel_size, nx, ny, nz, tsdf, weight, color, min_weight, total, workspace, workspace_bytes,
+                                   endo_fusion_extract_workspace_bytes(nx, ny, nz), q);
     if (err) return err;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     ProfScope prof(kProfSmall, stream, 0.0, static_cast<double>(nx) * ny * nz * 24.0);
@@ -503,7 +382,8 @@ extern "C" int endo_fusion_extract(const double* origin, double voxel_size, int 
                                    const float* color, float min_weight, float* rows, int64_t capacity, int64_t* total, void* workspace,
                                    int64_t workspace_bytes, void* stream_) {
     ExtractParams q;
-    const int err = extract_params(origin, voxel_size, nx, ny, nz, tsdf, weight, color, min_weight, total, workspace, workspace_bytes, q);
+    const int err = extract_params(origin, voxel_size, nx, ny, nz, tsdf, weight, color, min_weight, total, workspace, workspace_bytes,
+                                   endo_fusion_extract_workspace_bytes(nx, ny, nz), q);
     if (err) return err;
     if (capacity < 0 || (capacity > 0 && !rows)) return ENDO_E_BADARG;
     if (capacity == 0) return 0;

@@ -519,8 +519,13 @@ def _write_fused(ready, path, rows, ply_text):
     utils.write_point_cloud(path, rows.numpy(), text=ply_text)
 
 
+def _write_fused_mesh(ready, path, vertices, normals, faces, ply_text):
+    ready.synchronize()
+    utils.write_mesh(path, vertices.numpy(), normals.numpy(), faces.numpy(), text=ply_text)
+
+
 def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, voxel_size=None, resolution=256, truncation_voxels=4,
-                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, **register_kwargs):
+                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, mesh=False, **register_kwargs):
     """One model of a sequence: every batch of ``frames`` (a dataset.TestFrames) through posed_test_outputs with the poses
     ``translation_dict[name]`` / ``rotation_dict[name]`` (the network's forward runs once); each batch's depth, colour images,
     boundaries, intrinsics and poses stay on the device, with the bounding box of its posed rows.  Then a fusion.TSDFVolume around
@@ -531,8 +536,11 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
     With ``target`` (a registration.TargetModel, or rows to make one of): the fused rows registered once with
     registration.register(**register_kwargs) from ``initial`` (_initial_transform), ``fused_registered.ply`` (the rows under that
     registration, colours kept) and a one-row ``fused_registration.csv`` with REGISTRATION_COLUMNS.
+    mesh=True: the surface comes from volume.extract_mesh -- the same rows, with normals and faces -- and ``fused_mesh.ply``
+    (utils.write_mesh) is written on the same pool; every other file is what it is without it.
     Returns a dictionary: frames (their number), empty and zero_range (names), voxel_size, dims and origin of the volume (None when no
-    frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None)."""
+    frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None), and with mesh=True triangles
+    (the mesh's faces)."""
     names_ahead = getattr(frames, "image_file_names", None)
     if names_ahead is not None:
         for name in names_ahead:
@@ -577,13 +585,21 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
                                                      truncation_voxels=truncation_voxels, max_weight=max_weight)
             for depth, boundaries, colors, intrinsics, rot, tr in kept:
                 volume.integrate(depth, boundaries, colors, intrinsics, rot, tr)
-            surface = volume.extract(min_weight)
+            if mesh:
+                surface, normals, faces = volume.extract_mesh(min_weight)
+            else:
+                surface = volume.extract(min_weight)
             result.update({"voxel_size": volume.voxel_size, "dims": volume.dims, "origin": volume.origin.copy(),
                            "observed_voxels": volume.observed_voxels()})
         else:
             surface = torch.zeros((0, 6), dtype=torch.float32)
+            normals, faces = torch.zeros((0, 3), dtype=torch.float32), torch.zeros((0, 3), dtype=torch.int32)
         result["points"] = int(surface.shape[0])
         pool.submit(_write_fused, os.path.join(out_dir, "fused_surface.ply"), surface.to("cpu", non_blocking=True), ply_text)
+        if mesh:
+            result["triangles"] = int(faces.shape[0])
+            pool.submit(_write_fused_mesh, os.path.join(out_dir, "fused_mesh.ply"), surface.to("cpu", non_blocking=True),
+                        normals.to("cpu", non_blocking=True), faces.to("cpu", non_blocking=True), ply_text)
         if target is not None:
             if not isinstance(target, registration.TargetModel):
                 target = registration.TargetModel(target)

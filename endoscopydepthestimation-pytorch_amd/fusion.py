@@ -8,7 +8,9 @@ reference has no code for this step; tests/fusion_restate.py is the numpy float3
                  against every frame of the batch in order; a wave whose box of voxels no frame can see loads and stores nothing;
                  one read of the per-frame flags
     at the end   volume.extract (three launches): the surface points on the grid's edges as (P, 6) rows of x, y, z, r, g, b, which
-                 registration.register and utils.write_point_cloud take as they are; one 8-byte read of the count in between
+                 registration.register and utils.write_point_cloud take as they are; one 8-byte read of the count in between;
+                 or volume.extract_mesh (csrc/fusion_mesh.hip, four launches): the same rows as vertices, a unit normal per row and
+                 the (T, 3) faces of marching cubes, which utils.write_mesh takes; tests/fusion_mesh_restate.py states them
 
 Depth maps, masks, colour images, intrinsics and poses are the ones evaluate.posed_outputs_from_predictions takes and returns: a pose
 maps scaled camera coordinates to the tracker's frame, ``x = R (s x_cam) + t``, and without explicit scales ``s`` is the posed
@@ -210,6 +212,38 @@ class TSDFVolume(object):
                                                _lib.ptr(total), _lib.ptr(workspace), self._extract_bytes, _lib.stream()),
                        "endo_fusion_extract")
         return rows
+
+    def extract_mesh(self, min_weight=1.0):
+        """The surface as a triangle mesh (csrc/fusion_mesh.hip, four launches): ``(vertices, normals, faces)`` on the device.
+        vertices (P, 6) fp32: the rows of ``extract(min_weight)``, byte for byte.  normals (P, 3) fp32: the unit gradient of the signed
+        distance at each row, from the surface towards the cameras; (0, 0, 0) where the gradient vanishes.  faces (T, 3) int32: the
+        rows of each triangle, counter-clockwise as seen from outside; marching cubes over the cells whose eight voxels all have
+        weight >= min_weight, cells in (k, j, i) order.  A row on the rim of the observed part that no such cell touches stays
+        unreferenced.  One 32-byte read of the two counts between the count and the write launches; P = 0 or T = 0 is valid."""
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError("min_weight is NaN")
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        origin = _host_doubles(self.origin)
+        need = int(lib.endo_fusion_mesh_workspace_bytes(nx, ny, nz))
+        with torch.cuda.device(self.device):
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            totals = torch.empty(4, dtype=torch.int64, device=self.device)
+            volume = (origin, self.voxel_size, nx, ny, nz, _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color), min_weight)
+            state = (_lib.ptr(totals), _lib.ptr(workspace), need, _lib.stream())
+            _lib.check(lib.endo_fusion_mesh_count(*(volume + state)), "endo_fusion_mesh_count")
+            _, points, _, triangles = totals.cpu().tolist()          # the one read between the scan and the write launches
+            if max(points, triangles) > 2 ** 31 - 1:
+                raise ValueError("a mesh of %d vertices and %d triangles does not fit int32 faces: extract a smaller volume" % (points, triangles))
+            vertices = torch.empty((points, 6), dtype=torch.float32, device=self.device)
+            normals = torch.empty((points, 3), dtype=torch.float32, device=self.device)
+            faces = torch.empty((triangles, 3), dtype=torch.int32, device=self.device)
+            _lib.check(lib.endo_fusion_mesh_vertices(*(volume + (_lib.ptr(vertices) if points else None, _lib.ptr(normals) if points else None,
+                                                                 points) + state)), "endo_fusion_mesh_vertices")
+            _lib.check(lib.endo_fusion_mesh_faces(*(volume + (_lib.ptr(faces) if triangles else None, triangles) + state)),
+                       "endo_fusion_mesh_faces")
+        return vertices, normals, faces
 
     def observed_voxels(self):
         """The number of voxels at least one frame has seen (one read)."""

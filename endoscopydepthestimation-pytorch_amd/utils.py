@@ -298,6 +298,50 @@ def write_point_cloud(path, point_cloud, text=True):
             f.write(rec.tobytes())
 
 
+_PLY_MESH_PROPERTIES = ("property float x", "property float y", "property float z", "property float nx", "property float ny",
+                        "property float nz", "property uchar red", "property uchar green", "property uchar blue")
+
+
+def write_mesh(path, vertices, normals, faces, text=False):
+    """A triangle mesh as PLY 1.0 without plyfile: a ``vertex`` element of float x, y, z, float nx, ny, nz and uchar red, green, blue
+    from the (P, 6) float32 ``vertices`` (x, y, z, r, g, b: fusion.TSDFVolume.extract_mesh's, the colours whole numbers in
+    [0, 255]) and the (P, 3) float32 ``normals``, and a ``face`` element of ``property list uchar int vertex_indices`` from the
+    (T, 3) int32 ``faces``.  text=False: binary_little_endian; text=True: ASCII in write_point_cloud's number format, one vertex or
+    face per line.  P = 0 and T = 0 are valid."""
+    import numpy as np
+    points = np.asarray(vertices, dtype=np.float32).reshape(-1, 6)
+    normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+    faces = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+    n, t = points.shape[0], faces.shape[0]
+    if normals.shape[0] != n:
+        raise ValueError("write_mesh expects one normal per vertex: %d normals for %d vertices" % (normals.shape[0], n))
+    if t and (faces.min() < 0 or faces.max() >= n):
+        raise ValueError("write_mesh: a face index lies outside the %d vertices" % n)
+    header = "\n".join(("ply", "format ascii 1.0" if text else "format binary_little_endian 1.0", "element vertex %d" % n)
+                       + _PLY_MESH_PROPERTIES + ("element face %d" % t, "property list uchar int vertex_indices", "end_header")) + "\n"
+    with open(str(path), "wb") as f:
+        f.write(header.encode("ascii"))
+        if text:
+            if n:
+                both = np.concatenate([points[:, :3], normals, points[:, 3:]], axis=1).astype(np.float64)
+                f.write((("%.9g %.9g %.9g %.9g %.9g %.9g %d %d %d\n" * n) % tuple(both.ravel().tolist())).encode("ascii"))
+            if t:
+                f.write((("3 %d %d %d\n" * t) % tuple(faces.ravel().tolist())).encode("ascii"))
+        else:
+            rec = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                     ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+            for k, name in enumerate(("x", "y", "z")):
+                rec[name] = points[:, k]
+                rec["n" + name] = normals[:, k]
+            for k, name in enumerate(("red", "green", "blue")):
+                rec[name] = points[:, 3 + k]
+            f.write(rec.tobytes())
+            tri = np.empty(t, dtype=[("count", "u1"), ("index", "<i4", (3,))])
+            tri["count"] = 3
+            tri["index"] = faces
+            f.write(tri.tobytes())
+
+
 def write_png(path, bgr, compress_level=1):
     """cv2.imwrite(path, bgr) for an (H, W, 3) uint8 image in cv2's B, G, R order, with zlib and struct only: an 8-bit RGB PNG
     (colour type 2, no interlace, filter type 0 on every row).  The pixels are the contract, not libpng's bytes."""

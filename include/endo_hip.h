@@ -1128,6 +1128,49 @@ int endo_fusion_extract(const double* origin, double voxel_size, int nx, int ny,
                         const float* color, float min_weight, float* rows, int64_t capacity, int64_t* total, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The fused surface as a triangle mesh (csrc/fusion_mesh.hip): marching cubes on the volume above.  The vertices are
+ * endo_fusion_extract's rows, byte for byte and in its order: every triangle corner lies on a grid edge whose two voxels differ in
+ * sign, and the extraction has one row per such edge.  Added here: which three rows form each triangle, and a unit normal per row.
+ * tests/fusion_mesh_restate.py is the numpy float32 statement, matched bit for bit.  An additive part of ABI 7.
+ *
+ * A cell is the voxels (i..i+1, j..j+1, k..k+1), 0 <= i < nx - 1 and likewise j, k; its corner c is voxel (i + (c & 1),
+ * j + ((c >> 1) & 1), k + ((c >> 2) & 1)) and its case the sum of (tsdf[c] < 0) << c.  Cell edge e = 4 a + p runs along axis a from its
+ * start corner, p = (bit o0 of the start corner) + 2 (bit o1), o0 < o1 the other two axes; its vertex is the row of the start corner's
+ * voxel, edge a.  A cell takes part when all eight weights are >= min_weight.  The case table is built by rule
+ * (tools/gen_fusion_mesh_table.py writes csrc/fusion_mesh_table.h): at most 5 triangles per case, 820 over the 256 cases, triangle
+ * normals (right-hand rule) from negative to positive tsdf, and two cells that share a face cut it the same way: the mesh of a volume
+ * whose cells all take part is closed.
+ *
+ * endo_fusion_mesh_case(index, edges): HOST only, no device work.  Returns the case's number of triangles and, with edges != NULL,
+ *   its 15 cell-edge ids (3 per triangle, in order, padded with -1); -1 for an index outside 0..255.
+ * endo_fusion_mesh_workspace_bytes(nx, ny, nz): the workspace of the next three entries (-1 for sizes outside the volume's).
+ * endo_fusion_mesh_count: two launches.  totals (4 int64, device) receives 0, P, 0, T: P endo_fusion_count's number, T the number of
+ *   triangles of the cells that take part; the workspace receives every (k, j) voxel row's and cell row's offset and is read by the
+ *   next two entries (STATE between the calls).
+ * endo_fusion_mesh_vertices: one launch after endo_fusion_mesh_count with the same arguments: rows (capacity x 6 fp32) as
+ *   endo_fusion_extract writes them, and normals (capacity x 3 fp32): with g_x = t[min(i + 1, nx - 1)] - t[max(i - 1, 0)] and g_y, g_z
+ *   likewise at a voxel (no division; neighbours as they stand, whatever their weight), v = g_a + lambda (g_b - g_a) per component
+ *   for the row's edge a -> b and its own lambda, n = v / sqrt((v_x v_x + v_y v_y) + v_z v_z), every fp32 operation rounded on its
+ *   own, and n = (0, 0, 0) where that length is 0 or not finite.  Rows at or past `capacity` are not written.
+ * endo_fusion_mesh_faces: one launch after endo_fusion_mesh_count with the same arguments: faces (capacity x 3 int32) receives the
+ *   row indices of the triangles, cells in (k, j, i) order and a cell's triangles in table order.  Faces at or past `capacity` are not
+ *   written.  Rows that no cell taking part touches stay unreferenced.
+ *   Faces are int32: a capacity above 2^31 - 1 is ENDO_E_BADARG in both entries, and where P or T as counted exceeds it the launch
+ *   writes no face (the caller has read both and reports it).  capacity 0 is valid in both.
+ * ------------------------------------------------------------------------------------------- */
+int endo_fusion_mesh_case(int index, int32_t* edges);
+int64_t endo_fusion_mesh_workspace_bytes(int nx, int ny, int nz);
+int endo_fusion_mesh_count(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
+                           const float* color, float min_weight, int64_t* totals, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+int endo_fusion_mesh_vertices(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
+                              const float* color, float min_weight, float* rows, float* normals, int64_t capacity, int64_t* totals,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int endo_fusion_mesh_faces(const double* origin, double voxel_size, int nx, int ny, int nz, const float* tsdf, const float* weight,
+                           const float* color, float min_weight, int32_t* faces, int64_t capacity, int64_t* totals, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
