@@ -162,6 +162,9 @@ SIGNATURES = {
     "endo_fusion_mesh_count": (_I, [_P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _F, _P, _P, _L, _P]),
     "endo_fusion_mesh_vertices": (_I, [_P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _F, _P, _P, _L, _P, _P, _L, _P]),
     "endo_fusion_mesh_faces": (_I, [_P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _F, _P, _L, _P, _P, _L, _P]),
+    "endo_fusion_render_tile": (_I, [_I]),
+    "endo_fusion_render_workspace_bytes": (_L, [_I] * 6),
+    "endo_fusion_render": (_I, [_P, ctypes.c_double, ctypes.c_double, _I, _I, _I] + [_P] * 8 + [_I, _I, _I, _F, _F, _I] + [_P] * 5 + [_L, _P]),
 }
 
 # the backward bricks of the 16-bit-storage family (one launch of endo_net16_bwd each), over bf16 and over half

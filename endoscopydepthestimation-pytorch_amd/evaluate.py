@@ -41,7 +41,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, display, fusion, models, registration, utils
+from . import _lib, display, fusion, losses, models, registration, utils
 from .train_step import mask_mul
 
 
@@ -524,8 +524,27 @@ def _write_fused_mesh(ready, path, vertices, normals, faces, ply_text):
     utils.write_mesh(path, vertices.numpy(), normals.numpy(), faces.numpy(), text=ply_text)
 
 
+CONSISTENCY_COLUMNS = ("name", "pixels", "abs_rel", "sigma_1", "sigma_2", "sigma_3")
+
+
+def _write_fused_color(ready, path, image):
+    ready.synchronize()
+    utils.write_png(path, image.numpy())
+
+
+def _write_consistency(ready, path, names, metrics, pixels, rows):
+    ready.synchronize()
+    for name, m, p in zip(names, torch.cat(metrics).numpy().astype(np.float64), torch.cat(pixels).numpy()):
+        rows.append((name, int(p), float(m[0]), float(m[1]), float(m[2]), float(m[3])))
+    with open(path, "w") as f:
+        f.write(",".join(CONSISTENCY_COLUMNS) + "\n")
+        for row in rows:
+            f.write(",".join([row[0], str(row[1])] + [repr(v) for v in row[2:]]) + "\n")
+
+
 def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, voxel_size=None, resolution=256, truncation_voxels=4,
-                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, mesh=False, **register_kwargs):
+                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, mesh=False, render=False,
+                     **register_kwargs):
     """One model of a sequence: every batch of ``frames`` (a dataset.TestFrames) through posed_test_outputs with the poses
     ``translation_dict[name]`` / ``rotation_dict[name]`` (the network's forward runs once); each batch's depth, colour images,
     boundaries, intrinsics and poses stay on the device, with the bounding box of its posed rows.  Then a fusion.TSDFVolume around
@@ -538,9 +557,15 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
     registration, colours kept) and a one-row ``fused_registration.csv`` with REGISTRATION_COLUMNS.
     mesh=True: the surface comes from volume.extract_mesh -- the same rows, with normals and faces -- and ``fused_mesh.ply``
     (utils.write_mesh) is written on the same pool; every other file is what it is without it.
+    render=True: after the last batch is integrated, every frame that took part is rendered from its own pose (volume.render with the
+    frame's own scale 20 / (z_max - z_min), its boundaries and ``min_weight``): ``fused_color_<name>.png``, the model's colours as that
+    frame sees them, comparable with run_posed_test_phase's test_color_<name>.png, and ``fused_consistency.csv``, one row per such
+    frame of CONSISTENCY_COLUMNS: the hit pixels and losses.depth_metrics(the frame's predicted depth, the rendered depth, the hit
+    mask), the frame's AbsRel and sigma 1, 2, 3 against what the whole sequence agrees the surface is (NaN without a hit pixel); both on
+    the same pool.  Every other file is what it is without it.
     Returns a dictionary: frames (their number), empty and zero_range (names), voxel_size, dims and origin of the volume (None when no
-    frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None), and with mesh=True triangles
-    (the mesh's faces)."""
+    frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None), with mesh=True triangles
+    (the mesh's faces), and with render=True consistency (the table's rows)."""
     names_ahead = getattr(frames, "image_file_names", None)
     if names_ahead is not None:
         for name in names_ahead:
@@ -548,7 +573,7 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
             translation_dict[key], rotation_dict[key]          # KeyError before anything runs
     out_dir = str(out_dir)
     count = 0
-    empty, zero_range, kept, boxes = [], [], [], []
+    empty, zero_range, kept, boxes, views, consistency = [], [], [], [], [], []
     for batch in frames:
         names = list(batch["names"])
         rotations = [rotation_dict[name] for name in names]
@@ -574,6 +599,8 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
             pick = torch.tensor(good, dtype=torch.int64, device=dev)
             kept.append((out["depth"][pick], batch["boundaries"].to(dev)[pick], out["color_images"][pick], batch["intrinsics"].to(dev)[pick],
                          rot[pick], tr[pick]))
+            if render:          # the posed output's own scale of each frame: evaluate_posed.hip:150-151
+                views.append(([names[f] for f in good], np.float32(20.0) / (ranges[good, 1] - ranges[good, 0])))
     os.makedirs(out_dir, exist_ok=True)
     result = {"frames": count, "empty": empty, "zero_range": zero_range, "voxel_size": None, "dims": None, "origin": None, "points": 0,
               "observed_voxels": 0, "registration": None}
@@ -591,6 +618,18 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
                 surface = volume.extract(min_weight)
             result.update({"voxel_size": volume.voxel_size, "dims": volume.dims, "origin": volume.origin.copy(),
                            "observed_voxels": volume.observed_voxels()})
+            if render:
+                shown, metrics, pixels = [], [], []
+                for (depth, boundaries, _, intrinsics, rot, tr), (names, scales) in zip(kept, views):
+                    height, width = int(depth.shape[-2]), int(depth.shape[-1])
+                    seen = volume.render(intrinsics, rot, tr, height, width, scales=scales, boundaries=boundaries, min_weight=min_weight)
+                    metrics.append(losses.depth_metrics(depth.reshape(-1, 1, height, width), seen["depth"], seen["mask"]).to("cpu", non_blocking=True))
+                    pixels.append(seen["mask"].sum(dim=(1, 2, 3)).to("cpu", non_blocking=True))
+                    images = seen["colors"].to("cpu", non_blocking=True)
+                    shown += names
+                    for f, name in enumerate(names):
+                        pool.submit(_write_fused_color, os.path.join(out_dir, "fused_color_{}.png".format(name)), images[f])
+                pool.submit(_write_consistency, os.path.join(out_dir, "fused_consistency.csv"), shown, metrics, pixels, consistency)
         else:
             surface = torch.zeros((0, 6), dtype=torch.float32)
             normals, faces = torch.zeros((0, 3), dtype=torch.float32), torch.zeros((0, 3), dtype=torch.int32)
@@ -612,4 +651,8 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
                 f.write(",".join(str(v) for v in ("fused", int(surface.shape[0]), fit.count, repr(fit.scale), repr(fit.mean), repr(fit.rms),
                                                   repr(fit.max), fit.iterations, int(fit.converged))) + "\n")
             result["registration"] = fit
+    if render:
+        result["consistency"] = consistency
+        if not boxes:          # no frame took part: the table has its header alone
+            _write_consistency(torch.cuda.Event(), os.path.join(out_dir, "fused_consistency.csv"), [], [torch.zeros((0, 4))], [torch.zeros(0)], consistency)
     return result

@@ -11,6 +11,9 @@ reference has no code for this step; tests/fusion_restate.py is the numpy float3
                  registration.register and utils.write_point_cloud take as they are; one 8-byte read of the count in between;
                  or volume.extract_mesh (csrc/fusion_mesh.hip, four launches): the same rows as vertices, a unit normal per row and
                  the (T, 3) faces of marching cubes, which utils.write_mesh takes; tests/fusion_mesh_restate.py states them
+    at any time  volume.render (csrc/fusion_render.hip, two launches whatever the batch, no read): the volume seen from posed cameras,
+                 a ray per pixel to the first zero crossing of the trilinear tsdf: depth, mask, colours and normals on the device;
+                 tests/fusion_render_restate.py states them
 
 Depth maps, masks, colour images, intrinsics and poses are the ones evaluate.posed_outputs_from_predictions takes and returns: a pose
 maps scaled camera coordinates to the tracker's frame, ``x = R (s x_cam) + t``, and without explicit scales ``s`` is the posed
@@ -27,6 +30,7 @@ from . import _lib
 
 FLAGS = ("ok", "empty", "zero_range", "bad_scale")          # ENDO_FUSION_FRAME_* of include/endo_hip.h
 NO_CULL = 1                                                 # ENDO_FUSION_NO_CULL
+NO_SKIP = 2                                                 # ENDO_FUSION_NO_SKIP
 
 
 def __getattr__(name):
@@ -34,6 +38,10 @@ def __getattr__(name):
     if name == "WAVE_BOX":
         lib = _lib.load()
         return tuple(int(lib.endo_fusion_tile(which)) for which in range(3))
+    # the render kernel's: the pixel tile of one wave (x, y), and the cells of a brick of the empty-space marks (x, y, z)
+    if name in ("RENDER_TILE", "RENDER_BRICK"):
+        lib = _lib.load()
+        return tuple(int(lib.endo_fusion_render_tile(which)) for which in (range(2) if name == "RENDER_TILE" else range(2, 5)))
     raise AttributeError(name)
 
 
@@ -244,6 +252,57 @@ class TSDFVolume(object):
             _lib.check(lib.endo_fusion_mesh_faces(*(volume + (_lib.ptr(faces) if triangles else None, triangles) + state)),
                        "endo_fusion_mesh_faces")
         return vertices, normals, faces
+
+    def render(self, intrinsics, rotations, translations, height, width, scales=None, boundaries=None, min_weight=1.0, step=0.5, skip=True):
+        """The volume seen by N posed cameras (csrc/fusion_render.hip, two launches whatever N is, no read back): one ray per pixel,
+        sampled every ``step`` voxels of distance, to the first zero crossing of the trilinear tsdf between two samples whose eight
+        voxels all have weight >= min_weight (extract_mesh's cell rule).  intrinsics (N, 3, 3) fp32 on the device; rotations
+        (N, 3, 3) and translations (N, 3) as integrate takes them; scales: N per-frame scales or None for ones -- with a frame's own
+        scale the depth is in the units of that frame's prediction; boundaries (N, 1, H, W) or (N, H, W) fp32 or None: a pixel that is
+        not > 0.5 casts no ray.  0 < step <= truncation / voxel_size.  skip=False marches without the empty-space marks: same bytes,
+        more traffic.  Returns a dictionary of device tensors, all 0 where a ray meets no surface: ``depth`` and ``mask`` (N, 1, H, W)
+        fp32, ``colors`` (N, H, W, 3) uint8 in the byte order integrate took, ``normals`` (N, H, W, 3) fp32 unit vectors in the
+        tracker's frame, from the surface towards free space.  tests/fusion_render_restate.py states all four, bit for bit."""
+        n, height, width = (int(intrinsics.shape[0]) if torch.is_tensor(intrinsics) and intrinsics.dim() == 3 else 0), int(height), int(width)
+        min_weight, step = float(min_weight), float(step)
+        if math.isnan(min_weight):
+            raise ValueError("min_weight is NaN")
+        if not (step > 0.0 and float(np.float32(step) * np.float32(self.voxel_size)) <= float(np.float32(self.truncation))):
+            raise ValueError("step must be positive and at most truncation / voxel_size = %g voxels, not %r" % (
+                self.truncation / self.voxel_size, step))
+        if n <= 0:
+            raise ValueError("intrinsics must be an (N, 3, 3) device tensor")
+        intrinsics = _device_tensor(intrinsics, torch.float32, (n, 3, 3), "intrinsics")
+        if boundaries is not None:
+            boundaries = _device_tensor(boundaries, torch.float32, (n, height, width), "boundaries")
+        for name, t in (("intrinsics", intrinsics), ("boundaries", boundaries)):
+            if t is not None and t.device != self.device:
+                raise ValueError("%s lives on %s, the volume on %s" % (name, t.device, self.device))
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        need = int(lib.endo_fusion_render_workspace_bytes(n, height, width, nx, ny, nz))
+        if need < 0:
+            raise ValueError("%d frames of %d x %d from %d x %d x %d voxels are outside endo_fusion_render's sizes" % (n, height, width, nx, ny, nz))
+        rotations, translations = _poses(rotations, translations, n, self.device)
+        if scales is not None:
+            if not torch.is_tensor(scales):
+                scales = torch.from_numpy(np.ascontiguousarray(np.asarray(scales, np.float32).reshape(-1)))
+            if int(scales.numel()) != n:
+                raise ValueError("scales must hold one value per frame: %d, not %d" % (n, int(scales.numel())))
+            scales = scales.detach().to(device=self.device, dtype=torch.float32).reshape(n).contiguous()
+        with torch.cuda.device(self.device):
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            out = {"depth": torch.empty((n, 1, height, width), dtype=torch.float32, device=self.device),
+                   "mask": torch.empty((n, 1, height, width), dtype=torch.float32, device=self.device),
+                   "colors": torch.empty((n, height, width, 3), dtype=torch.uint8, device=self.device),
+                   "normals": torch.empty((n, height, width, 3), dtype=torch.float32, device=self.device)}
+            _lib.check(lib.endo_fusion_render(_host_doubles(self.origin), self.voxel_size, self.truncation, nx, ny, nz, _lib.ptr(self.tsdf),
+                                              _lib.ptr(self.weight), _lib.ptr(self.color), _lib.ptr(intrinsics), _lib.ptr(rotations),
+                                              _lib.ptr(translations), _lib.ptr(scales), _lib.ptr(boundaries), n, height, width, min_weight,
+                                              step, 0 if skip else NO_SKIP, _lib.ptr(out["depth"]), _lib.ptr(out["mask"]),
+                                              _lib.ptr(out["colors"]), _lib.ptr(out["normals"]), _lib.ptr(workspace), need, _lib.stream()),
+                       "endo_fusion_render")
+        return out
 
     def observed_voxels(self):
         """The number of voxels at least one frame has seen (one read)."""

@@ -1171,6 +1171,57 @@ int endo_fusion_mesh_faces(const double* origin, double voxel_size, int nx, int 
                            const float* color, float min_weight, int32_t* faces, int64_t capacity, int64_t* totals, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The fused volume seen from a pose (csrc/fusion_render.hip): one ray per pixel marched to the first zero crossing of the trilinear
+ * tsdf, with depth, colour and normal there.  The reference has no code for it; tests/fusion_render_restate.py is the numpy float32
+ * statement, matched bit for bit.  An additive part of ABI 7.  Every fp32 operation below is rounded on its own, in the order written.
+ *
+ * The frame.  R = the rotation rounded to fp32, T = the translation rounded to fp32 (a pose maps scaled camera coordinates to the
+ *   volume's frame, x = R (s x_cam) + t, as in endo_fusion_integrate), fx, cx, fy, cy from intrinsics, s = scales[f] or 1 with scales
+ *   NULL.  A frame whose s is not finite and positive casts no ray.  L = step * voxel_size (step in voxels; step > 0, L <= truncation,
+ *   and (nx + ny + nz + 6) / step <= 2^20), I = 1 / voxel_size.
+ * The ray of pixel (u, v).  d_x = (float(u) - cx) / fx, d_y = (float(v) - cy) / fy, d_z = 1, so the ray parameter is the scaled camera
+ *   depth s z.  w_r = (R[r][0] d_x + R[r][1] d_y) + R[r][2];  dt = L / sqrt((d_x d_x + d_y d_y) + 1): `step` voxels of distance per
+ *   sample for every pixel.  A pixel with boundaries != NULL and not boundaries[v][u] > 0.5, or whose dt is not finite and positive,
+ *   casts no ray.
+ * Sample k = 1, 2, ... 2^20, on a grid that does not depend on which samples are evaluated: t_k = float(k) dt, x_a = T_a + t_k w_a,
+ *   g_a = (x_a - origin_a) I - 0.5, cell c_a = floor(g_a), fractions r_a = g_a - c_a.  The sample is VALID when 0 <= c_a <= n_a - 2 on
+ *   every axis and all eight voxels (c_x + 0/1, c_y + 0/1, c_z + 0/1) have weight >= min_weight: endo_fusion_mesh_count's cell rule.
+ *   lerp(p, q, r) = p + r (q - p).  Its value: f = lerp(lerp(a00, a10, r_y), lerp(a01, a11, r_y), r_z) with a_yz = lerp(t_0yz, t_1yz, r_x)
+ *   over the tsdf; a plane's value at the sample likewise.  Its gradient, from the same differences: with d_yz = t_1yz - t_0yz,
+ *   a_yz = t_0yz + r_x d_yz, e_z = a_1z - a_0z, b_z = a_0z + r_y e_z:  G_x = lerp(lerp(d00, d10, r_y), lerp(d01, d11, r_y), r_z),
+ *   G_y = lerp(e_0, e_1, r_z), G_z = b_1 - b_0 (and f = b_0 + r_z G_z, the same number).
+ * The outcome.  The first valid sample k with f <= 0 ends the ray.  It is a HIT when k > 1, sample k - 1 is valid and its value f' > 0:
+ *   lambda = f' / (f' - f), t* = float(k - 1) dt + lambda dt.  Otherwise the ray ends without a hit (the camera inside or behind the
+ *   surface, or an unobserved gap in front of it).  A ray no sample ends is a miss.  Samples outside the grid are invalid, so the
+ *   kernel clips k to the ray's passage through the grid, conservatively; a grid that lies beyond sample 2^20 of a ray is not seen.
+ * The outputs, device, all 0 where there is no hit:  depth [n][h][w] fp32 = t* / s;  mask [n][h][w] fp32 = 1;  colors [n][h][w][3]
+ *   uint8: byte c = min(max(rint(lerp(plane c at sample k - 1, plane c at sample k, lambda)), 0), 255), the byte order
+ *   endo_fusion_integrate took;  normals [n][h][w][3] fp32: v = lerp(G', G, lambda) per component, n = v / sqrt((v_x v_x + v_y v_y) +
+ *   v_z v_z), (0, 0, 0) where that length is 0 or not finite: from the surface towards free space, as endo_fusion_mesh_vertices'.
+ * Empty-space skipping.  A first launch marks every brick: brick (bx, by, bz) is the cells whose base voxel has c_a / B = b_a, so it
+ *   covers voxels b_a B .. b_a B + B on every axis (one voxel shared with the next brick), and its mark is "holds a voxel with
+ *   weight >= min_weight and tsdf <= 0".  A sample whose cell lies in an unmarked brick has eight positive corners or is invalid: it
+ *   cannot end a ray and is not evaluated.  The ending sample found, sample k - 1 is evaluated whether its brick is marked or not.
+ *   ENDO_FUSION_NO_SKIP marches without marks (one launch); every output byte is the same either way.
+ *
+ * endo_fusion_render_tile(which): 0, 1: the pixel tile of one wave (x, y); 2, 3, 4: B, the brick's cells (x, y, z).
+ * endo_fusion_render_workspace_bytes(n, h, w, nx, ny, nz): the workspace (the marks); -1 outside endo_fusion_integrate's sizes,
+ *   for nx > 2^24 or h > 65535 * 16.
+ * endo_fusion_render: two launches whatever n is, no host read.  The volume as in endo_fusion_extract plus its truncation; intrinsics
+ *   [n][3][3] fp32, rotations [n][3][3] and translations [n][3] fp64, scales [n] fp32 or NULL, boundaries [n][h][w] fp32 or NULL: all on
+ *   the device.  ENDO_E_BADARG before any device work for a NULL or misaligned plane, a NULL output, sizes outside the above, a step
+ *   outside its bounds, a NaN min_weight, unknown options or a workspace that is too small.  The planes are only read.  workspace: SCRATCH.
+ * ------------------------------------------------------------------------------------------- */
+#define ENDO_FUSION_NO_SKIP 2
+int endo_fusion_render_tile(int which);
+int64_t endo_fusion_render_workspace_bytes(int frames, int height, int width, int nx, int ny, int nz);
+int endo_fusion_render(const double* origin, double voxel_size, double truncation, int nx, int ny, int nz, const float* tsdf,
+                       const float* weight, const float* color, const float* intrinsics, const double* rotations,
+                       const double* translations, const float* scales, const float* boundaries, int frames, int height, int width,
+                       float min_weight, float step, int options, float* depth, float* mask, uint8_t* colors, float* normals,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
