@@ -31,7 +31,8 @@ pose as its start, ``registration_errors.csv`` and the registered clouds.
 
 run_fusion_phase makes one model of the sequence before that step: the posed outputs per batch, their depth maps fused into a
 fusion.TSDFVolume around the posed clouds' bounding box (csrc/fusion.hip), the surface written as ``fused_surface.ply`` and, with a
-target, registered once.
+target, registered once.  With refine=K the frames are first tracked against that volume (csrc/fusion_track.hip) and fused again
+under the refined poses and scales, K times.
 """
 
 import os
@@ -542,8 +543,50 @@ def _write_consistency(ready, path, names, metrics, pixels, rows):
             f.write(",".join([row[0], str(row[1])] + [repr(v) for v in row[2:]]) + "\n")
 
 
+TRACKING_COLUMNS = ("name", "status", "iterations", "count", "rms_before", "rms_after", "rotation_degrees", "translation", "scale_ratio")
+
+
+def _write_tracking(path, rows):
+    with open(path, "w") as f:
+        f.write(",".join(TRACKING_COLUMNS) + "\n")
+        for row in rows:
+            f.write(",".join([row[0], row[1], str(row[2]), str(row[3])] + [repr(v) for v in row[4:]]) + "\n")
+
+
+def _refine_poses(volume, kept, poses, names, rounds, min_weight):
+    """run_fusion_phase's refine: ``rounds`` times, every kept batch tracked against the volume (fusion.TSDFVolume.track), the volume
+    cleared and the batches integrated again under the poses and scales found.  ``poses``: per batch (rotations, translations,
+    scales) as host fp64 arrays, updated in place.  A frame whose tracking does not end "ok" keeps the pose and scale it entered the
+    round with: the tracker's own in the first.  Returns the rows of TRACKING_COLUMNS, one per frame: status, count and rms after of the
+    last round, the iterations of all rounds, rms before of the first, and the change from the tracker's pose and the frame's own scale."""
+    first = [tuple(a.copy() for a in pose) for pose in poses]
+    state = [[{"iterations": 0, "before": None} for _ in batch_names] for batch_names in names]
+    fits = []
+    for _ in range(rounds):
+        fits = [volume.track(depth, boundaries, intrinsics, pose[0], pose[1], scales=pose[2], min_weight=min_weight)
+                for (depth, boundaries, _, intrinsics, _, _), pose in zip(kept, poses)]          # every batch against the same model
+        for pose, batch_fits, batch_state in zip(poses, fits, state):
+            for f, (fit, frame) in enumerate(zip(batch_fits, batch_state)):
+                frame["iterations"] += fit.iterations
+                if frame["before"] is None:
+                    frame["before"] = fit.initial_rms
+                if fit.status == "ok":
+                    pose[0][f], pose[1][f], pose[2][f] = fit.rotation, fit.translation, fit.scale
+        volume.clear()
+        for (depth, boundaries, colors, intrinsics, _, _), pose in zip(kept, poses):
+            volume.integrate(depth, boundaries, colors, intrinsics, pose[0], pose[1], scales=pose[2].astype(np.float32))
+    rows = []
+    for pose, start, batch_fits, batch_state, batch_names in zip(poses, first, fits, state, names):
+        for f, (fit, frame, name) in enumerate(zip(batch_fits, batch_state, batch_names)):
+            cosine = (float(np.trace(pose[0][f] @ start[0][f].T)) - 1.0) / 2.0
+            rows.append((name, fit.status, frame["iterations"], fit.count, float(frame["before"]), float(fit.rms),
+                         float(np.degrees(np.arccos(min(1.0, max(-1.0, cosine))))), float(np.linalg.norm(pose[1][f] - start[1][f])),
+                         float(pose[2][f] / start[2][f])))
+    return rows
+
+
 def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, voxel_size=None, resolution=256, truncation_voxels=4,
-                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, mesh=False, render=False,
+                     min_weight=2.0, max_weight=64.0, target=None, initial=None, ply_text=False, mesh=False, render=False, refine=0,
                      **register_kwargs):
     """One model of a sequence: every batch of ``frames`` (a dataset.TestFrames) through posed_test_outputs with the poses
     ``translation_dict[name]`` / ``rotation_dict[name]`` (the network's forward runs once); each batch's depth, colour images,
@@ -563,17 +606,30 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
     frame of CONSISTENCY_COLUMNS: the hit pixels and losses.depth_metrics(the frame's predicted depth, the rendered depth, the hit
     mask), the frame's AbsRel and sigma 1, 2, 3 against what the whole sequence agrees the surface is (NaN without a hit pixel); both on
     the same pool.  Every other file is what it is without it.
+    refine=K > 0: after the sequence is integrated, K times: every frame that took part is tracked against the volume
+    (fusion.TSDFVolume.track(min_weight=min_weight), a similarity per frame, each frame starting from the tracker's pose
+    and its own scale 20 / (z_max - z_min)), the volume is cleared and the batches are integrated again under the refined poses and
+    explicit scales; a frame whose tracking does not end "ok" keeps the pose it had.  The surface, the mesh, the renders and the
+    registration then come from the final volume and the final poses.  ``fused_tracking.csv`` has one row per such frame of
+    TRACKING_COLUMNS: status, iterations, count, the rms of the signed distances before and after, and how far the pose moved:
+    the rotation in degrees, the translation, the ratio of the scales.  A known bias: a frame is tracked against a model that
+    contains the frame itself, with 1 / weight of every voxel it saw, which pulls it towards where it already is; tracking a frame
+    before it is integrated, or taking it out first, is not done here.  With refine=0 every file and the dictionary are what they are
+    without it.
     Returns a dictionary: frames (their number), empty and zero_range (names), voxel_size, dims and origin of the volume (None when no
     frame took part), points (the surface's rows), observed_voxels, registration (a registration.Registration, or None), with mesh=True triangles
-    (the mesh's faces), and with render=True consistency (the table's rows)."""
+    (the mesh's faces), with render=True consistency (the table's rows), and with refine > 0 tracking (fused_tracking.csv's rows) and poses (name -> the final rotation, translation and scale)."""
     names_ahead = getattr(frames, "image_file_names", None)
     if names_ahead is not None:
         for name in names_ahead:
             key = os.path.basename(str(name))[-12:-4]
             translation_dict[key], rotation_dict[key]          # KeyError before anything runs
     out_dir = str(out_dir)
+    refine = int(refine)
+    if refine < 0:
+        raise ValueError("refine must not be negative, not %d" % refine)
     count = 0
-    empty, zero_range, kept, boxes, views, consistency = [], [], [], [], [], []
+    empty, zero_range, kept, boxes, views, consistency, tracking = [], [], [], [], [], [], []
     for batch in frames:
         names = list(batch["names"])
         rotations = [rotation_dict[name] for name in names]
@@ -599,7 +655,7 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
             pick = torch.tensor(good, dtype=torch.int64, device=dev)
             kept.append((out["depth"][pick], batch["boundaries"].to(dev)[pick], out["color_images"][pick], batch["intrinsics"].to(dev)[pick],
                          rot[pick], tr[pick]))
-            if render:          # the posed output's own scale of each frame: evaluate_posed.hip:150-151
+            if render or refine:          # the posed output's own scale of each frame: evaluate_posed.hip:150-151
                 views.append(([names[f] for f in good], np.float32(20.0) / (ranges[good, 1] - ranges[good, 0])))
     os.makedirs(out_dir, exist_ok=True)
     result = {"frames": count, "empty": empty, "zero_range": zero_range, "voxel_size": None, "dims": None, "origin": None, "points": 0,
@@ -612,6 +668,13 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
                                                      truncation_voxels=truncation_voxels, max_weight=max_weight)
             for depth, boundaries, colors, intrinsics, rot, tr in kept:
                 volume.integrate(depth, boundaries, colors, intrinsics, rot, tr)
+            if refine:
+                poses = [(rot.cpu().numpy(), tr.cpu().numpy(), scales.astype(np.float64)) for (_, _, _, _, rot, tr), (_, scales) in zip(kept, views)]
+                tracking += _refine_poses(volume, kept, poses, [names for names, _ in views], refine, min_weight)
+                result["poses"] = {name: (pose[0][f].copy(), pose[1][f].copy(), float(pose[2][f]))
+                                   for (names, _), pose in zip(views, poses) for f, name in enumerate(names)}
+                kept = [batch[:4] + (rot, tr) for batch, (rot, tr, _) in zip(kept, poses)]
+                views = [(names, scales.astype(np.float32)) for (names, _), (_, _, scales) in zip(views, poses)]
             if mesh:
                 surface, normals, faces = volume.extract_mesh(min_weight)
             else:
@@ -651,6 +714,10 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
                 f.write(",".join(str(v) for v in ("fused", int(surface.shape[0]), fit.count, repr(fit.scale), repr(fit.mean), repr(fit.rms),
                                                   repr(fit.max), fit.iterations, int(fit.converged))) + "\n")
             result["registration"] = fit
+    if refine:
+        result["tracking"] = tracking
+        result.setdefault("poses", {})
+        _write_tracking(os.path.join(out_dir, "fused_tracking.csv"), tracking)
     if render:
         result["consistency"] = consistency
         if not boxes:          # no frame took part: the table has its header alone

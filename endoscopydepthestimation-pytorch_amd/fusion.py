@@ -14,6 +14,10 @@ reference has no code for this step; tests/fusion_restate.py is the numpy float3
     at any time  volume.render (csrc/fusion_render.hip, two launches whatever the batch, no read): the volume seen from posed cameras,
                  a ray per pixel to the first zero crossing of the trilinear tsdf: depth, mask, colours and normals on the device;
                  tests/fusion_render_restate.py states them
+    at any time  volume.residuals / volume.track (csrc/fusion_track.hip, two launches per call whatever the batch, one read of 40
+                 doubles per frame): each predicted pixel's signed distance to the model under its frame's scale and pose, and
+                 Gauss-Newton on those distances over a similarity per frame, solved on the host; tests/fusion_track_restate.py
+                 states them
 
 Depth maps, masks, colour images, intrinsics and poses are the ones evaluate.posed_outputs_from_predictions takes and returns: a pose
 maps scaled camera coordinates to the tracker's frame, ``x = R (s x_cam) + t``, and without explicit scales ``s`` is the posed
@@ -31,6 +35,7 @@ from . import _lib
 FLAGS = ("ok", "empty", "zero_range", "bad_scale")          # ENDO_FUSION_FRAME_* of include/endo_hip.h
 NO_CULL = 1                                                 # ENDO_FUSION_NO_CULL
 NO_SKIP = 2                                                 # ENDO_FUSION_NO_SKIP
+TRACK_SUMS = 40                                             # endo_fusion_track's doubles per frame
 
 
 def __getattr__(name):
@@ -42,6 +47,10 @@ def __getattr__(name):
     if name in ("RENDER_TILE", "RENDER_BRICK"):
         lib = _lib.load()
         return tuple(int(lib.endo_fusion_render_tile(which)) for which in (range(2) if name == "RENDER_TILE" else range(2, 5)))
+    # the track kernel's: the pixel tile of one block (x, y) and the consecutive tiles of a frame a block walks
+    if name == "TRACK_TILE":
+        lib = _lib.load()
+        return tuple(int(lib.endo_fusion_track_tile(which)) for which in range(3))
     raise AttributeError(name)
 
 
@@ -64,6 +73,57 @@ def _device_tensor(t, dtype, shape, name):
 def _poses(rotations, translations, n, dev):
     from . import evaluate          # (evaluate imports this module)
     return evaluate._poses_f64(rotations, translations, n, dev)
+
+
+def _track_rms(sums):
+    return math.sqrt(float(sums[1] / sums[0])) if sums[0] > 0 else float("nan")
+
+
+def rodrigues(omega):
+    """exp([omega]x) in fp64: the rotation about ``omega`` by its length in radians."""
+    omega = np.asarray(omega, np.float64).reshape(3)
+    angle = float(np.linalg.norm(omega))
+    k = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]], [-omega[1], omega[0], 0.0]])
+    if angle < 1.0e-12:
+        return np.eye(3) + k
+    return np.eye(3) + (math.sin(angle) / angle) * k + ((1.0 - math.cos(angle)) / (angle * angle)) * (k @ k)
+
+
+def gauss_newton_step(sums, with_scale=True, damping=0.0):
+    """One frame's 40 sums of endo_fusion_track to its step (omega, tau, sigma), 7 fp64 numbers (sigma 0 without the scale): the
+    solution of ``(JtJ + damping diag(JtJ)) delta = -Jt r`` through a Cholesky factorisation; None where that fails (a system that is
+    not positive definite, or not finite)."""
+    m = 7 if with_scale else 6
+    full = np.zeros((7, 7))
+    full[np.triu_indices(7)] = np.asarray(sums, np.float64)[12:40]
+    full = full + np.triu(full, 1).T
+    a, b = full[:m, :m], np.asarray(sums, np.float64)[5:5 + m]
+    a = a + float(damping) * np.diag(np.diag(a))
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return None
+    try:
+        lower = np.linalg.cholesky(a)
+    except np.linalg.LinAlgError:
+        return None
+    delta = np.zeros(7)
+    delta[:m] = -np.linalg.solve(lower.T, np.linalg.solve(lower, b))
+    return delta if np.isfinite(delta).all() else None
+
+
+class Tracking(object):
+    """One frame's result of TSDFVolume.track: rotation (3 x 3), translation and scale of the refined pose ``x = R (s x_cam) + t`` (the
+    input's for a frame that failed); status, "ok", "bad_scale", "too_few" or "singular"; iterations (the steps taken), converged;
+    count and rms of the signed distances under the returned pose; initial_rms (under the input pose) and history (the rms of every
+    iteration, before its update)."""
+
+    def __init__(self, rotation, translation, scale, iterations, converged, status, count, rms, initial_rms, history):
+        self.rotation, self.translation, self.scale = np.array(rotation, np.float64), np.array(translation, np.float64), float(scale)
+        self.iterations, self.converged, self.status = int(iterations), bool(converged), str(status)
+        self.count, self.rms, self.initial_rms, self.history = int(count), float(rms), float(initial_rms), list(history)
+
+    def __repr__(self):
+        return "Tracking(status=%s, scale=%.6g, count=%d, rms=%.6g, iterations=%d, converged=%s)" % (
+            self.status, self.scale, self.count, self.rms, self.iterations, self.converged)
 
 
 class TSDFVolume(object):
@@ -302,6 +362,141 @@ class TSDFVolume(object):
                                               step, 0 if skip else NO_SKIP, _lib.ptr(out["depth"]), _lib.ptr(out["mask"]),
                                               _lib.ptr(out["colors"]), _lib.ptr(out["normals"]), _lib.ptr(workspace), need, _lib.stream()),
                        "endo_fusion_render")
+        return out
+
+    def _track_call(self, depth, boundaries, intrinsics, n, height, width):
+        """The checked device inputs of residuals and track, and one call of endo_fusion_track on them for given poses and scales."""
+        depth = _device_tensor(depth, torch.float32, (n, height, width), "depth")
+        boundaries = _device_tensor(boundaries, torch.float32, (n, height, width), "boundaries")
+        intrinsics = _device_tensor(intrinsics, torch.float32, (n, 3, 3), "intrinsics")
+        for name, t in (("depth", depth), ("boundaries", boundaries), ("intrinsics", intrinsics)):
+            if t.device != self.device:
+                raise ValueError("%s lives on %s, the volume on %s" % (name, t.device, self.device))
+        lib = _lib.load()
+        need = int(lib.endo_fusion_track_workspace_bytes(n, height, width))
+        nx, ny, nz = self.dims
+        if need < 0 or nx > 2 ** 24:
+            raise ValueError("%d frames of %d x %d against %d x %d x %d voxels are outside endo_fusion_track's sizes" % (n, height, width, nx, ny, nz))
+        origin = _host_doubles(self.origin)
+        with torch.cuda.device(self.device):
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            meta = torch.empty(n * 8 * TRACK_SUMS + n * 4, dtype=torch.uint8, device=self.device)          # sums, then flags: one read
+        sums, flags = meta[:n * 8 * TRACK_SUMS].view(torch.float64), meta[n * 8 * TRACK_SUMS:].view(torch.int32)
+
+        def call(rotations, translations, scales, min_weight, per_pixel):
+            rotations, translations = _poses(rotations, translations, n, self.device)
+            scales = torch.from_numpy(np.ascontiguousarray(np.asarray(scales, np.float32).reshape(n))).to(self.device)
+            with torch.cuda.device(self.device):
+                maps = None
+                if per_pixel:
+                    maps = {"residual": torch.empty((n, 1, height, width), dtype=torch.float32, device=self.device),
+                            "valid": torch.empty((n, 1, height, width), dtype=torch.float32, device=self.device),
+                            "gradient": torch.empty((n, height, width, 3), dtype=torch.float32, device=self.device)}
+                _lib.check(lib.endo_fusion_track(origin, self.voxel_size, self.truncation, nx, ny, nz, _lib.ptr(self.tsdf),
+                                                 _lib.ptr(self.weight), _lib.ptr(depth), _lib.ptr(boundaries), _lib.ptr(intrinsics),
+                                                 _lib.ptr(rotations), _lib.ptr(translations), _lib.ptr(scales), n, height, width,
+                                                 min_weight, _lib.ptr(sums), _lib.ptr(flags), _lib.ptr(maps["residual"]) if maps else None,
+                                                 _lib.ptr(maps["valid"]) if maps else None, _lib.ptr(maps["gradient"]) if maps else None,
+                                                 _lib.ptr(workspace), need, _lib.stream()), "endo_fusion_track")
+                host = meta.cpu().numpy()          # the call's one read back (it waits for the stream)
+            return (host[:n * 8 * TRACK_SUMS].view(np.float64).reshape(n, TRACK_SUMS).copy(),
+                    [FLAGS[v] for v in host[n * 8 * TRACK_SUMS:].view(np.int32)], maps)
+        return call
+
+    @staticmethod
+    def _track_arguments(depth, scales, min_weight):
+        if not torch.is_tensor(depth) or depth.dim() not in (3, 4):
+            raise ValueError("depth must be an (N, 1, H, W) or (N, H, W) device tensor")
+        n, height, width = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError("min_weight is NaN")
+        if scales is None:
+            scales = np.ones(n, np.float64)
+        else:
+            scales = (scales.detach().cpu().numpy() if torch.is_tensor(scales) else np.asarray(scales)).astype(np.float64).reshape(-1)
+            if scales.shape[0] != n:
+                raise ValueError("scales must hold one value per frame: %d, not %d" % (n, scales.shape[0]))
+        return n, height, width, scales, min_weight
+
+    def residuals(self, depth, boundaries, intrinsics, rotations, translations, scales=None, min_weight=1.0, per_pixel=True):
+        """Each predicted pixel's signed distance to the model (csrc/fusion_track.hip, two launches whatever N is, one read of the
+        sums): the pixel back-projected under its frame's scale and pose, ``x = R (s d ray) + t``, and the trilinear tsdf sampled
+        there, times the truncation.  depth and boundaries (N, 1, H, W) or (N, H, W) fp32 and intrinsics (N, 3, 3) fp32 on the
+        device; rotations (N, 3, 3) and translations (N, 3) as integrate takes them; scales: N per-frame scales or None for ones, as
+        in render.  A pixel is a sample when its boundary is > 0.5, its depth finite and positive and the eight voxels around the
+        point all have weight >= min_weight (render's cell rule).  Returns a dictionary: ``residual`` and ``valid`` (N, 1, H, W) and
+        ``gradient`` (N, H, W, 3), fp32 device tensors, 0 where the pixel is no sample (None with per_pixel=False): the signed
+        distance, positive in free space, 1, and the distance's gradient per unit length in the tracker's frame; per frame ``sums``
+        ((N, 40) numpy fp64, the layout of endo_fusion_track), ``count``, ``rms`` (NaN without a sample) and ``flags`` ("ok" or
+        "bad_scale": a scale that is not finite and positive; such a frame has no sample).  tests/fusion_track_restate.py states them."""
+        n, height, width, scales, min_weight = self._track_arguments(depth, scales, min_weight)
+        call = self._track_call(depth, boundaries, intrinsics, n, height, width)
+        sums, flags, maps = call(rotations, translations, scales, min_weight, bool(per_pixel))
+        out = dict(maps) if maps else {"residual": None, "valid": None, "gradient": None}
+        out.update({"sums": sums, "flags": flags, "count": [int(round(v)) for v in sums[:, 0]], "rms": [_track_rms(row) for row in sums]})
+        return out
+
+    def track(self, depth, boundaries, intrinsics, rotations, translations, scales=None, with_scale=True, iterations=20, tolerance=None,
+              min_weight=1.0, min_count=64, damping=0.0):
+        """Frame-to-model alignment of N frames against the volume: Gauss-Newton on the signed distances of ``residuals`` over a
+        similarity per frame (rotation, translation and, with_scale, the scale: monocular depth is known up to scale), the whole batch
+        in lock-step.  Each iteration is one call without per-pixel outputs, one read of N x 40 doubles and a numpy fp64 solve of
+        ``(JtJ + damping diag(JtJ)) delta = -Jt r``, 7 x 7 or 6 x 6; then ``R <- exp([omega]x) R``, ``t <- t + tau``,
+        ``s <- s exp(sigma)``: the increment acts in the tracker's frame about the camera centre.  A frame stops when
+        ``max(|omega| rho, |tau|, |sigma| rho) <= tolerance``, rho the rms length of its samples' rays (None: 1e-3 voxel_size, two
+        orders above the float32 floor of the per-pixel work and far below what the surface resolves); the others go on.  One more
+        call after the last update gives the count and rms of the returned poses.  Returns a list of N Tracking.  A frame that
+        fails -- "bad_scale", "too_few" (fewer than min_count samples) or "singular" (the system is not positive definite) --
+        keeps its input pose and scale; nothing raises for it."""
+        n, height, width, scales, min_weight = self._track_arguments(depth, scales, min_weight)
+        tolerance = 1.0e-3 * self.voxel_size if tolerance is None else float(tolerance)
+        call = self._track_call(depth, boundaries, intrinsics, n, height, width)
+        rot, tr = _poses(rotations, translations, n, torch.device("cpu"))
+        rot, tr = rot.numpy().copy(), tr.numpy().copy()
+        start = (rot.copy(), tr.copy(), scales.copy())
+        status, steps, converged = ["ok"] * n, [0] * n, [False] * n
+        history, initial = [[] for _ in range(n)], [float("nan")] * n
+        active = list(range(n))
+        for it in range(int(iterations)):
+            if not active:
+                break
+            sums, flags, _ = call(rot, tr, scales, min_weight, False)
+            for f in list(active):
+                rms = _track_rms(sums[f])
+                history[f].append(rms)
+                if it == 0:
+                    initial[f] = rms
+                delta = None
+                if flags[f] != "ok":
+                    status[f] = flags[f]
+                elif sums[f, 0] < min_count:
+                    status[f] = "too_few"
+                else:
+                    delta = gauss_newton_step(sums[f], with_scale, damping)
+                    if delta is None:
+                        status[f] = "singular"
+                if delta is None:          # it stays where it came from
+                    rot[f], tr[f], scales[f] = start[0][f], start[1][f], start[2][f]
+                    active.remove(f)
+                    continue
+                rot[f] = rodrigues(delta[:3]) @ rot[f]
+                tr[f] = tr[f] + delta[3:6]
+                scales[f] = scales[f] * math.exp(delta[6])
+                steps[f] += 1
+                rho = math.sqrt(sums[f, 4] / sums[f, 0])
+                if max(float(np.linalg.norm(delta[:3])) * rho, float(np.linalg.norm(delta[3:6])), abs(float(delta[6])) * rho) <= tolerance:
+                    converged[f] = True
+                    active.remove(f)
+        sums, flags, _ = call(rot, tr, scales, min_weight, False)
+        out = []
+        for f in range(n):
+            if status[f] == "ok" and flags[f] != "ok":
+                status[f] = flags[f]
+            if not history[f]:          # iterations = 0
+                initial[f] = _track_rms(sums[f])
+            out.append(Tracking(rot[f], tr[f], scales[f], steps[f], converged[f], status[f], int(round(sums[f, 0])), _track_rms(sums[f]),
+                                initial[f], history[f]))
         return out
 
     def observed_voxels(self):

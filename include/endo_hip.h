@@ -1222,6 +1222,46 @@ int endo_fusion_render(const double* origin, double voxel_size, double truncatio
                        float min_weight, float step, int options, float* depth, float* mask, uint8_t* colors, float* normals,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A frame tracked against the fused volume (csrc/fusion_track.hip): every pixel of a depth map back-projected under its frame's scale
+ * and pose, the trilinear tsdf sampled there -- the pixel's signed distance to the model -- and the normal equations of one
+ * Gauss-Newton step over a similarity (rotation, translation, log-scale), summed per frame.  The reference has no code for it;
+ * tests/fusion_track_restate.py is the numpy statement: the per-pixel fp32 numbers bit for bit, the fp64 sums up to their order of
+ * addition.  An additive part of ABI 7.  Every fp32 operation below is rounded on its own, in the order written.
+ *
+ * The frame.  R, T, fx, cx, fy, cy, I = 1 / voxel_size as in endo_fusion_render; s = scales[f] or 1 with scales NULL.  A frame whose s
+ *   is not finite and positive has no sample: flag ENDO_FUSION_FRAME_BAD_SCALE, sums 0.  Every other frame: ENDO_FUSION_FRAME_OK.
+ * The pixel (u, v) with depth d, the camera's z.  d_x = (float(u) - cx) / fx, d_y = (float(v) - cy) / fy,
+ *   w_a = (R[a][0] d_x + R[a][1] d_y) + R[a][2], y_a = (s d) w_a, x_a = T_a + y_a;  the cell c_a and fractions r_a of x as of a sample
+ *   of endo_fusion_render.  The pixel is a SAMPLE when boundaries[v][u] > 0.5, d is finite and > 0, 0 <= c_a <= n_a - 2 on every axis
+ *   and all eight voxels of the cell have weight >= min_weight.  Then with (f, G) the value and gradient of endo_fusion_render:
+ *   r = f truncation, n_a = G_a (truncation I): the signed distance, positive in free space, and its gradient per unit length.
+ * The Jacobian of r under x' = (1 + sigma) exp([omega]x) (x - T) + T + tau, the increment in the volume's frame about the camera centre:
+ *   J = (y x n, n, n . y) with (y x n)_0 = y_1 n_2 - y_2 n_1, _1 = y_2 n_0 - y_0 n_2, _2 = y_0 n_1 - y_1 n_0 and
+ *   n . y = (n_0 y_0 + n_1 y_1) + n_2 y_2, seven fp32 numbers; q = (y_0 y_0 + y_1 y_1) + y_2 y_2.
+ * The sums, 40 doubles per frame over its samples, J, r and q converted to fp64 and multiplied and added there:
+ *   [0] the number of samples, [1] sum r r, [2] sum |r|, [3] max |r|, [4] sum q, [5 + i] sum J_i r (i < 7), and from [12] on the upper
+ *   triangle of sum J_i J_j row by row: (0,0) .. (0,6), (1,1) .. (1,6), ... (6,6).  The order of addition is fixed -- a thread's
+ *   pixels in order, lanes, waves and blocks in fixed trees, no atomics -- so the same arguments give the same bytes; it is not part
+ *   of the contract otherwise.
+ *
+ * endo_fusion_track_tile(which): 0, 1: the pixel tile of one block (x, y); 2: the consecutive tiles of a frame a block walks.
+ * endo_fusion_track_workspace_bytes(n, h, w): the workspace (the blocks' partial sums); -1 outside endo_fusion_integrate's sizes.
+ * endo_fusion_track: two launches whatever n is, no host read.  The volume as in endo_fusion_render without its colour planes; depth
+ *   and boundaries [n][h][w] fp32, intrinsics [n][3][3] fp32, rotations [n][3][3] and translations [n][3] fp64, scales [n] fp32 or NULL:
+ *   all on the device.  Outputs, device: sums [n][40] fp64, flags [n] int32, and three that may each be NULL: residual [n][h][w] fp32 = r,
+ *   valid [n][h][w] fp32 = 1, gradient [n][h][w][3] fp32 = n, all 0 where the pixel is no sample.  ENDO_E_BADARG before any device work
+ *   for a NULL or misaligned plane, a NULL input or sums or flags, sizes outside the above (nx > 2^24), a NaN min_weight or a
+ *   workspace that is too small.  The planes are only read.  workspace: SCRATCH.
+ * ------------------------------------------------------------------------------------------- */
+int endo_fusion_track_tile(int which);
+int64_t endo_fusion_track_workspace_bytes(int frames, int height, int width);
+int endo_fusion_track(const double* origin, double voxel_size, double truncation, int nx, int ny, int nz, const float* tsdf,
+                      const float* weight, const float* depth, const float* boundaries, const float* intrinsics,
+                      const double* rotations, const double* translations, const float* scales, int frames, int height, int width,
+                      float min_weight, double* sums, int32_t* flags, float* residual, float* valid, float* gradient, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
