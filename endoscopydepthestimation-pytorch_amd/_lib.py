@@ -185,6 +185,22 @@ for _prefix in ("endo_bf16_", "endo_f16_"):
     for _name, _sig in BACKWARD_BRICKS.items():
         SIGNATURES[_prefix + _name] = _sig
 
+
+# the weight-gradient bricks of the fp32 family (one weight-gradient launch of endo_net_bwd each): endo_wgrad_operands of the header
+class WgradOperands(ctypes.Structure):
+    _fields_ = [("in_", _P), ("in_ns", _L), ("in_cs", ctypes.c_int32), ("in_w", ctypes.c_int32),
+                ("dy", _P), ("dy_ns", _L), ("dy_cs", ctypes.c_int32), ("dy_w", ctypes.c_int32),
+                ("saved", _P), ("gamma", _P), ("beta", _P), ("dy_idx", _P), ("idx_ns", _L), ("gs", _L), ("in_gs", _L),
+                ("prep_x", _P), ("prep_p", _P), ("prep_q", _P), ("prep_bias", _P), ("dw", _P),
+                ("group_n", ctypes.c_int32), ("n", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("cin", ctypes.c_int32), ("cout", ctypes.c_int32)]
+
+
+SIGNATURES["endo_wgrad_brick_scratch_floats"] = (_L, [_I, _I])
+SIGNATURES["endo_wgrad_brick_ok"] = (_I, [_I, _I, ctypes.POINTER(WgradOperands)])
+SIGNATURES["endo_wgrad_brick"] = (_I, [_I, _I, ctypes.POINTER(WgradOperands), _P, _L, _P])
+SIGNATURES["endo_wgrad_brick_f34_batch"] = (_I, [ctypes.POINTER(WgradOperands), _I, _P, _L, _P])
+
 _lib = None
 
 

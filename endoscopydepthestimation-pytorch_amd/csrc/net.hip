@@ -1129,7 +1129,48 @@ static BwdPlan plan_bwd(const Ctx& c) {
     return pl;
 }
 
+// ---- the weight-gradient launches by planned form.  endo_net_bwd and the weight-gradient bricks (endo_wgrad_brick, the end of this file) both go
+// through these four functions: nothing else switches over the forms, so a brick launches what the network launches.  bf16: the network's
+// ENDO_OPT_MFMA_BF16 operand rounding (the bricks are fp32-operand only) ----
 // batch / slice: the F(3x3, 4x4) form leaves its partial sums in scratch slice `slice` and its reduction to the caller's batched launch
+static int launch_dense_wgrad(DenseWgrad form, const WgradParams& p, float* scratch, hipStream_t stream, F34ReduceBatch* batch = nullptr, int slice = 0,
+                              bool bf16 = false) {
+    switch (form) {
+        case DenseWgrad::F34: return launch_wgrad_f34(p, scratch + (batch ? slice : 0) * kF34ScratchFloats, stream, batch);          // Winograd F(3x3, 4x4)
+        case DenseWgrad::NSplit: return launch_wgrad_nsplit(p, scratch, stream, bf16);
+        case DenseWgrad::Taps: return bf16 ? launch_wgrad_taps<12, IN_BNRELU, 1>(p, stream) : launch_wgrad_taps<12, IN_BNRELU>(p, stream);
+        case DenseWgrad::Direct: return launch_wgrad<3, 1, IN_BNRELU, DY_PLAIN>(p, stream);
+    }
+    return ENDO_E_BADARG;
+}
+
+// transition down, 1x1 on the un-routed pooled gradient: the LDS-DMA kernel where whole code dwords allow it (BwdPlan::td_wgrad_dma), else the plain one
+static int launch_td_wgrad(bool dma, const WgradParams& p, hipStream_t stream, bool bf16 = false) {
+    return !dma ? launch_wgrad1x1(p, stream) : bf16 ? launch_wgrad1x1_dma<1>(p, stream) : launch_wgrad1x1_dma<0>(p, stream);
+}
+
+// transition up; p as tu_wgrad_params(.., form == Subpix) fills it (the sub-pixel form walks the low-resolution grid)
+static int launch_tu_wgrad(TuWgrad form, const WgradParams& p, float* scratch, hipStream_t stream) {
+    switch (form) {
+        case TuWgrad::Subpix: return launch_tu_wgrad_subpix(p, scratch, stream);
+        case TuWgrad::Taps: return launch_wgrad_taps<12, IN_UPSAMPLE>(p, stream);
+        case TuWgrad::Direct: return launch_wgrad<3, 1, IN_UPSAMPLE, DY_PLAIN>(p, stream);
+    }
+    return ENDO_E_BADARG;
+}
+
+// first convolution, 3 -> 48 channels: in the F(3x3, 4x4) form the four sets of 12 output channels share one launch (the tap-folded kernel runs a
+// 108-row GEMM with 3 of 16 columns in use, four times: 216 us alone on the chip at the very end of the backward)
+static int launch_first_wgrad(FirstWgrad form, const WgradParams& p, float* scratch, hipStream_t stream) {
+    switch (form) {
+        case FirstWgrad::F34Prep: return launch_wgrad_f34<0, true, true>(p, scratch, stream);
+        case FirstWgrad::F34: return launch_wgrad_f34<0, true>(p, scratch, stream);
+        case FirstWgrad::Taps: return launch_wgrad_taps<12, IN_PLAIN>(p, stream);
+        case FirstWgrad::Direct: return launch_wgrad<3, 3, IN_PLAIN, DY_PLAIN>(p, stream);
+    }
+    return ENDO_E_BADARG;
+}
+
 static int dense_wgrad(const Ctx& c, int b, int j, F34ReduceBatch* batch = nullptr, int slice = 0) {
     const DenseBlock k = dense_block(b);
     const ConvP& cv = k.cv[j];
@@ -1137,13 +1178,7 @@ static int dense_wgrad(const Ctx& c, int b, int j, F34ReduceBatch* batch = nullp
     const WgradParams p = dense_wgrad_params(c, k, j);
     float* scratch = c.gradws + c.net->wg_scratch_off;
     ProfScope prof(kProfWgradDense, c.stream, conv_flops(c.net, k.level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin + cv.cout));
-    switch (c.bwd->wgrad[b * kLayers + j]) {
-        case DenseWgrad::F34: return launch_wgrad_f34(p, scratch + (batch ? slice : 0) * kF34ScratchFloats, c.stream, batch);          // Winograd F(3x3, 4x4)
-        case DenseWgrad::NSplit: return launch_wgrad_nsplit(p, scratch, c.stream, c.bwd->bf16_wgrad);
-        case DenseWgrad::Taps: return c.bwd->bf16_wgrad ? launch_wgrad_taps<12, IN_BNRELU, 1>(p, c.stream) : launch_wgrad_taps<12, IN_BNRELU>(p, c.stream);
-        case DenseWgrad::Direct: return launch_wgrad<3, 1, IN_BNRELU, DY_PLAIN>(p, c.stream);
-    }
-    return ENDO_E_BADARG;
+    return launch_dense_wgrad(c.bwd->wgrad[b * kLayers + j], p, scratch, c.stream, batch, slice, c.bwd->bf16_wgrad);
 }
 
 // dense layer backward: bias grad + deferred-term fold, wgrad, dgrad fused with ReLU/BN backward
@@ -1307,7 +1342,7 @@ static int td_bwd(const Ctx& c, int level) {
         rc = c.fork_wgrad(cw, level);
         if (rc) return rc;
         ProfScope prof(kProfWgradOther, cw.stream, conv_flops(c.net, level, cv.cin, cv.cout, 1), 4.0 * c.nt() * lv.plane * cv.cin);
-        rc = !c.bwd->td_wgrad_dma[level] ? launch_wgrad1x1(p, cw.stream) : c.bwd->bf16_wgrad ? launch_wgrad1x1_dma<1>(p, cw.stream) : launch_wgrad1x1_dma<0>(p, cw.stream);
+        rc = launch_td_wgrad(c.bwd->td_wgrad_dma[level], p, cw.stream, c.bwd->bf16_wgrad);
         if (rc) return rc;
     }
     {
@@ -1336,8 +1371,7 @@ static int tu_bwd(const Ctx& c, int level, int src_level, int src_c0, const Conv
         rc = c.fork_wgrad(cw, level);
         if (rc) return rc;
         ProfScope prof(kProfWgradOther, cw.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cin / 4.0 + cv.cout));
-        rc = form == TuWgrad::Subpix ? launch_tu_wgrad_subpix(p, c.gradws + c.net->wg_scratch_off, cw.stream)
-           : form == TuWgrad::Taps ? launch_wgrad_taps<12, IN_UPSAMPLE>(p, cw.stream) : launch_wgrad<3, 1, IN_UPSAMPLE, DY_PLAIN>(p, cw.stream);
+        rc = launch_tu_wgrad(form, p, c.gradws + c.net->wg_scratch_off, cw.stream);
         if (rc) return rc;
     }
     ProfScope prof(kProfDgradOther, c.stream, conv_flops(c.net, level, cv.cin, cv.cout, 3), 4.0 * c.nt() * lv.plane * (cv.cout + cv.cin / 4.0));
@@ -1636,14 +1670,7 @@ extern "C" int endo_net_bwd(endo_net* net, const float* params, const float* x, 
         rc = c.fork_wgrad(cw, 0);
         if (rc) return rc;
         ProfScope prof(kProfWgradOther, cw.stream, conv_flops(net, 0, 3, kFirst, 3), 4.0 * c.nt() * lv.plane * (3 + kFirst));
-        // 3 -> 48 channels: in the F(3x3, 4x4) form the four sets of 12 output channels share one launch (the tap-folded kernel runs a
-        // 108-row GEMM with 3 of 16 columns in use, four times: 216 us alone on the chip at the very end of the backward)
-        switch (plan.first) {
-            case FirstWgrad::F34Prep: rc = launch_wgrad_f34<0, true, true>(p, gradws + net->wg_scratch_off, cw.stream); break;
-            case FirstWgrad::F34: rc = launch_wgrad_f34<0, true>(p, gradws + net->wg_scratch_off, cw.stream); break;
-            case FirstWgrad::Taps: rc = launch_wgrad_taps<12, IN_PLAIN>(p, cw.stream); break;
-            case FirstWgrad::Direct: rc = launch_wgrad<3, 3, IN_PLAIN, DY_PLAIN>(p, cw.stream); break;
-        }
+        rc = launch_first_wgrad(plan.first, p, gradws + net->wg_scratch_off, cw.stream);
         if (rc) return rc;
     }
     if (bias_parts.table.n > 0) {          // the conv-bias gradients from prep_dy's per-block sums (BiasParts): one launch for the whole pass
@@ -1780,4 +1807,123 @@ extern "C" const char* endo_net_plan_name(int kind, int value) {
     const PlanKind& k = kPlanKinds[kind];
     if (value == -1) return k.name;
     return (k.values && value >= 0 && value < k.count) ? k.values[value] : nullptr;
+}
+
+// ---- WEIGHT-GRADIENT BRICKS of the fp32 family (include/endo_hip.h): one weight-gradient launch of endo_net_bwd on the caller's operands ----
+namespace {
+
+int brick_forms(int kind) { return kind == ENDO_WGRAD_DENSE || kind == ENDO_WGRAD_FIRST ? 4 : kind == ENDO_WGRAD_TD ? 2 : kind == ENDO_WGRAD_TU ? 3 : 0; }
+bool brick_form_ok(int kind, int form) { return form >= 0 && form < brick_forms(kind); }
+
+// the WgradParams the network's fillers (dense_wgrad_params, first_wgrad_params, td_wgrad_params, tu_wgrad_params) would hand the launch
+WgradParams brick_params(int kind, int form, const endo_wgrad_operands& a) {
+    WgradParams p{};
+    p.n = a.n; p.h = a.h; p.w = a.w;
+    p.group_n = a.group_n > 0 ? a.group_n : a.n; p.gs = a.gs; p.in_gs = a.in_gs;
+    p.tiles_x = (a.w + kWgTileX - 1) / kWgTileX;
+    p.tiles_y = (a.h + kWgTileY - 1) / kWgTileY;
+    p.in = a.in; p.in_ns = a.in_ns; p.in_cs = a.in_cs; p.in_w = a.in_w; p.cin = a.cin;
+    p.dy = a.dy; p.dy_ns = a.dy_ns; p.dy_cs = a.dy_cs; p.dy_w = a.dy_w; p.cout = a.cout;
+    p.dw = a.dw;
+    if (kind == ENDO_WGRAD_DENSE || kind == ENDO_WGRAD_TD) { p.saved = a.saved; p.gamma = a.gamma; p.beta = a.beta; }
+    if (kind == ENDO_WGRAD_TD) { p.dy_idx = a.dy_idx; p.idx_ns = a.idx_ns; }
+    if (kind == ENDO_WGRAD_FIRST && static_cast<FirstWgrad>(form) == FirstWgrad::F34Prep) {
+        p.prep_x = a.prep_x; p.prep_p = a.prep_p; p.prep_q = a.prep_q; p.prep_bias = a.prep_bias;
+    }
+    if (kind == ENDO_WGRAD_TU && static_cast<TuWgrad>(form) == TuWgrad::Subpix) { p.h = a.h / 2; p.w = a.w / 2; }          // the low-resolution grid
+    return p;
+}
+
+// sizes, strides and the pointers every form of the kind reads (what no kernel predicate looks at)
+bool brick_operands_ok(int kind, int form, const endo_wgrad_operands& a) {
+    if (!a.in || !a.dy || !a.dw || a.n <= 0 || a.h <= 0 || a.w <= 0 || a.cin <= 0 || a.cout <= 0 || a.group_n < 0) return false;
+    const bool half_in = kind == ENDO_WGRAD_TU, half_dy = kind == ENDO_WGRAD_TD;
+    if ((half_in || half_dy) && (a.h % 2 != 0 || a.w % 2 != 0)) return false;
+    const int64_t in_h = half_in ? a.h / 2 : a.h, in_w = half_in ? a.w / 2 : a.w, dy_h = half_dy ? a.h / 2 : a.h, dy_w = half_dy ? a.w / 2 : a.w;
+    if (a.in_w < in_w || a.in_cs < in_h * a.in_w || a.in_ns < static_cast<int64_t>(a.cin) * a.in_cs) return false;
+    if (a.dy_w < dy_w || a.dy_cs < dy_h * a.dy_w || a.dy_ns < static_cast<int64_t>(a.cout) * a.dy_cs) return false;
+    const int group_n = a.group_n > 0 ? a.group_n : a.n;
+    if (a.n % group_n != 0 || a.n / group_n > kMaxGroups) return false;
+    if (a.n / group_n > 1 && (a.gs < group_n * a.dy_ns || a.in_gs < group_n * a.in_ns)) return false;
+    if (kind == ENDO_WGRAD_DENSE && a.cout != kGrowth) return false;
+    if (kind == ENDO_WGRAD_FIRST && (a.cin > 16 || a.cout % 12 != 0 || a.cout / 12 > 16)) return false;
+    if ((kind == ENDO_WGRAD_DENSE || kind == ENDO_WGRAD_TD) && (!a.saved || !a.gamma || !a.beta)) return false;
+    if (kind == ENDO_WGRAD_TD && (!a.dy_idx || a.idx_ns < static_cast<int64_t>(a.cout) * a.dy_cs)) return false;
+    if (kind == ENDO_WGRAD_FIRST && static_cast<FirstWgrad>(form) == FirstWgrad::F34Prep && (!a.prep_x || !a.prep_p || !a.prep_q)) return false;
+    return true;
+}
+
+// the form's own predicate, as plan_bwd asks it, without the tile / chunk minimum (a brick launches the form at any size)
+bool brick_predicate(int kind, int form, const WgradParams& p) {
+    switch (kind) {
+        case ENDO_WGRAD_DENSE:
+            switch (static_cast<DenseWgrad>(form)) {
+                case DenseWgrad::F34: return wgrad_f34_ok(p, 0);
+                case DenseWgrad::NSplit: return wgrad_nsplit_shape_ok(p);
+                case DenseWgrad::Taps: return wgrad_taps_ok(p);
+                case DenseWgrad::Direct: return true;
+            }
+            return false;
+        case ENDO_WGRAD_FIRST:
+            switch (static_cast<FirstWgrad>(form)) {
+                case FirstWgrad::F34Prep:
+                case FirstWgrad::F34: return wgrad_f34_raw_ok(p, 0);
+                case FirstWgrad::Taps: return wgrad_taps_ok(p);
+                case FirstWgrad::Direct: return true;
+            }
+            return false;
+        case ENDO_WGRAD_TD: return form == 0 || wgrad1x1_dma_ok(p);
+        case ENDO_WGRAD_TU:
+            switch (static_cast<TuWgrad>(form)) {
+                case TuWgrad::Subpix: return tu_wgrad_subpix_ok(p);
+                case TuWgrad::Taps: return wgrad_taps_ok(p, true);
+                case TuWgrad::Direct: return true;
+            }
+            return false;
+    }
+    return false;
+}
+
+}  // namespace
+
+extern "C" int64_t endo_wgrad_brick_scratch_floats(int kind, int form) {
+    if (!brick_form_ok(kind, form)) return ENDO_E_BADARG;
+    if (kind == ENDO_WGRAD_DENSE) return static_cast<DenseWgrad>(form) == DenseWgrad::F34 ? kF34ScratchFloats : static_cast<DenseWgrad>(form) == DenseWgrad::NSplit ? kNsScratchFloats : 0;
+    if (kind == ENDO_WGRAD_FIRST) return static_cast<FirstWgrad>(form) == FirstWgrad::F34Prep || static_cast<FirstWgrad>(form) == FirstWgrad::F34 ? kF34ScratchFloats : 0;
+    if (kind == ENDO_WGRAD_TU) return static_cast<TuWgrad>(form) == TuWgrad::Subpix ? kSpScratchFloats : 0;
+    return 0;
+}
+
+extern "C" int endo_wgrad_brick_ok(int kind, int form, const endo_wgrad_operands* a) {
+    if (!a || !brick_form_ok(kind, form) || !brick_operands_ok(kind, form, *a)) return 0;
+    return brick_predicate(kind, form, brick_params(kind, form, *a)) ? 1 : 0;
+}
+
+extern "C" int endo_wgrad_brick(int kind, int form, const endo_wgrad_operands* a, float* scratch, int64_t scratch_cap, void* stream) {
+    if (!endo_wgrad_brick_ok(kind, form, a)) return ENDO_E_BADARG;
+    const int64_t need = endo_wgrad_brick_scratch_floats(kind, form);
+    if (need > 0 && (!scratch || scratch_cap < need)) return ENDO_E_BADARG;
+    const WgradParams p = brick_params(kind, form, *a);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (kind) {
+        case ENDO_WGRAD_DENSE: return launch_dense_wgrad(static_cast<DenseWgrad>(form), p, scratch, s);
+        case ENDO_WGRAD_FIRST: return launch_first_wgrad(static_cast<FirstWgrad>(form), p, scratch, s);
+        case ENDO_WGRAD_TD: return launch_td_wgrad(form != 0, p, s);
+        case ENDO_WGRAD_TU: return launch_tu_wgrad(static_cast<TuWgrad>(form), p, scratch, s);
+    }
+    return ENDO_E_BADARG;
+}
+
+extern "C" int endo_wgrad_brick_f34_batch(const endo_wgrad_operands* layers, int count, float* scratch, int64_t scratch_cap, void* stream) {
+    const int f34 = static_cast<int>(DenseWgrad::F34);
+    if (!layers || count < 1 || count > 4 || !scratch || scratch_cap < count * kF34ScratchFloats) return ENDO_E_BADARG;
+    for (int k = 0; k < count; ++k)
+        if (!endo_wgrad_brick_ok(ENDO_WGRAD_DENSE, f34, layers + k)) return ENDO_E_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    F34ReduceBatch red{};
+    for (int k = 0; k < count; ++k) {
+        const int rc = launch_dense_wgrad(DenseWgrad::F34, brick_params(ENDO_WGRAD_DENSE, f34, layers[k]), scratch, s, &red, k);
+        if (rc) return rc;
+    }
+    return launch_wgrad_f34_reduce_batch(red, s);
 }

@@ -298,13 +298,17 @@ constexpr int kNsMinChunks = 2048;           // launches with fewer row chunks g
 constexpr int kNsMaxBlocks = 1024;
 constexpr int64_t kNsScratchFloats = static_cast<int64_t>(kNsMaxBlocks) * 12 * kNsMG * 256;   // blocks * groups <= 1024 * 12
 
-// fill: the row chunks count `fill` times over (ENDO_OPT_CHIP_DIVISOR: the chip as 1 / fill of its compute units)
-inline bool wgrad_nsplit_ok(const WgradParams& p, long fill = 1) {
+// what the kernel itself needs (16-byte loads of both operands, 12 gradient maps), whatever the launch's size
+inline bool wgrad_nsplit_shape_ok(const WgradParams& p) {
     const bool aligned = (p.w % 4 == 0) && (p.dy_w % 4 == 0) && (p.dy_cs % 4 == 0) && (p.dy_ns % 4 == 0) && (p.in_w % 4 == 0) &&
                          (p.in_cs % 4 == 0) && (p.in_ns % 4 == 0) && (reinterpret_cast<uintptr_t>(p.dy) % 16 == 0) &&
                          (reinterpret_cast<uintptr_t>(p.in) % 16 == 0);
+    return aligned && p.cout == 12;
+}
+// fill: the row chunks count `fill` times over (ENDO_OPT_CHIP_DIVISOR: the chip as 1 / fill of its compute units)
+inline bool wgrad_nsplit_ok(const WgradParams& p, long fill = 1) {
     const long chunks = static_cast<long>((p.w + kNsSeg - 1) / kNsSeg) * p.h * p.n;
-    return aligned && p.cout == 12 && chunks * fill >= kNsMinChunks;
+    return wgrad_nsplit_shape_ok(p) && chunks * fill >= kNsMinChunks;
 }
 
 template <int NG, int EXP = 0, int BF = 0>

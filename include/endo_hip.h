@@ -592,6 +592,72 @@ int endo_net_plan_query(const endo_net* net, int pass, int training, const float
 const char* endo_net_plan_name(int kind, int value);
 
 /* ---------------------------------------------------------------------------------------------
+ * WEIGHT-GRADIENT BRICKS of the fp32 family: each call is ONE weight-gradient launch of endo_net_bwd -- the network's own parameter
+ * struct (WgradParams), launcher and template arguments, reached through the very function endo_net_bwd switches over the forms
+ * in (csrc/net.hip: launch_dense_wgrad / launch_first_wgrad / launch_td_wgrad / launch_tu_wgrad) -- so that a test can hold a single
+ * kernel to fp64 on operands of its own.  fp32 operands only (the ENDO_OPT_MFMA_BF16 forms stay with the network).  Additive: the
+ * version stays 7.  Not covered by a brick: prep_dy_kernel, the bn_bwd_finalize kernels, final_bwd_weight_kernel.
+ *
+ *   kind  ENDO_WGRAD_DENSE  3x3, a = relu(bn(x)), 12 output channels     form: an enumerator of ENDO_PLAN_DENSE_WGRAD (F34 NSplit Taps Direct)
+ *         ENDO_WGRAD_FIRST  3x3, a = x, cin <= 16, cout % 12 == 0        form: of ENDO_PLAN_FIRST_WGRAD (F34Prep F34 Taps Direct)
+ *         ENDO_WGRAD_TD     1x1, a = relu(bn(x)), G un-routed            form: of ENDO_PLAN_TD_WGRAD (Plain Dma)
+ *         ENDO_WGRAD_TU     3x3, a = nearest x2 of x                     form: of ENDO_PLAN_TU_WGRAD (Subpix Taps Direct)
+ *
+ * dw[co][ci][ky][kx] += sum over samples and pixels p of G[co][p] * a[ci][p + (ky - 1, kx - 1)] (a = 0 outside the image; 1x1: no
+ * taps).  dw is fp32 [cout][cin][ks][ks], ACCUMULATED into; nothing outside it (and `scratch`, and prep_bias) is written.
+ * Operands are planar fp32 with explicit strides, as the network holds them: sample s belongs to group s / group_n (group_n 0 or n:
+ * one group; n a multiple of group_n, at most 4 groups) and is number nl = s % group_n in it;
+ *   in      channel c of sample s starts at in + group * in_gs + nl * in_ns + c * in_cs: rows of in_w floats on the h x w grid (TU:
+ *           the (h / 2) x (w / 2) grid).  The caller owns cin * in_cs floats from every sample's start (the F34 and Dma forms
+ *           read them through a buffer descriptor of that extent and mask what lies outside the image; values there must be finite).
+ *   dy      the prepared gradient G, channel co at dy + group * gs + nl * dy_ns + co * dy_cs, rows of dy_w floats on the h x w grid
+ *           (TD: the pooled (h / 2) x (w / 2) grid); cout * dy_cs floats from every sample's start.
+ *   saved / gamma / beta   DENSE and TD: a = relu(fma(x, sc, sh)), sc = gamma[c] * saved[2 c + 1], sh = fma(-saved[2 c], sc, beta[c]);
+ *           group g reads saved + g * gs.  Ignored (may be null) for FIRST and TU.
+ *   dy_idx  TD: bytes laid out as dy's floats (channel stride dy_cs BYTES, sample stride idx_ns, group stride 4 * gs bytes): the
+ *           window position 2 * (row & 1) + (col & 1) that receives the pooled value.  h and w even.
+ *   prep_x / prep_p / prep_q / prep_bias   FIRST, F34Prep only: dy holds the raw gradient d and the kernel forms G = d + P x + Q
+ *           (prep_x laid out as dy; P, Q per output channel, group g at + g * gs) and adds sum G into prep_bias[cout] (may be null).
+ *   scratch at least endo_wgrad_brick_scratch_floats(kind, form) floats (contents on entry ignored; 0: may be null).
+ * endo_wgrad_brick_ok: 1 if the form accepts these operands, else 0 -- the form's own predicate of the plan (alignment of pointers
+ *   and strides, channel counts, descriptor range) WITHOUT the tile / chunk minimum that makes the plan prefer another form at small
+ *   sizes.  Needs no device and dereferences nothing.
+ * endo_wgrad_brick: asynchronous on `stream`.  ENDO_E_BADARG before any device work for null pointers, sizes <= 0, strides
+ *   shorter than what they span, scratch_cap below the query, an unknown (kind, form) or one whose endo_wgrad_brick_ok is 0.
+ * endo_wgrad_brick_f34_batch: `count` (1..4) DENSE F34 launches, layer k into scratch slice k (scratch_cap >= count *
+ *   endo_wgrad_brick_scratch_floats(DENSE, F34)), then ONE batched reduction -- what a fused dense block does.
+ * ------------------------------------------------------------------------------------------- */
+#define ENDO_WGRAD_DENSE 0
+#define ENDO_WGRAD_FIRST 1
+#define ENDO_WGRAD_TD 2
+#define ENDO_WGRAD_TU 3
+typedef struct endo_wgrad_operands {
+    const float* in;
+    int64_t in_ns;
+    int32_t in_cs, in_w;
+    const float* dy;
+    int64_t dy_ns;
+    int32_t dy_cs, dy_w;
+    const float* saved;
+    const float* gamma;
+    const float* beta;
+    const uint8_t* dy_idx;
+    int64_t idx_ns;
+    int64_t gs, in_gs;
+    const float* prep_x;
+    const float* prep_p;
+    const float* prep_q;
+    float* prep_bias;
+    float* dw;
+    int32_t group_n;
+    int32_t n, h, w, cin, cout;
+} endo_wgrad_operands;
+int64_t endo_wgrad_brick_scratch_floats(int kind, int form);
+int endo_wgrad_brick_ok(int kind, int form, const endo_wgrad_operands* a);
+int endo_wgrad_brick(int kind, int form, const endo_wgrad_operands* a, float* scratch, int64_t scratch_cap, void* stream);
+int endo_wgrad_brick_f34_batch(const endo_wgrad_operands* layers, int count, float* scratch, int64_t scratch_cap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * clip_grad_norm_(params, max_norm) + SGD(momentum) -- reference train.py:327-328, 202
  * grads are scaled in place by grad_scale (1/world after the all-reduce) and then by the clip
  * coefficient min(1, max_norm / (norm + 1e-6)); momentum buf = mu * buf + g; p -= lr * buf.
