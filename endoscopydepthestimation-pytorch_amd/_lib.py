@@ -168,6 +168,9 @@ SIGNATURES = {
     "endo_fusion_track_tile": (_I, [_I]),
     "endo_fusion_track_workspace_bytes": (_L, [_I, _I, _I]),
     "endo_fusion_track": (_I, [_P, ctypes.c_double, ctypes.c_double, _I, _I, _I] + [_P] * 8 + [_I, _I, _I, _F] + [_P] * 6 + [_L, _P]),
+    "endo_mesh_render_tile": (_I, [_I]),
+    "endo_mesh_render_workspace_bytes": (_L, [_I, _I, _I, _L]),
+    "endo_mesh_render": (_I, [_P, _L, _L, _P, _L] + [_P] * 5 + [_I, _I, _I, _I] + [_P] * 8 + [_L, _P]),
 }
 
 # the backward bricks of the 16-bit-storage family (one launch of endo_net16_bwd each), over bf16 and over half

@@ -33,6 +33,10 @@ run_fusion_phase makes one model of the sequence before that step: the posed out
 fusion.TSDFVolume around the posed clouds' bounding box (csrc/fusion.hip), the surface written as ``fused_surface.ply`` and, with a
 target, registered once.  With refine=K the frames are first tracked against that volume (csrc/fusion_track.hip) and fused again
 under the refined poses and scales, K times.
+
+model_depth_errors / run_model_depth_phase measure the predictions against a surface that does not come from them: a mesh.TriangleMesh
+(the CT model) drawn from each frame's camera (csrc/mesh_render.hip), the prediction scaled to that depth over the pixels the model
+covers and the reference's AbsRel and sigma 1, 2, 3 there -- ``model_depth_errors.csv``.
 """
 
 import os
@@ -42,7 +46,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, display, fusion, losses, models, registration, utils
+from . import _lib, display, fusion, losses, mesh as mesh_module, models, registration, utils
 from .train_step import mask_mul
 
 
@@ -723,3 +727,153 @@ def run_fusion_phase(model, frames, translation_dict, rotation_dict, out_dir, vo
         if not boxes:          # no frame took part: the table has its header alone
             _write_consistency(torch.cuda.Event(), os.path.join(out_dir, "fused_consistency.csv"), [], [torch.zeros((0, 4))], [torch.zeros(0)], consistency)
     return result
+
+
+MODEL_DEPTH_COLUMNS = ("name", "pixels", "scale", "abs_rel", "sigma_1", "sigma_2", "sigma_3")
+
+
+def _model_poses(rotations, translations, transforms, n):
+    """Each frame's camera in the model's frame: with the tracker-to-model similarity (sigma, Q, tau) of the frame, the rotation Q R_f
+    and the centre sigma Q t_f + tau, host fp64.  transforms: one start (_initial_transform) for all frames or a list of N."""
+    rot, tr = _poses_f64(rotations, translations, n, torch.device("cpu"))
+    rot, tr = rot.numpy(), tr.numpy()
+    if not (isinstance(transforms, list) and len(transforms) == n and not np.isscalar(transforms[0])):          # ([scale, R, t] is one)
+        transforms = [transforms] * n
+    out_rot, out_tr = np.empty((n, 3, 3)), np.empty((n, 3))
+    for f, transform in enumerate(transforms):
+        sigma, q, tau = _initial_transform(transform)
+        out_rot[f] = np.asarray(q, np.float64) @ rot[f]
+        out_tr[f] = float(sigma) * (np.asarray(q, np.float64) @ tr[f]) + np.asarray(tau, np.float64)
+    return out_rot, out_tr
+
+
+def model_depth_errors(predictions, boundaries, intrinsics, rotations, translations, mesh, transform=None, cull=None):
+    """Predicted depth against the depth of a model's surface, per frame.  predictions and boundaries (N, 1, H, W) and intrinsics
+    (N, 3, 3), fp32 on the device; rotations (N, 3, 3) and translations (N, 3): each frame's pose in the tracker's frame
+    (reader.read_initial_pose_file); mesh: a mesh.TriangleMesh in the model's frame; transform: the tracker-to-model similarity
+    (_initial_transform: None, a registration.Registration, a 4 x 4 matrix or (scale, rotation, translation)), or a list of N of
+    them, one per frame.  The camera of frame f stands in the model's frame with rotation Q R_f at sigma Q t_f + tau -- no scale of the
+    prediction enters, which is why the scale can be taken from the render afterwards.  The mesh is rendered from there at scale 1
+    (mesh.render with the frame's boundaries and ``cull``), so its depth is in the model's units; each prediction is scaled to it over
+    the rendered mask as the reference scales to sparse depth (models.DepthScalingLayer), and losses.depth_metrics compares the two.
+    Returns the render's dictionary (depth, mask, normals, colors, triangle, barycentric, flags) plus ``scaled`` (N, 1, H, W), the
+    scaled predictions, ``metrics`` (N, 4) fp32 [abs rel, sigma 1, 2, 3] (NaN for a frame the model does not cover), ``pixels`` (N,)
+    fp32, the covered pixels, and ``scale`` (N,) fp64, the factor each prediction was multiplied by (NaN likewise): device tensors."""
+    if not isinstance(mesh, mesh_module.TriangleMesh):
+        raise ValueError("mesh must be a mesh.TriangleMesh")
+    if not torch.is_tensor(predictions) or predictions.dim() != 4 or predictions.shape[1] != 1:
+        raise ValueError("predictions must be an (N, 1, H, W) device tensor")
+    n, _, height, width = (int(v) for v in predictions.shape)
+    predictions = _device_f32(predictions, (n, 1, height, width), "predictions")
+    boundaries = _device_f32(boundaries, (n, 1, height, width), "boundaries")
+    intrinsics = _device_f32(intrinsics, (n, 3, 3), "intrinsics")
+    model_rot, model_tr = _model_poses(rotations, translations, transform, n)
+    with torch.no_grad(), torch.cuda.device(predictions.device):
+        seen = mesh.render(intrinsics, model_rot, model_tr, height, width, boundaries=boundaries, cull=cull)
+        scaled, _ = models.DepthScalingLayer()([predictions, seen["depth"], seen["mask"]])
+        metrics = losses.depth_metrics(scaled, seen["depth"], seen["mask"])
+        mask = seen["mask"].to(torch.float64)
+        scale = (scaled.to(torch.float64) * mask).sum(dim=(1, 2, 3)) / (predictions.to(torch.float64) * mask).sum(dim=(1, 2, 3))
+        pixels = seen["mask"].sum(dim=(1, 2, 3))
+    out = dict(seen)
+    out.update({"scaled": scaled, "metrics": metrics, "pixels": pixels, "scale": scale})
+    return out
+
+
+def _cloud_start(start, translation, model_scale, z_range):
+    """Where ICP starts for one frame's posed cloud.  The cloud is ``R (s d ray) + t`` with the posed output's own
+    s = 20 / (z_max - z_min), not the tracker's metric: it is the frame's surface scaled about the camera centre t by an unknown lambda.
+    The render from ``start`` = (sigma, Q, tau) tells lambda: ``model_scale`` times the prediction is the model's depth there, so
+    lambda = s sigma / model_scale, and the start is x -> sigma Q ((x - t) / lambda + t) + tau: scale model_scale / s, rotation Q,
+    translation tau + (sigma - model_scale / s) Q t."""
+    sigma, q, tau = start
+    own = 20.0 / (float(z_range[1]) - float(z_range[0]))
+    scale = float(model_scale) / own
+    return scale, q, np.asarray(tau, np.float64) + (float(sigma) - scale) * (np.asarray(q, np.float64) @ np.asarray(translation, np.float64).reshape(3))
+
+
+def _write_model_depth_images(ready, names, left, right, out_dir):
+    ready.synchronize()
+    for f, name in enumerate(names):
+        utils.write_png(os.path.join(out_dir, "model_depth_{}.png".format(name)), np.concatenate([left[f].numpy(), right[f].numpy()], axis=1))
+
+
+def _depth_images(depth, boundaries):
+    """utils.display_depth_map's colours for a batch of (N, 1, H, W) maps: endo_evaluate_posed's depth images, (N, H, W, 3) B, G, R."""
+    n, _, height, width = (int(v) for v in depth.shape)
+    dev = depth.device
+    zeros = torch.zeros((n, 3, height, width), dtype=torch.float32, device=dev)
+    k = torch.eye(3, dtype=torch.float32, device=dev).reshape(1, 3, 3).repeat(n, 1, 1)
+    return posed_outputs_from_predictions(zeros, boundaries, depth, k, np.stack([np.eye(3)] * n), np.zeros((n, 3)))["depth_images"]
+
+
+def run_model_depth_phase(model, frames, translation_dict, rotation_dict, mesh, out_dir, initial=None, refine=False, write_images=True,
+                          writers=4, **register_kwargs):
+    """Dense depth errors of a sequence against a model: every batch of ``frames`` (a dataset.TestFrames) through the network in eval
+    mode on ``boundaries * colors``, as run_registration_phase runs it, then model_depth_errors with the poses
+    ``translation_dict[name]`` / ``rotation_dict[name]`` and ``initial``, the tracker-to-model similarity (_initial_transform).
+    refine=True: each frame's posed cloud (posed_outputs_from_predictions) is first registered to ``mesh.target()`` with
+    registration.register(**register_kwargs) and the frame uses its own similarity.  The cloud has the posed output's own scale about
+    its camera centre, so its start is ``initial`` with that scale taken out by a first render from ``initial`` (_cloud_start).  A
+    frame that fails -- no kept pixels, equal kept depths, no pixel the model covers from ``initial`` or matches that do not
+    determine a similarity -- falls back to ``initial`` and is named in ``failed``.
+    Writes ``model_depth_errors.csv`` in ``out_dir``: one line per frame of MODEL_DEPTH_COLUMNS -- the pixels the model covers, the
+    factor the prediction was scaled by, AbsRel and sigma 1, 2, 3 of the scaled prediction against the model's depth there (NaN
+    without such a pixel); and with write_images ``model_depth_<name>.png``: prediction | rendered depth, each in
+    utils.display_depth_map's colours over its own range, on run_test_phase's writer pool.  A frame whose name is missing from either
+    dictionary raises KeyError before anything runs.
+    Returns a dictionary: frames (their number), failed (names; empty without refine), rows (the table's rows), covered (the frames
+    with at least one covered pixel) and mean_metrics ((4,) float64 over those frames; NaN without one)."""
+    names_ahead = getattr(frames, "image_file_names", None)
+    if names_ahead is not None:
+        for name in names_ahead:
+            key = os.path.basename(str(name))[-12:-4]
+            translation_dict[key], rotation_dict[key]          # KeyError before anything runs
+    if not isinstance(mesh, mesh_module.TriangleMesh):
+        raise ValueError("mesh must be a mesh.TriangleMesh")
+    start = _initial_transform(initial)
+    target = mesh.target() if refine else None
+    out_dir = str(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    count, failed, all_names, collected = 0, [], [], []
+    with _WriterPool(writers) as pool:
+        for batch in frames:
+            names = list(batch["names"])
+            rotations = [rotation_dict[name] for name in names]
+            translations = [translation_dict[name] for name in names]
+            masked, boundaries, pred, intrinsics = _masked_forward(model, batch, "run_model_depth_phase")
+            transforms = [start] * len(names)
+            if refine:
+                posed = posed_outputs_from_predictions(masked, boundaries, pred, intrinsics, rotations, translations,
+                                                       is_hsv=getattr(frames, "is_hsv", False))
+                offsets, ranges = posed["offsets"], posed["ranges"]
+                first = model_depth_errors(pred, boundaries, intrinsics, rotations, translations, mesh, start)["scale"].cpu().numpy()
+                for f, name in enumerate(names):
+                    fit = None
+                    if ranges[f, 0] < ranges[f, 1] and np.isfinite(first[f]) and first[f] > 0.0:
+                        try:
+                            fit = registration.register(posed["points"][offsets[f]:offsets[f + 1]], target,
+                                                        *_cloud_start(start, translations[f], first[f], ranges[f]), **register_kwargs)
+                        except ValueError:
+                            fit = None
+                    if fit is None:
+                        failed.append(name)
+                    else:
+                        transforms[f] = (fit.scale, fit.rotation, fit.translation)
+            out = model_depth_errors(pred, boundaries, intrinsics, rotations, translations, mesh, transforms)
+            count += len(names)
+            all_names += names
+            collected.append(torch.cat([out["pixels"].to(torch.float64)[:, None], out["scale"][:, None], out["metrics"].to(torch.float64)], dim=1))
+            if write_images:
+                left = _depth_images(pred, boundaries).to("cpu", non_blocking=True)
+                right = _depth_images(out["depth"], boundaries).to("cpu", non_blocking=True)
+                pool.submit(_write_model_depth_images, names, left, right, out_dir)
+    table = torch.cat(collected, dim=0).cpu().numpy() if collected else np.zeros((0, 6))          # the phase's one read of the measures
+    rows = [(name, int(row[0])) + tuple(float(v) for v in row[1:]) for name, row in zip(all_names, table)]
+    with open(os.path.join(out_dir, "model_depth_errors.csv"), "w") as f:
+        f.write(",".join(MODEL_DEPTH_COLUMNS) + "\n")
+        for row in rows:
+            f.write(",".join([row[0], str(row[1])] + [repr(v) for v in row[2:]]) + "\n")
+    covered = table[:, 0] > 0
+    return {"frames": count, "failed": failed, "rows": rows, "covered": int(covered.sum()),
+            "mean_metrics": table[covered, 2:].mean(axis=0) if covered.any() else np.full(4, np.nan)}

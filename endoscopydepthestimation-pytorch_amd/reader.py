@@ -125,6 +125,106 @@ def read_point_cloud(path):
     return points
 
 
+def read_mesh(path):
+    """A triangle mesh from a PLY file, ASCII or binary_little_endian: ``(vertices, faces)``, (V, 3) float32 rows of x, y, z -- (V, 6)
+    with r, g, b when the vertices have red, green and blue -- and (T, 3) int32.  Vertex properties may come in any order; normals and
+    whatever else they carry are ignored.  The face element's first list property (``uchar`` or ``int`` counts, int or uint indices)
+    is the corners: a polygon of more than 3 is cut into a fan about its first corner, one of fewer than 3 is dropped.  What
+    utils.write_mesh writes in both encodings reads back exactly; a file without a face element gives T = 0.  Elements other than
+    ``vertex`` and ``face`` are skipped where their size is known (no list properties in binary files)."""
+    with open(str(path), "rb") as fp:
+        raw = fp.read()
+    marker = raw.find(b"end_header")
+    if not raw.startswith(b"ply") or marker < 0:
+        raise ValueError("%s is not a PLY file" % path)
+    at = raw.index(b"\n", marker) + 1
+    encoding, elements = None, []          # elements: [name, count, [(kind, type) or ("list", count type, index type), name]]
+    for line in raw[:marker].decode("ascii").splitlines():
+        words = line.split()
+        if not words:
+            continue
+        if words[0] == "format":
+            encoding = words[1]
+        elif words[0] == "element":
+            elements.append([words[1], int(words[2]), []])
+        elif words[0] == "property" and elements:
+            if words[1] == "list":
+                elements[-1][2].append((("list", _PLY_TYPES[words[2]], _PLY_TYPES[words[3]]), words[4]))
+            else:
+                elements[-1][2].append((("scalar", _PLY_TYPES[words[1]]), words[2]))
+    if encoding not in ("ascii", "binary_little_endian"):
+        raise ValueError("%s: PLY format %r is not supported (ascii or binary_little_endian)" % (path, encoding))
+    tokens, token_at = (raw[at:].split(), 0) if encoding == "ascii" else (None, 0)
+    vertices, faces = np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+    for name, count, props in elements:
+        scalar_only = all(kind[0] == "scalar" for kind, _ in props)
+        names = [prop for _, prop in props]
+        if name == "vertex":
+            if not scalar_only or not all(axis in names for axis in "xyz"):
+                raise ValueError("%s: the vertex element needs scalar x, y and z" % path)
+            wanted = ["x", "y", "z"] + (["red", "green", "blue"] if all(c in names for c in ("red", "green", "blue")) else [])
+            if encoding == "ascii":
+                table = np.array(tokens[token_at:token_at + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                token_at += count * len(props)
+                vertices = np.stack([table[:, names.index(w)] for w in wanted], axis=1).astype(np.float32) if count else np.zeros((0, len(wanted)), np.float32)
+            else:
+                record = np.dtype([(prop, "<" + kind[1] if kind[1] not in "bB" else kind[1]) for kind, prop in props])
+                table = np.frombuffer(raw, dtype=record, count=count, offset=at)
+                at += count * record.itemsize
+                vertices = np.stack([table[w].astype(np.float32) for w in wanted], axis=1) if count else np.zeros((0, len(wanted)), np.float32)
+        elif name == "face":
+            lists = [i for i, (kind, _) in enumerate(props) if kind[0] == "list"]
+            if not lists:
+                raise ValueError("%s: the face element has no list property" % path)
+            out = []
+            if len(props) == 1 and count:          # the common file, triangles only: one table, no loop
+                kind = props[0][0]
+                triangles = None
+                if encoding == "ascii":
+                    table = np.array(tokens[token_at:token_at + 4 * count], dtype=np.int64)
+                    if table.size == 4 * count and (table[0::4] == 3).all():
+                        triangles, token_at = table.reshape(count, 4)[:, 1:], token_at + 4 * count
+                else:
+                    record = np.dtype([("n", kind[1] if kind[1] in "bB" else "<" + kind[1]), ("i", "<" + kind[2], (3,))])
+                    if at + count * record.itemsize <= len(raw):
+                        table = np.frombuffer(raw, dtype=record, count=count, offset=at)
+                        if (table["n"] == 3).all():
+                            triangles, at = table["i"].astype(np.int64), at + count * record.itemsize
+                if triangles is not None:
+                    out, count = triangles, 0
+            for _ in range(count):
+                for i, (kind, _) in enumerate(props):
+                    if kind[0] == "scalar":
+                        if encoding == "ascii":
+                            token_at += 1
+                        else:
+                            at += struct.calcsize("<" + kind[1])
+                        continue
+                    if encoding == "ascii":
+                        corners = int(tokens[token_at])
+                        index = [int(v) for v in tokens[token_at + 1:token_at + 1 + corners]]
+                        token_at += 1 + corners
+                    else:
+                        corners = struct.unpack_from("<" + kind[1], raw, at)[0]
+                        at += struct.calcsize("<" + kind[1])
+                        index = struct.unpack_from("<%d%s" % (corners, kind[2]), raw, at)
+                        at += corners * struct.calcsize("<" + kind[2])
+                    if i == lists[0]:
+                        out += [(index[0], index[j], index[j + 1]) for j in range(1, corners - 1)]
+            faces = np.asarray(out, np.int64).reshape(-1, 3)
+            if faces.size and (faces.min() < -2 ** 31 or faces.max() > 2 ** 31 - 1):
+                raise ValueError("%s: a face index does not fit int32" % path)
+            faces = faces.astype(np.int32)
+        else:
+            if encoding == "ascii" and scalar_only:
+                token_at += count * len(props)
+            elif scalar_only:
+                at += count * sum(struct.calcsize("<" + kind[1]) for kind, _ in props)
+            elif count:
+                raise ValueError("%s: cannot skip element %r with list properties" % (path, name))
+    return vertices, faces
+
+
 def read_view_indexes_per_point(prefix_seq, visible_view_indexes, point_cloud_count):
     """(points, views) 0/1 float64 matrix: a negative line starts the next point  [utils.py:214-224]"""
     column = {}

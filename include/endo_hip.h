@@ -1328,6 +1328,71 @@ int endo_fusion_track(const double* origin, double voxel_size, double truncation
                       float min_weight, double* sums, int32_t* flags, float* residual, float* valid, float* gradient, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A triangle mesh seen from a pose (csrc/mesh_render.hip): the ray through every pixel centre against the triangles, the nearest hit
+ * kept -- what the CT model looks like from a frame's camera, the dense depth a prediction is measured against.  The reference has no
+ * code for it (its README, step 4, leaves the comparison with the CT model to another tool); tests/mesh_render_restate.py is the numpy
+ * float32 statement, matched bit for bit.  An additive part of ABI 7.  Every fp32 operation below is rounded on its own, in the order
+ * written.
+ *
+ * The mesh.  vertices: fp32 rows, `vertex_stride` floats apart: x, y, z and, with a stride >= 6, r, g, b in columns 3, 4, 5
+ *   (endo_fusion_extract's rows); V = vertex_count <= 2^31 - 1.  faces: T x 3 int32, T = triangles <= 2^31 - 1.  A face with an index
+ *   outside 0 .. V - 1 is never hit and none of its vertices is read.  Both on the device; V = 0 and T = 0 are valid.
+ * The frame.  R, T, fx, cx, fy, cy and s as in endo_fusion_render (x = R (s x_cam) + t).  A frame whose s is not finite and positive
+ *   renders nothing: flag ENDO_FUSION_FRAME_BAD_SCALE; every other frame ENDO_FUSION_FRAME_OK.
+ * A vertex x in (scaled) camera coordinates: q = x - T, p_a = (R[0][a] q_0 + R[1][a] q_1) + R[2][a] q_2.
+ * Pixel (u, v) against triangle (a, b, c), their p written a, b, c:  d_x = (float(u) - cx) / fx, d_y = (float(v) - cy) / fy;  the
+ *   sheared vertices A_x = a_x - d_x a_z, A_y = a_y - d_y a_z, B and C likewise;  f(P, Q) = P_x Q_y - P_y Q_x (two rounded products, then
+ *   the difference, so f(Q, P) = -f(P, Q) exactly: no fused multiply-add);  U = f(C, B), V = f(A, C), W = f(B, A);
+ *   det = (U + V) + W;  t = ((U a_z + V b_z) + W c_z) / det.  The pixel HITS the triangle when
+ *     U, V, W are all >= 0 or all <= 0;
+ *     neither A_x, B_x, C_x nor A_y, B_y, C_y are all > 0 or all < 0 (the span rule: in exact arithmetic it follows from the line
+ *       above; in fp32 it keeps three nearly collinear products from agreeing by rounding far away from the triangle, and it makes
+ *       the pixel box below a statement about these very numbers);
+ *     det != 0, and t is finite and > 0.
+ *   Two triangles on one edge see the same sheared vertices and the same |f| with opposite sign, and zero is inclusive: a closed
+ *   mesh has no cracks.  det > 0 is the FRONT: the face whose right-hand-rule normal (b - a) x (c - a) points to the camera,
+ *   endo_fusion_mesh_faces' outside.  ENDO_MESH_CULL_BACK refuses det < 0, ENDO_MESH_CULL_FRONT det > 0.
+ *   The pixel's hit is the triangle with the smallest t and of equal t the lowest face index.  A pixel with boundaries != NULL and
+ *   not boundaries[v][u] > 0.5 has no hit.
+ * The outputs, device, all 0 where there is no hit except triangle, -1 there; every one but depth may be NULL:
+ *   depth [n][h][w] fp32 = t / s;  mask [n][h][w] fp32 = 1;  triangle [n][h][w] int32;
+ *   barycentric [n][h][w][3] fp32 = U / det, V / det, W / det, the weights of a, b, c;
+ *   normals [n][h][w][3] fp32: with e = b - a, g = c - a of the rows' x, y, z:  v = (e_y g_z - e_z g_y, e_z g_x - e_x g_z,
+ *     e_x g_y - e_y g_x) (f again), n = v / sqrt((v_x v_x + v_y v_y) + v_z v_z) as endo_fusion_mesh_vertices normalises, (0, 0, 0) where
+ *     that length is 0 or not finite, and -n where det < 0: towards the camera;
+ *   colors [n][h][w][3] uint8, only with a stride >= 6: byte c = min(max(rint((beta_0 col_a + beta_1 col_b) + beta_2 col_c), 0), 255)
+ *     of column 5 - c (beta the barycentric output): rows hold r, g, b = colour planes 2, 1, 0, so byte c is plane c, the byte order
+ *     of endo_fusion_render's colours;
+ *   flags [n] int32.
+ * The pixel box.  With a_z, b_z, c_z all > 0 and fx > 0, A_x falls as u grows and changes sign about u = fx a_x / a_z + cx: left of the
+ *   smallest of the three such numbers all are > 0, right of the largest all < 0, and the span rule refuses.  The kernel tests the
+ *   pixels between them, 1 / 16 pixel and 2^-19 of the coordinate wider, clipped to the image; a triangle with a vertex that is not in
+ *   front of the camera, or a number that is not finite, takes the whole image; one with a_z, b_z, c_z all <= 0 is dropped (t would be
+ *   a mean of numbers <= 0).  ENDO_MESH_BRUTE tests every pixel against every triangle; every output byte is the same either way.
+ *
+ * endo_mesh_render_tile(which): 0, 1: the pixel tile of one wave of the queue pass (x, y); 2: the largest box, in pixels, the setup
+ *   pass tests in place; 3: the threads of a block.
+ * endo_mesh_render_workspace_bytes(n, h, w, triangles): 8 bytes per pixel (the keys), 256 (the queue's count) and 8 per (frame,
+ *   triangle) (the queue), each rounded up to 256; -1 outside endo_evaluate_posed's sizes or for triangles outside 0 .. 2^31 - 1.
+ * endo_mesh_render: four launches whatever n is (two with T = 0), no host read: clear, setup (a thread per frame and triangle), queue
+ *   (a wave per queued triangle) and resolve (a thread per pixel); hits meet in a 64-bit atomic minimum per pixel on
+ *   (bits of t) << 32 | face.  intrinsics [n][3][3] fp32, rotations [n][3][3] and translations [n][3] fp64, scales [n] fp32 or NULL,
+ *   boundaries [n][h][w] fp32 or NULL: all on the device.  ENDO_E_BADARG before any device work for a NULL or misaligned input, a
+ *   NULL depth, a stride < 3, colors with a stride < 6, both cull bits, unknown options, sizes outside the above or a workspace that
+ *   is too small.  The mesh is only read.  workspace: SCRATCH.
+ * ------------------------------------------------------------------------------------------- */
+#define ENDO_MESH_CULL_BACK 1
+#define ENDO_MESH_CULL_FRONT 2
+#define ENDO_MESH_BRUTE 4
+int endo_mesh_render_tile(int which);
+int64_t endo_mesh_render_workspace_bytes(int frames, int height, int width, int64_t triangles);
+int endo_mesh_render(const float* vertices, int64_t vertex_stride, int64_t vertex_count, const int32_t* faces, int64_t triangles,
+                     const float* intrinsics, const double* rotations, const double* translations, const float* scales,
+                     const float* boundaries, int frames, int height, int width, int options, float* depth, float* mask,
+                     int32_t* triangle, float* barycentric, float* normals, uint8_t* colors, int32_t* flags, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
